@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- GNNML3 training-step throughput on ZINC-12k-shaped synthetic graphs (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--batch GRAPHS_PER_GPU | --global-batch GRAPHS]
+    python bench.py --gpus N --steps K --warmup W [--batch GRAPHS_PER_GPU | --global-batch GRAPHS] [--dump-outputs DIR]
+
+K is the number of timed steps.  --dump-outputs DIR writes what the last of them returned (loss, parameters, gradients) as
+DIR/<name>.npy; the inputs and the initial parameters are seeded, so two builds run with the same arguments can be compared
+output for output.
 
 A step = forward + L1-sum loss + backward + (N>1: one flat SUM all-reduce of the gradients) + Adam,
 of the reference's ZINC GNNML3 (Zinc12k.py:310-371: 4 x ML3Layer 30+2, S = 8 supports, 25 input
@@ -148,12 +152,15 @@ def write_extras(res):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='K: the number of timed steps')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=131072, help='graphs per GPU per step (SURVEY s8d: 65,536 .. 262,144 for the roofline run)')
     ap.add_argument('--global-batch', type=int, default=0, help='strong scaling: total graphs per step, split over the ranks')
     ap.add_argument('--pool', type=int, default=2048, help='distinct synthetic graphs (tiled to --batch)')
-    ap.add_argument('--min-seconds', type=float, default=3.0, help='repeat the K-step block until this much GPU time; the median block is reported')
+    ap.add_argument('--min-seconds', type=float, default=3.0, help='before the timed steps, keep the GPU busy this long with the same '
+                    'step on a copy of the model (the timed steps and their outputs are the same whatever this is)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write what the last timed step '
+                    'returned to its caller as DIR/<name>.npy: the loss, the parameters the step left and their gradients')
     ap.add_argument('--cpu-graphs', type=int, default=2048)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-profile', action='store_true', help='skip the live per-kernel HIP-event timing and the extra measurements')
@@ -163,6 +170,24 @@ def parse_args():
     ap.add_argument('--ref-batch', type=int, default=64, help='also time the reference batch size (Zinc12k.py:20) as a '
                     'HIP-graph-captured step; 0 = skip')
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what one training step hands its caller -- the loss it returns, the parameters it leaves in the model and
+    their gradients -- as out_dir/<name>.npy in float32 (loss.npy, param.<name>.npy, grad.<name>.npy).  The model is small
+    (33,309 parameters): the whole of it is written, far below 64 MB.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss': loss}
+    for n, p in model.named_parameters():
+        arrays['param.' + n] = p
+        arrays['grad.' + n] = p.grad
+    nbytes = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        nbytes += a.nbytes
+    assert nbytes <= 64 << 20, nbytes
+    return nbytes
 
 
 def spawn_ranks(args):
@@ -470,29 +495,43 @@ def main():
         step()
     fence()
     log('warm-up done')
-    # EXACTLY K steps per block, bracketed by barrier + synchronize; the block is repeated until min-seconds of GPU time
-    # have passed (so that a sampler sees the GPU busy) and the MEDIAN block is reported.  Kernel events: last block.
-    # (all ranks take the same number of blocks: the decision is made on rank 0's clock and broadcast)
-    # (the cyclic garbage collector is parked for the timed blocks, as timeit does: a generation-2 pass is a ~65 ms host stall,
-    #  which in the block that records two HIP events per launch shows up as GPU idle time inside one event pair)
+    def settle():
+        """--min-seconds: keep the GPU busy that long right before the timed steps (so that a sampler sees it busy, and the timed
+        steps run at the steady-state rate) with the same step on a COPY of the model and optimizer.  The copy is dropped: the timed steps
+        start from the model the warm-up left, so what they compute does not depend on how many settling steps the clock allowed.
+        (all ranks take the same number of blocks: rank 0's clock decides)"""
+        import copy
+        twin = copy.deepcopy(model)
+        twin_trainer = TrainStep(twin, lambda mod, d_: models.zinc_step_loss(mod, d_), torch.optim.Adam(twin.parameters(), lr=1e-3, fused=True),
+                                 sync=FlatGradSync(twin.parameters()))
+        busy = 0.0
+        while True:
+            busy += timed_block(lambda: twin_trainer.step(data), args.steps)[0]
+            more = busy < args.min_seconds
+            if world > 1:
+                flag = torch.tensor([1 if more else 0], device=dev)
+                dist.broadcast(flag, 0)
+                more = bool(flag.item())
+            if not more:
+                return busy
+
+    # EXACTLY K timed steps, bracketed by barrier + synchronize.  Kernel events come from one more K-step block after them.
+    # (the cyclic garbage collector is parked first, as timeit does: a collection is a host stall that leaves the GPU idle -- a
+    #  full one between the settling and the timed steps made the 20 timed steps ~1.5 % slower; a generation-2 pass (~65 ms)
+    #  in the block that records two HIP events per launch shows up as GPU idle time inside one event pair)
     import gc
     gc.collect()
     gc.disable()
     try:
-        blocks, total = [], 0.0
-        while True:
-            last = total + (blocks[-1] if blocks else 0) >= args.min_seconds or len(blocks) >= 63
-            if world > 1:
-                flag = torch.tensor([1 if last else 0], device=dev)
-                dist.broadcast(flag, 0)
-                last = bool(flag.item())
-            if last and not args.no_profile:
-                Fn.PROFILE = {}
-            dt, loss = timed_block(step, args.steps)
-            blocks.append(dt)
-            total += dt
-            if last:
-                break
+        if args.min_seconds > 0:
+            log('settled: %.2f s of steps on a copy of the model' % settle())
+        own_dt, loss = timed_block(step, args.steps)
+        if args.dump_outputs and rank == 0:
+            nbytes = dump_outputs(args.dump_outputs, loss, model)
+            log('outputs of the last timed step: %.1f KB in %s' % (nbytes / 1024, args.dump_outputs))
+        if not args.no_profile:
+            Fn.PROFILE = {}
+            timed_block(step, args.steps)
     finally:
         gc.enable()
     prof, Fn.PROFILE = Fn.PROFILE, None
@@ -502,10 +541,8 @@ def main():
             n = max(len(ms) // args.steps, 1)
             log('launches of %s: %s' % (tag, [round(sum(ms[i::n]) / args.steps, 3) for i in range(n)]))
             log('   first launch of every step: %s' % [round(v, 2) for v in ms[0::n]])
-        log('blocks: %s' % [round(b, 4) for b in blocks])
-    dt = float(np.median(blocks))
-    log('timed region: %d blocks of %d steps, median %.3f s (min %.3f, max %.3f)' % (len(blocks), args.steps, dt, min(blocks), max(blocks)))
-    tt = torch.tensor([dt], dtype=torch.float64, device=dev)
+    log('timed region: %d steps, %.3f s' % (args.steps, own_dt))
+    tt = torch.tensor([own_dt], dtype=torch.float64, device=dev)
     gcount = torch.tensor([data.num_graphs], dtype=torch.int64, device=dev)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -528,10 +565,10 @@ def main():
     assert np.isfinite(lossv) or os.environ.get('GML_BENCH_NOCHECK'), 'loss diverged'   # (NOCHECK: ablation builds)
     dp = None
     if world > 1:
-        # ---- what the collective costs (every rank runs this: collectives): each rank's own median block, the flat gradient
+        # ---- what the collective costs (every rank runs this: collectives): each rank's own timed steps, the flat gradient
         #      all-reduce alone, and the reference's batch size per rank as ONE captured HIP graph with the all-reduce inside
         from gnn_matlang_amd.dist import TrainStep
-        own = torch.tensor([float(np.median(blocks)) / args.steps * 1e3], dtype=torch.float64, device=dev)
+        own = torch.tensor([own_dt / args.steps * 1e3], dtype=torch.float64, device=dev)
         per_rank = [torch.zeros_like(own) for _ in range(world)]
         dist.all_gather(per_rank, own)
         nparam = sum(p.numel() for p in model.parameters())
@@ -583,7 +620,7 @@ def main():
                                graphs_per_gpu=data.num_graphs, global_batch=graphs, nodes_per_gpu=int(data.x.size(0)),
                                support_edges_per_gpu=int(data.edge_index2.size(1)), supports=8,
                                parallelism='dp%d' % world, params=sum(p.numel() for p in model.parameters())),
-                   final_loss=lossv, blocks=len(blocks), block_seconds=[round(b, 4) for b in blocks],
+                   final_loss=lossv, blocks=1, block_seconds=[round(own_dt, 4)],
                    n_ranks_seen=dist.get_world_size() if world > 1 else 1,
                    rccl_version='.'.join(str(v) for v in torch.cuda.nccl.version()) if (world > 1 and not share) else None)
         try:                                                   # share of the support rows the edge branch evaluates (the rest: bitwise mirrors)

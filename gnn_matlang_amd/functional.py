@@ -18,7 +18,7 @@ from .graph import _ptr, _stream, _require_cuda
 
 
 # ---------------------------------------------------------------------------- live kernel timing
-# bench.py sets PROFILE = {} for the timed region: every tagged launch is then bracketed by two HIP
+# bench.py sets PROFILE = {} for one profiled block: every tagged launch is then bracketed by two HIP
 # events recorded on the stream the kernel runs on, with its algorithmic bytes / flops.
 PROFILE = None
 

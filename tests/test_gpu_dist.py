@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN, ROOT, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +60,25 @@ def test_bench_strong_scaling_shards_one_global_batch():
     sh = d['sharding']
     assert sh['graphs_per_rank'] == [4096] and sh['support_edges_per_rank'][0] == d['config']['support_edges_per_gpu']
     assert abs(sh['max_over_mean'] - 1.0) < 1e-12
+
+
+def test_bench_dump_outputs_after_exactly_the_requested_steps(tmp_path):
+    """--dump-outputs writes the last timed step's loss, parameters and gradients.  --steps is the exact number of timed steps:
+    1 warm-up + 3 timed and 2 warm-up + 2 timed are the same four steps on the same seeded inputs, in two fresh processes, so
+    every array agrees (one more Adam step would move the parameters by ~1e-3) -- also when the first run settles the GPU for
+    --min-seconds on a copy of the model before its timed steps."""
+    runs = []
+    for warm, steps, settle in ((1, 3, '0.5'), (2, 2, '0')):
+        out = tmp_path / ('w%d_s%d' % (warm, steps))
+        d = _run_bench(['--gpus', '1', '--batch', '2048', '--no-profile', '--warmup', str(warm), '--steps', str(steps),
+                        '--min-seconds', settle, '--dump-outputs', str(out)])
+        assert d['steps'] == steps
+        runs.append({f[:-4]: np.load(out / f) for f in os.listdir(out)})
+    a, b = runs
+    assert set(a) == set(b) and 'loss' in a and len(a) == 1 + 2 * len([k for k in a if k.startswith('param.')])
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert rel_err(a[k], b[k]) <= 1e-5, (k, rel_err(a[k], b[k]))
 
 
 def test_bench_two_ranks_share_the_device_over_gloo():

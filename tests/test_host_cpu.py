@@ -287,6 +287,22 @@ def _load_bench():
     return mod
 
 
+def test_bench_dump_outputs_writes_loss_parameters_and_gradients(tmp_path):
+    """bench.dump_outputs (--dump-outputs): one float32 .npy per array the step hands back -- the loss, every parameter, every gradient."""
+    bench = _load_bench()
+    m = torch.nn.Linear(3, 2)
+    loss = m(torch.ones(4, 3)).sum()
+    loss.backward()
+    out = tmp_path / 'out'
+    nbytes = bench.dump_outputs(str(out), loss.detach(), m)
+    assert sorted(os.listdir(out)) == ['grad.bias.npy', 'grad.weight.npy', 'loss.npy', 'param.bias.npy', 'param.weight.npy']
+    for name, t in (('loss', loss), ('param.weight', m.weight), ('param.bias', m.bias), ('grad.weight', m.weight.grad),
+                    ('grad.bias', m.bias.grad)):
+        a = np.load(out / (name + '.npy'))
+        assert a.dtype == np.float32 and np.array_equal(a, t.detach().numpy()), name
+    assert nbytes == 4 * (1 + 2 * (6 + 2))
+
+
 def test_bench_line_is_compact():
     """a 24 KB line made the driver's record unparseable.  The contract line is built from the full record by
     bench.compact_line: json.loads round-trips, < 8,000 characters (budget 6,000), roofline + cpu_baseline + config kept
