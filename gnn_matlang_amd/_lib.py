@@ -24,11 +24,18 @@ SIGNATURES = {
     'gml_csr_group_info': (ctypes.c_int, [_p, _p, _i64, _i32, _p, _p]),
     'gml_csr_group_info2': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p]),
     'gml_batch_assemble': (ctypes.c_int, [_p, _p]),
+    'gml_batch_assemble_edges': (ctypes.c_int, [_p, _p]),
     'gml_bn_workspace_bytes': (ctypes.c_size_t, [_i64]),
     'gml_bn_stats': (ctypes.c_int, [_p, _i64, _i64, _i32, ctypes.c_float, _p, _p, _p, _p, ctypes.c_size_t, _p]),
     'gml_bn_apply': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
     'gml_bn_bwd_sums': (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, ctypes.c_size_t, _p]),
     'gml_bn_bwd_apply': (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    'gml_bn_masked_workspace_bytes': (ctypes.c_size_t, [_i64]),
+    'gml_bn_masked_stats': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, ctypes.c_float, _p, _p, _p, _p, _p, ctypes.c_size_t, _p]),
+    'gml_bn_masked_apply': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    'gml_bn_masked_bwd_sums': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _p, _p, _p, ctypes.c_size_t, _p]),
+    'gml_bn_masked_bwd_apply': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    'gml_bn_masked_running_update': (ctypes.c_int, [_p, _p, _p, _i32, ctypes.c_float, _p, _p, _p]),
     'gml_gather_rows': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p]),
     'gml_gather_rows_presplit': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _p]),
     'gml_scatter_rows': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p]),
@@ -137,6 +144,13 @@ class BatchDesc(ctypes.Structure):
                [('G', _i64), ('E2all', _i64), ('F', _i32), ('S', _i32), ('ids', _p), ('B', _i32), ('n_pad', _i32), ('e2_pad', _i32), ('dmax', _i32)] + \
                [(n, _p) for n in ('x_out', 'ea_out', 'es_out', 'y_out', 'valid_out', 'ptr_out', 'batch_out', 'rowptr', 'col', 'perm', 'rowptr_t',
                                   'col_t', 'pos_t')] + [('ldx_out', _i32), ('nblk_main', _i32), ('ginfo128', _p), ('ginfo_t128', _p)]
+
+
+class BatchEdgesDesc(ctypes.Structure):
+    """gml_batch_edges_desc of include/gml.h"""
+    _fields_ = [(n, _p) for n in ('node_ptr', 'edge_ptr', 'edge_index', 'tperm', 'sperm', 'pos', 'tpos', 'rp_src', 'rp_dst')] + \
+               [('G', _i64), ('Eall', _i64), ('ids', _p), ('B', _i32), ('n_pad', _i32), ('e_pad', _i32), ('deal', _i32)] + \
+               [(n, _p) for n in ('rowptr', 'col', 'perm', 'rowptr_t', 'col_t', 'perm_t', 'pos_t', 'tpos_out', 'ginfo128', 'ginfo_t128')]
 
 
 GML_OK, GML_E_BADARG, GML_E_UNSUPPORTED, GML_E_WORKSPACE = 0, -1, -2, -3

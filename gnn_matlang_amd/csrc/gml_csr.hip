@@ -504,3 +504,86 @@ extern "C" int gml_batch_assemble(const gml_batch_desc* d, gml_stream_t stream) 
     hipLaunchKernelGGL(gml_k_batch_assemble, dim3((unsigned)(dd.nblk_main + extra)), dim3(256), lds, (hipStream_t)stream, dd);
     return gml_launch_status();
 }
+
+// =============================================================================================
+// gml_batch_assemble_edges: the RAW adjacency of the same padded batch (the GNNML1 models' SpectConv(K = 1) over edge_index,
+// mutag.py:253, sr25.py:231) from its per-graph structure: both views are per-graph arrays plus the graph's node / edge offset.
+// The raw edges need not be sorted by source, so the source view carries its own stable sort (sperm) instead of the identity.
+// Padding: unit-valued self loops dealt `deal` per padding node, on padding nodes only.
+// =============================================================================================
+__global__ __launch_bounds__(256) void gml_k_batch_assemble_edges(const gml_batch_edges_desc d) {
+    extern __shared__ int64_t sh[];                          // nlo[B], elo[B], nnew[B + 1], enew[B + 1]
+    int64_t* nlo = sh;
+    int64_t* elo = sh + d.B;
+    int64_t* nnew = sh + 2 * d.B;
+    int64_t* enew = sh + 3 * d.B + 1;
+    const int B = d.B;
+    for (int g = threadIdx.x; g < B; g += blockDim.x) {
+        const int64_t id = d.ids[g];
+        const bool has = id >= 0 && id < d.G;
+        const int64_t ic = has ? id : 0;
+        nlo[g] = d.node_ptr[ic];
+        elo[g] = d.edge_ptr[ic];
+        nnew[g + 1] = has ? d.node_ptr[ic + 1] - d.node_ptr[ic] : 0;
+        enew[g + 1] = has ? d.edge_ptr[ic + 1] - d.edge_ptr[ic] : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        nnew[0] = 0; enew[0] = 0;
+        for (int g = 0; g < B; ++g) { nnew[g + 1] += nnew[g]; enew[g + 1] += enew[g]; }
+    }
+    __syncthreads();
+    const int64_t n_real = nnew[B] < d.n_pad ? nnew[B] : d.n_pad, e_real = enew[B] < d.e_pad ? enew[B] : d.e_pad;
+    auto seg_of = [&](const int64_t* ptr, int64_t i) {       // first g with ptr[g + 1] > i (i below ptr[B])
+        int lo = 0, hi = B;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (ptr[mid + 1] > i) hi = mid; else lo = mid + 1; }
+        return lo;
+    };
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // ---- nodes: row pointers of both views
+    if (i <= d.n_pad) {
+        if (i == d.n_pad) { d.rowptr[i] = d.e_pad; d.rowptr_t[i] = d.e_pad; }
+        else if (i < n_real) {
+            const int g = seg_of(nnew, i);
+            const int64_t src = i - nnew[g] + nlo[g];
+            d.rowptr_t[i] = (int32_t)(enew[g] + d.rp_src[src]);
+            d.rowptr[i] = (int32_t)(enew[g] + d.rp_dst[src]);
+        } else {
+            const int64_t r = e_real + (i - n_real) * (int64_t)d.deal;
+            d.rowptr_t[i] = d.rowptr[i] = (int32_t)(r < d.e_pad ? r : d.e_pad);
+        }
+    }
+    // ---- edges
+    if (i < d.e_pad) {
+        if (i < e_real) {
+            const int g = seg_of(enew, i);
+            const int64_t sp = elo[g] + (i - enew[g]), base = nnew[g];
+            const int64_t tp = d.tperm[sp], sq = d.sperm[sp];
+            d.col[i] = (int32_t)(d.edge_index[elo[g] + tp] + base);                  // source of the k-th target-sorted edge
+            d.perm[i] = (int32_t)(enew[g] + tp);
+            d.col_t[i] = (int32_t)(d.edge_index[d.Eall + elo[g] + sq] + base);       // target of the k-th source-sorted edge
+            d.perm_t[i] = (int32_t)(enew[g] + sq);
+            d.pos_t[i] = (int32_t)(enew[g] + d.pos[sp]);
+            d.tpos_out[i] = (int32_t)(enew[g] + d.tpos[sp]);
+        } else {
+            int64_t node = n_real + (i - e_real) / d.deal;
+            if (node > d.n_pad - 1) node = d.n_pad - 1;
+            d.col[i] = d.col_t[i] = (int32_t)node;
+            d.perm[i] = d.perm_t[i] = d.pos_t[i] = d.tpos_out[i] = (int32_t)i;
+        }
+    }
+}
+
+extern "C" int gml_batch_assemble_edges(const gml_batch_edges_desc* d, gml_stream_t stream) {
+    if (!d || d->B <= 0 || d->B > 4096 || d->n_pad <= 0 || d->e_pad < 0 || d->deal <= 0 || d->G <= 0 || d->Eall < 0) return GML_E_BADARG;
+    if (!d->ids || !d->node_ptr || !d->edge_ptr || (d->Eall > 0 && (!d->edge_index || !d->tperm || !d->sperm || !d->pos || !d->tpos)) ||
+        !d->rp_src || !d->rp_dst || !d->rowptr || !d->col || !d->perm || !d->rowptr_t || !d->col_t || !d->perm_t || !d->pos_t || !d->tpos_out)
+        return GML_E_BADARG;
+    if ((d->ginfo128 == nullptr) != (d->ginfo_t128 == nullptr)) return GML_E_BADARG;
+    const int64_t m = d->n_pad + 1 > d->e_pad ? d->n_pad + 1 : d->e_pad;
+    const size_t lds = (size_t)(4 * d->B + 2) * sizeof(int64_t);
+    hipLaunchKernelGGL(gml_k_batch_assemble_edges, dim3((unsigned)gml_cdiv(m, 256)), dim3(256), lds, (hipStream_t)stream, *d);
+    int rc = gml_launch_status();
+    if (rc != GML_OK || !d->ginfo128) return rc;
+    return gml_csr_group_info2(d->rowptr, d->col, d->ginfo128, d->rowptr_t, d->col_t, d->ginfo_t128, d->n_pad, 128, stream);
+}

@@ -83,9 +83,13 @@ class DeviceDataset(object):
         e = (self.edge_ptr2[1:] - self.edge_ptr2[:-1])
         gid = torch.repeat_interleave(torch.arange(len(self), device=n.device), e)
         deg = torch.bincount(self.edge_index2[0] + self.node_ptr[gid], minlength=int(self.x.size(0)))
-        nmax, n_top, e_top, dmax = [int(v) for v in torch.stack([
+        # the raw adjacency (edge_index): its padded edge count and deal ride on the same host read (additive keys, below)
+        ea_ = (self.edge_ptr[1:] - self.edge_ptr[:-1])
+        gida = torch.repeat_interleave(torch.arange(len(self), device=n.device), ea_)
+        dega = torch.cat([torch.bincount(self.edge_index[r] + self.node_ptr[gida], minlength=int(self.x.size(0))) for r in (0, 1)])
+        nmax, n_top, e_top, dmax, ea_top, dmaxa = [int(v) for v in torch.stack([
             n.max(), torch.topk(n, min(batch_size, n.numel()))[0].sum(), torch.topk(e, min(batch_size, e.numel()))[0].sum(),
-            deg.max()]).tolist()]
+            deg.max(), torch.topk(ea_, min(batch_size, ea_.numel()))[0].sum(), dega.max()]).tolist()]
         dmax = max(dmax, 1)
         e2_pad = (e_top + 63) // 64 * 64
         # padding edges are dealt `deal` per padding node = the data set's mean degree, rounded up: a 128-row group of padding then
@@ -93,14 +97,23 @@ class DeviceDataset(object):
         # of a real group and a one-group-per-workgroup launch waited for them: ZINC batch 64, conv forward 52 -> 23 us)
         deal = max(1, min(dmax, -(-int(self.edge_index2.size(1)) // max(int(self.x.size(0)), 1))))
         n_pad = (n_top + (e2_pad + deal - 1) // deal + 127) // 128 * 128
-        return dict(n_pad=n_pad, e2_pad=e2_pad, dmax=dmax, deal=deal, caps=(128 * dmax, 128 + 2 * nmax))
+        # raw adjacency (batch_padded / batch_assembled with adjacency=True): e_pad edges; the padding edges are unit self loops on
+        # the n_pad - n_top (>= 1: e2_pad >= 1 padding-room nodes above) padding nodes every batch has at least, e_deal per node;
+        # e_caps bound its 128-row groups like caps.  caps64: caps for 64-row groups (the 4-wave kernel families' records)
+        e_pad = (ea_top + 63) // 64 * 64
+        e_deal = max(1, -(-e_pad // max(n_pad - n_top, 1)))
+        return dict(n_pad=n_pad, e2_pad=e2_pad, dmax=dmax, deal=deal, caps=(128 * dmax, 128 + 2 * nmax),
+                    e_pad=e_pad, e_deal=e_deal, e_caps=(128 * max(dmaxa, e_deal, 1), 128 + 2 * nmax), caps64=(64 * dmax, 64 + 2 * nmax))
 
-    def batch_padded(self, ids, bounds):
+    def batch_padded(self, ids, bounds, adjacency=False):
         """The batch of graphs ``ids`` (entries equal to len(self) = no graph) padded to bounds['n_pad'] nodes and
         bounds['e2_pad'] support edges with torch ops of STATIC shapes only (no host read): padding nodes carry zero
         features and form one extra graph (index B) at the end; padding edges are zero-valued self loops dealt bounds['deal'] per
         padding node (sorted by source like the rest; a zero support stays zero through the bias-free edge MLP and moves
-        no gradient).  Returns a Batch with ptr [B + 2], y [B + 1] and ``graph_valid`` [B] (0 for absent graphs)."""
+        no gradient).  Returns a Batch with ptr [B + 2], y [B + 1] and ``graph_valid`` [B] (0 for absent graphs).
+        adjacency=True: also the raw adjacency ``edge_index`` padded to bounds['e_pad'] edges -- each real graph's edges in its own
+        order, offset to its node range, then self loops on padding nodes only, dealt bounds['e_deal'] per padding node (the GNNML1
+        models give them unit values; a padding node never reaches a real one)."""
         n_pad, e2_pad, dmax = bounds['n_pad'], bounds['e2_pad'], bounds.get('deal', bounds['dmax'])
         dev = ids.device
         B = int(ids.numel())
@@ -126,9 +139,14 @@ class DeviceDataset(object):
         ea2 = self.edge_attr2[epos] * eok.unsqueeze(1).to(self.edge_attr2.dtype)
         ptr = torch.cat([nptr, torch.full((1,), n_pad, dtype=torch.int64, device=dev)]).int()
         y = torch.cat([torch.where(has, self.y[idc], torch.zeros_like(self.y[idc])), torch.zeros(1, dtype=self.y.dtype, device=dev)])
-        # (no `edge_index`: the raw adjacency is not padded here -- a consumer of data.csr('edge_index'), e.g. a GNNML1 model or a
-        #  K = 1 raw-adjacency conv, must fail loudly on a padded batch instead of computing on the support edges)
+        # (no `edge_index` unless asked for: a consumer of data.csr('edge_index'), e.g. a GNNML1 model or a K = 1 raw-adjacency conv,
+        #  must fail loudly on a padded batch without it instead of computing on the support edges)
         b = Batch(x=x, edge_index2=ei2, edge_attr2=ea2, batch=nseg, ptr=ptr, y=y, graph_valid=has.to(self.x.dtype))
+        if adjacency:
+            e_pad, e_deal = bounds['e_pad'], bounds['e_deal']
+            apos, aptr, _, aok, asc, ka = layout(self.edge_ptr, e_pad)
+            pad_a = (nptr[-1] + (ka - aptr[-1]).clamp(min=0) // e_deal).clamp(max=n_pad - 1)
+            b.edge_index = torch.where(aok.unsqueeze(0), self.edge_index[:, apos] + nptr[asc].unsqueeze(0), pad_a.unsqueeze(0))
         b.static_caps = bounds['caps']
         b.pad_graph = True                                 # the last graph is padding: pooling skips it (its pooled row is zero)
         return b
@@ -166,12 +184,43 @@ class DeviceDataset(object):
         es = Fn.edge_presplit(self.edge_attr2.contiguous()) if S <= 8 else None
         self._prep = dict(tperm=tperm.contiguous(), tinv=tinv, rp_src=local_rows(src), rp_dst=local_rows(dst), es=es,
                           x=self.x.contiguous(), ea=self.edge_attr2.contiguous(), ei2=self.edge_index2.contiguous(), y=self.y.contiguous())
+        self._prep.update(self.adjacency_structure())
         return self
 
-    def batch_assembled(self, ids, bounds):
+    def adjacency_structure(self):
+        """Per graph, the structure of its raw adjacency (edge_index, any order inside a graph): the stable target AND source sorts
+        of its edges (a_tperm / a_sperm: k-th sorted edge -> input position), the positions that link the two views (a_pos: target-
+        sorted position of the k-th source-sorted edge, a_tpos: the converse), both local row-pointer prefixes -- what
+        csrc/gml_csr.hip gml_batch_assemble_edges offsets per graph.  Torch ops only (prepare() keeps the result)."""
+        dev, Nall, G = self.x.device, int(self.x.size(0)), len(self)
+        EA = int(self.edge_index.size(1))
+        ga = torch.repeat_interleave(torch.arange(G, device=dev), self.edge_ptr[1:] - self.edge_ptr[:-1], output_size=EA)
+        abase, eabase = self.node_ptr[ga], self.edge_ptr[ga]
+        asrc, adst = self.edge_index[0] + abase, self.edge_index[1] + abase
+        ka = torch.arange(EA, device=dev)
+        ot, os_ = torch.sort(adst, stable=True)[1], torch.sort(asrc, stable=True)[1]     # global stable sorts = per-graph stable sorts
+        tinv_a, sinv_a = torch.empty(EA, dtype=torch.int64, device=dev), torch.empty(EA, dtype=torch.int64, device=dev)
+        tinv_a[ot] = ka - eabase[ot]                                       # [input position] -> local target-sorted position
+        sinv_a[os_] = ka - eabase[os_]                                     # [input position] -> local source-sorted position
+        firsta = self.edge_ptr[torch.repeat_interleave(torch.arange(G, device=dev), self.node_ptr[1:] - self.node_ptr[:-1], output_size=Nall)]
+
+        def local_rows_a(keys):
+            cnt = torch.bincount(keys, minlength=Nall)
+            return (torch.cumsum(cnt, 0) - cnt - firsta).int().contiguous()
+        out = dict(a_tperm=(ot - eabase[ot]).int().contiguous(), a_sperm=(os_ - eabase[os_]).int().contiguous(),
+                   a_pos=tinv_a[os_].int().contiguous(), a_tpos=sinv_a[ot].int().contiguous(),
+                   a_rp_src=local_rows_a(asrc), a_rp_dst=local_rows_a(adst), a_ei=self.edge_index.contiguous())
+        out['a_sorted'] = bool((out['a_sperm'] == (ka - eabase).int()).all()) if EA else True   # input order = source order
+        return out
+
+    def batch_assembled(self, ids, bounds, adjacency=False, groups64=False):
         """``batch_padded(ids, bounds)`` AND its index structure (Batch.csr('edge_index2')) in one kernel launch plus the two
         group-record passes, from the per-graph structure ``prepare()`` computed once: bit-identical tensors and CSR arrays
-        (tests/test_gpu_parity.py), no host read, capturable."""
+        (tests/test_gpu_parity.py), no host read, capturable.
+        adjacency=True: also Batch.csr('edge_index'), both views of ``batch_padded(ids, bounds, adjacency=True)``'s raw adjacency
+        (gml_batch_assemble_edges: one launch + its 128-row group records) -- what the GNNML1 models read.
+        groups64=True: also the 64-row group records of the support CSR (maxima: bounds['caps64']) -- the 4-wave kernel families of
+        the exact-product layer of BatchNorm models (mutag GNNML3) read them, and a captured step cannot build them lazily."""
         from . import _lib
         from .graph import GraphCSR, _ptr, _stream
         self.prepare()
@@ -214,6 +263,15 @@ class DeviceDataset(object):
             g.ginfo_t128, g.ginfo128 = both[0], both[1]
             d.ginfo128, d.ginfo_t128 = _ptr(g.ginfo128), _ptr(g.ginfo_t128)  # round 5: the group records of both views come out of the same launch
             _lib.call('gml_batch_assemble', ctypes.addressof(d), st)
+            if groups64:
+                ng = max((n_pad + 63) // 64, 1)
+                rec64 = int(_lib.lib().gml_csr_group_record_ints(64))
+                g64 = torch.empty(2, ng, rec64, **i32)
+                _lib.call('gml_csr_group_info2', _ptr(g.rowptr), _ptr(g.col), _ptr(g64[0]), _ptr(g.rowptr_t), _ptr(g.col_t), _ptr(g64[1]),
+                          n_pad, 64, st)
+                g._ginfo, g._ginfo_t = g64[0], g64[1]
+                g._gmax = g._gmax_t = (int(bounds['caps64'][0]), int(bounds['caps64'][1]))
+            ga = self._assemble_edges(ids, bounds, st) if adjacency else None
         g.gmax_t128 = g.gmax128 = (int(bounds['caps'][0]), int(bounds['caps'][1]))
         g.src_sorted = True
         g.static_shape = True
@@ -223,20 +281,54 @@ class DeviceDataset(object):
         b.static_caps = bounds['caps']
         b.pad_graph = True
         b._csr['edge_index2'] = g
+        if ga is not None:
+            b._csr['edge_index'] = ga
         b._batch_i32 = batch
         return b
 
-    def epoch_static(self, batch_size, generator=None, shuffle=True, bounds=None):
+    def _assemble_edges(self, ids, bounds, st):
+        """GraphCSR of the padded raw adjacency of the graphs ``ids`` (batch_assembled(adjacency=True))."""
+        from . import _lib
+        from .graph import GraphCSR, _ptr
+        import ctypes
+        P = self._prep
+        n_pad, e_pad, dev = bounds['n_pad'], bounds['e_pad'], ids.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        g = GraphCSR()
+        g.N, g.E, g.device = n_pad, e_pad, dev
+        ar = torch.empty(2, n_pad + 1, **i32)
+        ae = torch.empty(6, e_pad, **i32)
+        g.rowptr, g.rowptr_t = ar[0], ar[1]
+        g.col, g.perm, g.col_t, g.perm_t, g.pos_t, g.tpos = ae[0], ae[1], ae[2], ae[3], ae[4], ae[5]
+        ng2 = max((n_pad + 127) // 128, 1)
+        both = torch.empty(2, ng2, int(_lib.lib().gml_csr_group_record_ints(128)), **i32)
+        g.ginfo128, g.ginfo_t128 = both[0], both[1]
+        d = _lib.BatchEdgesDesc()
+        for name, t in (('node_ptr', self.node_ptr), ('edge_ptr', self.edge_ptr), ('edge_index', P['a_ei']), ('tperm', P['a_tperm']),
+                        ('sperm', P['a_sperm']), ('pos', P['a_pos']), ('tpos', P['a_tpos']), ('rp_src', P['a_rp_src']),
+                        ('rp_dst', P['a_rp_dst']), ('ids', ids), ('rowptr', g.rowptr), ('col', g.col), ('perm', g.perm),
+                        ('rowptr_t', g.rowptr_t), ('col_t', g.col_t), ('perm_t', g.perm_t), ('pos_t', g.pos_t), ('tpos_out', g.tpos),
+                        ('ginfo128', g.ginfo128), ('ginfo_t128', g.ginfo_t128)):
+            setattr(d, name, _ptr(t) if t.numel() else None)
+        d.G, d.Eall, d.B, d.n_pad, d.e_pad, d.deal = len(self), int(self.edge_index.size(1)), int(ids.numel()), n_pad, e_pad, bounds['e_deal']
+        _lib.call('gml_batch_assemble_edges', ctypes.addressof(d), st)
+        g.gmax128 = g.gmax_t128 = (int(bounds['e_caps'][0]), int(bounds['e_caps'][1]))
+        g.src_sorted = bool(P['a_sorted'])
+        g.static_shape = True
+        return g
+
+    def epoch_static(self, batch_size, generator=None, shuffle=True, bounds=None, adjacency=False, groups64=False):
         """One shuffled epoch as STATIC-shape batches (``batch_assembled``): no host read per batch, every batch of the same padded
         shape -- absent slots in the last one.  Use the loss form of a padded batch: ``((pre[:B, 0] - b.y[:B]).abs() * b.graph_valid).sum()``
-        (Zinc12k.py:365's L1 sum over the real graphs)."""
+        (Zinc12k.py:365's L1 sum over the real graphs); models.mutag_loss(..., valid=b.graph_valid) for mutag.
+        adjacency / groups64: passed to ``batch_assembled`` (the GNNML1 models need adjacency=True)."""
         G = len(self)
         dev = self.node_ptr.device
         bd = bounds if bounds is not None else self.bounds(batch_size)
         perm = torch.randperm(G, generator=generator).to(dev) if shuffle else torch.arange(G, device=dev)
         perm = torch.cat([perm, torch.full(((-G) % batch_size,), G, dtype=torch.int64, device=dev)])
         for i in range(0, perm.numel(), batch_size):
-            yield self.batch_assembled(perm[i:i + batch_size].contiguous(), bd)
+            yield self.batch_assembled(perm[i:i + batch_size].contiguous(), bd, adjacency=adjacency, groups64=groups64)
 
     def epoch(self, batch_size, generator=None, shuffle=True):
         """yields one shuffled epoch of batches (the DataLoader(shuffle=True) loop of Zinc12k.py:20,359)."""

@@ -847,6 +847,68 @@ class BatchNormFunction(torch.autograd.Function):
         return dx, (sums[1] if weight is not None else None), (sums[0] if ctx.has_bias else None), None
 
 
+class MaskedBatchNormFunction(torch.autograd.Function):
+    """BatchNormFunction over the VALID rows of a padded batch (csrc/gml_bn.hip gml_bn_masked_*): row r takes part iff valid[r] != 0
+    (float32 [N] on the device).  Returns (y, stats [3, C] = batch mean / biased variance / rstd, count [1] = number of valid rows, on
+    the device); y and dx are exact zeros on the other rows.  No host read: capturable.  Raises NotImplementedError for shapes the
+    kernels do not take (there is no unmasked fallback that would be right)."""
+
+    @staticmethod
+    def forward(ctx, x, valid, weight, bias, eps):
+        N, C = int(x.size(0)), int(x.size(1))
+        dev = x.device
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            stats = torch.empty(3, C, dtype=torch.float32, device=dev)
+            count = torch.empty(1, dtype=torch.float32, device=dev)
+            ws = torch.empty(max(int(L.gml_bn_masked_workspace_bytes(N)), 4), dtype=torch.uint8, device=dev)
+            with _Timed('bn_fwd'):
+                rc = L.gml_bn_masked_stats(_ptr(x), int(x.stride(0)), _ptr(valid), N, C, float(eps), _ptr(stats[0]), _ptr(stats[1]),
+                                           _ptr(stats[2]), _ptr(count), _ptr(ws), ws.numel(), st)
+            if rc == _lib.GML_E_UNSUPPORTED:
+                raise NotImplementedError('masked BatchNorm: C <= 64, C % 4 == 0, float4-addressable rows')
+            _lib.check(rc)
+            y = torch.empty(N, C, dtype=torch.float32, device=dev)
+            with _Timed('bn_fwd'):
+                _lib.call('gml_bn_masked_apply', _ptr(x), int(x.stride(0)), _ptr(valid), N, C, _ptr(stats[0]), _ptr(stats[2]), _ptr(weight),
+                          _ptr(bias), _ptr(y), C, st)
+        ctx.save_for_backward(x, valid, weight, stats, count)
+        ctx.has_bias = bias is not None
+        ctx.mark_non_differentiable(stats, count)
+        return y, stats, count
+
+    @staticmethod
+    def backward(ctx, dy, _ds, _dc):
+        x, valid, weight, stats, count = ctx.saved_tensors
+        N, C = int(x.size(0)), int(x.size(1))
+        dev = x.device
+        dy = dy if (dy.stride(1) == 1 and dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0) else dy.contiguous()
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            sums = torch.empty(2, C, dtype=torch.float32, device=dev)
+            ws = torch.empty(max(int(_lib.lib().gml_bn_masked_workspace_bytes(N)), 4), dtype=torch.uint8, device=dev)
+            with _Timed('bn_bwd'):
+                _lib.call('gml_bn_masked_bwd_sums', _ptr(dy), int(dy.stride(0)), _ptr(x), int(x.stride(0)), _ptr(valid), N, C, _ptr(stats[0]),
+                          _ptr(stats[2]), _ptr(sums[0]), _ptr(sums[1]), _ptr(ws), ws.numel(), st)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty(N, C, dtype=torch.float32, device=dev)
+                with _Timed('bn_bwd'):
+                    _lib.call('gml_bn_masked_bwd_apply', _ptr(dy), int(dy.stride(0)), _ptr(x), int(x.stride(0)), _ptr(valid), N, C,
+                              _ptr(stats[0]), _ptr(stats[2]), _ptr(weight), _ptr(sums[0]), _ptr(sums[1]), _ptr(count), _ptr(dx), C, st)
+        return dx, None, (sums[1] if weight is not None else None), (sums[0] if ctx.has_bias else None), None
+
+
+def bn_masked_running_update(count, stats, momentum, running_mean, running_var):
+    """running_mean / running_var <- (1 - momentum) r + momentum stat over a padded batch's valid rows (unbiased variance, n read on
+    the device; n < 2: unchanged) -- gml_bn_masked_running_update, no host read."""
+    dev = running_mean.device
+    with torch.cuda.device(dev):
+        _lib.call('gml_bn_masked_running_update', _ptr(count), _ptr(stats[0]), _ptr(stats[1]), int(stats.size(1)), float(momentum),
+                  _ptr(running_mean), _ptr(running_var), _stream(dev))
+
+
 class TallLinearFunction(torch.autograd.Function):
     """F.linear for a small layer applied to many rows; only the weight gradient g^T x differs from autograd's
     (a K = rows contraction that a library GEMM runs on a single workgroup)."""

@@ -19,7 +19,11 @@ class BatchNorm1d(torch.nn.BatchNorm1d):
     [N, C] input runs on csrc/gml_bn.hip (C <= 64, C % 4 == 0, float4-addressable rows); eval mode, other shapes and dtypes: the
     base class.  GML_TORCH_BN=1 in the environment: always the base class (A/B)."""
 
-    def forward(self, x):
+    def forward(self, x, valid=None):
+        """valid: None (a plain batch: every row counts) or the row validity of a padded static batch (float [N], nonzero = a real row):
+        training statistics, running statistics and gradients then cover the valid rows only (gml_bn_masked_*), y is zero elsewhere."""
+        if valid is not None:
+            return self._forward_masked(x, valid)
         import os
         if not (self.training or self.running_mean is None) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 \
                 or x.size(1) > 64 or x.size(1) % 4 or x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < x.size(1) or x.data_ptr() % 16 \
@@ -36,6 +40,41 @@ class BatchNorm1d(torch.nn.BatchNorm1d):
                 self.running_mean.mul_(1 - m).add_(stats[0], alpha=m)
                 self.running_var.mul_(1 - m).add_(stats[1], alpha=m * n / (n - 1))
         return y
+
+    def _forward_masked(self, x, valid):
+        valid = valid.to(torch.float32).contiguous()
+        if not self.training and self.running_mean is not None:
+            return super().forward(x) * (valid != 0).to(x.dtype).unsqueeze(1)      # running statistics: row by row
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or valid.numel() != x.size(0) or x.size(1) > 64 or x.size(1) % 4 \
+                or x.stride(1) != 1 or x.stride(0) % 4 or x.stride(0) < x.size(1) or x.data_ptr() % 16:
+            raise NotImplementedError('BatchNorm over a padded batch runs on csrc/gml_bn.hip only: float32 CUDA [N, C <= 64], C % 4 == 0, '
+                                      'float4-addressable rows, one validity entry per row')
+        if self.momentum is None and self.running_mean is not None:
+            raise NotImplementedError('BatchNorm over a padded batch: momentum=None (a cumulative average) needs a host read')
+        from .functional import MaskedBatchNormFunction, bn_masked_running_update
+        y, stats, count = MaskedBatchNormFunction.apply(x, valid, self.weight, self.bias, self.eps)
+        if self.running_mean is not None:
+            with torch.no_grad():
+                self.num_batches_tracked += 1
+                bn_masked_running_update(count, stats, self.momentum, self.running_mean, self.running_var)
+        return y
+
+
+def _node_valid(data):
+    """float [N]: 1 for the real nodes of a padded static batch, 0 for its padding nodes (graph B = the last one); cached on the batch."""
+    v = getattr(data, '_node_valid', None)
+    if v is None:
+        v = data._node_valid = (data.batch != int(data.ptr.numel()) - 2).to(torch.float32)
+    return v
+
+
+def _adjacency(data):
+    """data.csr('edge_index'): a padded static batch has it only when built with adjacency=True -- fail loudly otherwise (the support
+    edges are not the raw adjacency)."""
+    if getattr(data, 'pad_graph', False) and 'edge_index' not in data._csr and getattr(data, 'edge_index', None) is None:
+        raise ValueError('this model reads the raw adjacency (edge_index): build the padded batch with adjacency=True '
+                         '(DeviceDataset.batch_padded / batch_assembled / epoch_static)')
+    return data.csr('edge_index')
 
 
 class _SegmentPool(torch.autograd.Function):
@@ -133,10 +172,12 @@ class GNNML3(torch.nn.Module):
 
     def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False):
         x = data.x
-        if getattr(data, 'pad_graph', False) and self.training and (self.bn or self.readout_bn):
-            # the padding nodes / the padding graph's pooled row would enter the batch statistics
-            raise NotImplementedError('BatchNorm models take plain batches: a padded static batch (pad_graph) would count its padding '
-                                      'rows in the statistics')
+        padded = getattr(data, 'pad_graph', False)
+        if padded and self.training and self.readout_bn:
+            # the padding graph's pooled row would enter the batch statistics of the readout BatchNorm
+            raise NotImplementedError('readout BatchNorm takes plain batches: a padded static batch (pad_graph) would count its padding '
+                                      'row in the statistics')
+        nvalid = _node_valid(data) if padded and self.training and self.bn else None     # the bnN layers: real nodes only
         if self.dense_n:
             from .dense_block import dense_supports, spectconv_dense, _library
             sp = getattr(data, '_spT', None)                    # per-batch data, like the CSR
@@ -166,7 +207,8 @@ class GNNML3(torch.nn.Module):
             else:
                 x = layer(x, csr, data.edge_attr2)
             if self.bn:
-                x = getattr(self, 'bn%d' % (i + 1))(x)
+                bn = getattr(self, 'bn%d' % (i + 1))
+                x = bn(x) if nvalid is None else bn(x, valid=nvalid)
         if not pooled:
             x = {'add': global_add_pool, 'mean': global_mean_pool, 'max': global_max_pool}[self.pool](x, data)
         if self.readout_bn:
@@ -216,7 +258,9 @@ class GNNML1Mutag(torch.nn.Module):
 
     def forward(self, data):
         x = data.x
-        csr = data.csr('edge_index')
+        csr = _adjacency(data)
+        # a padded static batch: padding nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only
+        nvalid = _node_valid(data) if getattr(data, 'pad_graph', False) and self.training else None
         ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)      # mutag.py:253
         for i in (1, 2, 3):
             g = lambda n: getattr(self, n % i)
@@ -224,7 +268,7 @@ class GNNML1Mutag(torch.nn.Module):
             if y is None:
                 y = torch.cat([F.relu(g('fc%d1')(x)), F.relu(g('conv%d1')(x, csr, ones)),
                                F.relu(g('fc%d2')(x)) * F.relu(g('fc%d3')(x))], 1)
-            x = g('bn%d')(y)
+            x = g('bn%d')(y) if nvalid is None else g('bn%d')(y, valid=nvalid)
         x = global_mean_pool(x, data)
         return tall_linear(F.relu(tall_linear(x, self.fc1)), self.fc2)
 
@@ -256,7 +300,11 @@ class GNNML1(torch.nn.Module):
 
     def forward(self, data):
         x = data.x
-        csr = data.csr('edge_index')
+        if self.head != 'lin10' and self.training and getattr(data, 'pad_graph', False):
+            # bn1 normalises the pooled rows: the padding graph's row and absent slots would enter its statistics
+            raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
+                                      'graph and absent slots in the statistics of bn1')
+        csr = _adjacency(data)
         ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)      # sr25.py:231
         actid = 0 if self.act is torch.tanh else 1
         for i in (1, 2, 3):
@@ -348,5 +396,17 @@ def mnist_loss(pre, y):                    # libs/metrics_tf.py softmax cross en
     return F.cross_entropy(pre, y.long())
 
 
-def mutag_loss(pre, y):                    # mutag.py:345-348
-    return F.binary_cross_entropy(torch.sigmoid(pre)[:, 0], y, reduction='sum')
+def mutag_loss(pre, y, valid=None):        # mutag.py:345-348
+    """valid: a padded static batch's graph_valid [B] -- the BCE sum over the real graphs of its first B rows (mutag.py:349-351)."""
+    if valid is None:
+        return F.binary_cross_entropy(torch.sigmoid(pre)[:, 0], y, reduction='sum')
+    nl = int(valid.numel())
+    l = F.binary_cross_entropy(torch.sigmoid(pre[:nl, 0]), y[:nl].to(pre.dtype), reduction='none')
+    return (l * valid).sum()
+
+
+def mutag_step_loss(model, data, valid=None):
+    """mutag_loss(model(data), data.y) for plain and padded batches alike (a padded batch: valid = data.graph_valid) -- the
+    ``loss_fn(model, data)`` of dist.TrainStep."""
+    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
+    return mutag_loss(model(data), data.y, valid)

@@ -195,6 +195,26 @@ typedef struct gml_batch_desc {
     int32_t* ginfo128; int32_t* ginfo_t128;
 } gml_batch_desc;
 int gml_batch_assemble(const gml_batch_desc* d, gml_stream_t stream);
+/* The RAW adjacency (edge_index) of the same padded batch, both CSR views, in one launch (a descriptor of its own: gml_batch_desc
+ * keeps its layout).  Data set side, per graph g its raw edges edge_ptr[g]..edge_ptr[g+1] of edge_index [2, Eall] (graph-LOCAL node
+ * ids, any order) and, indexed like those edges (position edge_ptr[g] + k): tperm[.] = input position (inside the graph) of the
+ * graph's k-th TARGET-sorted edge, sperm[.] = the same for the k-th SOURCE-sorted edge (both stable sorts), pos[.] = target-sorted
+ * position of the k-th source-sorted edge, tpos[.] = source-sorted position of the k-th target-sorted edge; rp_src / rp_dst [node] =
+ * number of the graph's edges whose source / target is a smaller node.  ids / B / n_pad: as the gml_batch_assemble call that built the
+ * batch.  Outputs: rowptr / col / perm, rowptr_t / col_t / perm_t, pos_t and tpos exactly as gml_csr_from_coo / _link_transpose give
+ * them for the padded edge_index of dataset.DeviceDataset.batch_padded(adjacency=True): e_pad edges, the real ones in batch order,
+ * then unit-valued self loops on PADDING nodes only, dealt `deal` per padding node (the caller sizes n_pad / e_pad / deal so that
+ * they fit: dataset.DeviceDataset.bounds).  Optional (both or neither): ginfo128 / ginfo_t128, the 128-row group records of the
+ * target- / source-keyed view (gml_csr_group_info, a second launch). */
+typedef struct gml_batch_edges_desc {
+    const int64_t* node_ptr; const int64_t* edge_ptr; const int64_t* edge_index;
+    const int32_t* tperm; const int32_t* sperm; const int32_t* pos; const int32_t* tpos; const int32_t* rp_src; const int32_t* rp_dst;
+    int64_t G, Eall;
+    const int64_t* ids; int32_t B, n_pad, e_pad, deal;
+    int32_t* rowptr; int32_t* col; int32_t* perm; int32_t* rowptr_t; int32_t* col_t; int32_t* perm_t; int32_t* pos_t; int32_t* tpos_out;
+    int32_t* ginfo128; int32_t* ginfo_t128;
+} gml_batch_edges_desc;
+int gml_batch_assemble_edges(const gml_batch_edges_desc* d, gml_stream_t stream);
 /* out[k, :] = in[perm[k], :]   (rows of `width` floats) */
 int gml_gather_rows(const float* in, const int32_t* perm, float* out, int64_t rows, int32_t width,
                     gml_stream_t stream);
@@ -565,6 +585,26 @@ int gml_bn_bwd_sums(const float* dy, int64_t lddy, const float* x, int64_t ldx, 
 int gml_bn_bwd_apply(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t num_rows, int32_t C, const float* mean,
                      const float* rstd, const float* weight, const float* sum_dy, const float* sum_dyxhat, float* dx, int64_t lddx,
                      gml_stream_t stream);
+/* The same over a padded batch (dataset.py static shapes): ROW VALIDITY is device-resident, a per-row float vector row_valid
+ * [num_rows] -- row r takes part iff row_valid[r] != 0 (padding nodes at the end of a node batch, absent graph slots anywhere in a
+ * pooled one).  stats: mean / biased variance over the valid rows, their count n -> count[0] (computed on the device; n == 0: mean 0,
+ * var 0).  apply: y of the valid rows, exact zeros on the others.  bwd_sums: over the valid rows.  bwd_apply: dx of the valid rows
+ * with n = count[0], exact zeros on the others.  running_update: running_mean / running_var <- (1 - momentum) r + momentum stat, the
+ * variance unbiased by n / (n - 1) with n read on the device; n < 2 leaves both untouched.  No host read anywhere (capturable); fixed
+ * reduction order (repeat runs are bitwise equal).  Shapes as above.  ws: gml_bn_masked_workspace_bytes(num_rows). */
+size_t gml_bn_masked_workspace_bytes(int64_t num_rows);
+int gml_bn_masked_stats(const float* x, int64_t ldx, const float* row_valid, int64_t num_rows, int32_t C, float eps, float* mean, float* var,
+                        float* rstd, float* count, void* ws, size_t ws_bytes, gml_stream_t stream);
+int gml_bn_masked_apply(const float* x, int64_t ldx, const float* row_valid, int64_t num_rows, int32_t C, const float* mean, const float* rstd,
+                        const float* weight, const float* bias, float* y, int64_t ldy, gml_stream_t stream);
+int gml_bn_masked_bwd_sums(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* row_valid, int64_t num_rows, int32_t C,
+                           const float* mean, const float* rstd, float* sum_dy, float* sum_dyxhat, void* ws, size_t ws_bytes,
+                           gml_stream_t stream);
+int gml_bn_masked_bwd_apply(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* row_valid, int64_t num_rows, int32_t C,
+                            const float* mean, const float* rstd, const float* weight, const float* sum_dy, const float* sum_dyxhat,
+                            const float* count, float* dx, int64_t lddx, gml_stream_t stream);
+int gml_bn_masked_running_update(const float* count, const float* mean, const float* var, int32_t C, float momentum, float* running_mean,
+                                 float* running_var, gml_stream_t stream);
 
 /* out[i, j] = sum_r A[r, i] * B[r, j]  (a, b <= 64): weight gradient g^T x of a small dense layer over n rows
  * (readout head fc1 / fc2, Zinc12k.py:343-345), rows split over the chip, fixed summation order */
