@@ -25,6 +25,9 @@ SIGNATURES = {
     'gml_csr_group_info2': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p]),
     'gml_batch_assemble': (ctypes.c_int, [_p, _p]),
     'gml_batch_assemble_edges': (ctypes.c_int, [_p, _p]),
+    'gml_batch_any_workspace_bytes': (_sz, [_i32]),
+    'gml_batch_scan': (ctypes.c_int, [_p, _p]),
+    'gml_batch_assemble_any': (ctypes.c_int, [_p, _p]),
     'gml_bn_workspace_bytes': (ctypes.c_size_t, [_i64]),
     'gml_bn_stats': (ctypes.c_int, [_p, _i64, _i64, _i32, ctypes.c_float, _p, _p, _p, _p, ctypes.c_size_t, _p]),
     'gml_bn_apply': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
@@ -57,7 +60,9 @@ SIGNATURES = {
     'gml_edge_mlp_fwd_stack6': (ctypes.c_int, [_p, _i32, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     'gml_edge_sym_flags': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p, _p]),
     'gml_edge_mlp_fwd_stack6_sym': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
+    'gml_edge_mlp_fwd_stack6_sym_dev': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     'gml_edge_mlp_bwd_sym_parts': (ctypes.c_int64, [_i64, _i32]),
+    'gml_edge_mlp_bwd_sym_dev': (ctypes.c_int, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, ctypes.c_size_t, _p]),
     'gml_edge_mlp_bwd_sym': (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, ctypes.c_size_t, _p]),
     'gml_edge_mlp_fwd6': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     'gml_spectconv_bwd_mix_relu': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _i32, _i32,
@@ -144,6 +149,12 @@ class BatchDesc(ctypes.Structure):
                [('G', _i64), ('E2all', _i64), ('F', _i32), ('S', _i32), ('ids', _p), ('B', _i32), ('n_pad', _i32), ('e2_pad', _i32), ('dmax', _i32)] + \
                [(n, _p) for n in ('x_out', 'ea_out', 'es_out', 'y_out', 'valid_out', 'ptr_out', 'batch_out', 'rowptr', 'col', 'perm', 'rowptr_t',
                                   'col_t', 'pos_t')] + [('ldx_out', _i32), ('nblk_main', _i32), ('ginfo128', _p), ('ginfo_t128', _p)]
+
+
+class BatchAnyDesc(ctypes.Structure):
+    """gml_batch_any_desc of include/gml.h"""
+    _fields_ = [('b', BatchDesc), ('exact', _i32), ('scanned', _i32)] + \
+               [(n, _p) for n in ('sym_ptr', 'sym_uid', 'sym_mir', 'uid_out', 'mir_out', 'count', 'bad', 'ws')] + [('ws_bytes', _sz)]
 
 
 class BatchEdgesDesc(ctypes.Structure):

@@ -328,33 +328,36 @@ extern "C" int gml_csr_group_info2(const int32_t* rowptr_a, const int32_t* col_a
 // Padding as dataset.DeviceDataset.batch_padded: padding nodes carry zero features and form graph B; padding edges are
 // zero-valued self loops dealt dmax per padding node.
 // =============================================================================================
-__global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc d) {
-    extern __shared__ int64_t sh[];                          // nlo[B], elo[B], nnew[B + 1], enew[B + 1]
-    int64_t* nlo = sh;
-    int64_t* elo = sh + d.B;
-    int64_t* nnew = sh + 2 * d.B;
-    int64_t* enew = sh + 3 * d.B + 1;
+// The any-B extras of gml_batch_assemble_any (unused by gml_batch_assemble): prefixes in global memory instead of LDS, the number of
+// leading graphs that fit (Bv), the exact mode and the unique-row list of the edge branch.
+struct GmlBatchAny {
+    const int64_t* ulo; const int64_t* unew; int64_t Bv;
+    const int32_t* sym_uid; const int32_t* sym_mir; int32_t* uid_out; int32_t* mir_out; int32_t* count;
+    int32_t exact;
+};
+
+// first g in [lo, hi] with ptr[g + 1] > i (the caller knows the answer lies there; i below ptr[B])
+__device__ __forceinline__ int gml_seg_of(const int64_t* ptr, int64_t i, int lo, int hi) {
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ptr[mid + 1] > i) hi = mid; else lo = mid + 1; }
+    return lo;
+}
+
+// ANY = false: gml_batch_assemble (prefixes in LDS, every search over all B graphs).  ANY = true: gml_batch_assemble_any (prefixes in
+// global memory; each workgroup first narrows the graph range its rows / edges / entries fall into, so the per-element search stays
+// short for any B).  nlo / elo: first node / support edge of graph g in the data set; nnew / enew [B + 1]: its first node / edge in the
+// batch (exclusive prefix).
+template <bool ANY>
+__device__ __forceinline__ void gml_batch_assemble_body(const gml_batch_desc& d, const int64_t* nlo, const int64_t* elo, const int64_t* nnew,
+                                                        const int64_t* enew, const GmlBatchAny& a) {
     const int B = d.B;
-    for (int g = threadIdx.x; g < B; g += blockDim.x) {
-        const int64_t id = d.ids[g];
-        const bool has = id >= 0 && id < d.G;
-        const int64_t ic = has ? id : 0;
-        nlo[g] = d.node_ptr[ic];
-        elo[g] = d.edge_ptr2[ic];
-        nnew[g + 1] = has ? d.node_ptr[ic + 1] - d.node_ptr[ic] : 0;
-        enew[g + 1] = has ? d.edge_ptr2[ic + 1] - d.edge_ptr2[ic] : 0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        nnew[0] = 0; enew[0] = 0;
-        for (int g = 0; g < B; ++g) { nnew[g + 1] += nnew[g]; enew[g + 1] += enew[g]; }
-    }
-    __syncthreads();
     const int64_t n_real = nnew[B] < d.n_pad ? nnew[B] : d.n_pad, e_real = enew[B] < d.e2_pad ? enew[B] : d.e2_pad;
-    auto seg_of = [&](const int64_t* ptr, int64_t i) {       // first g with ptr[g + 1] > i (i below ptr[B])
-        int lo = 0, hi = B;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (ptr[mid + 1] > i) hi = mid; else lo = mid + 1; }
-        return lo;
+    __shared__ int rng[6];                                   // ANY: [lo, hi] of the graphs holding this block's nodes, edges, entries
+    // (ANY) graph range of the elements [i0, i1) of a prefix array with `real` elements, by one thread
+    auto narrow = [&](const int64_t* ptr, int64_t i0, int64_t i1, int64_t real, int* out) {
+        if (i1 > real) i1 = real;
+        if (i0 >= i1) { out[0] = 0; out[1] = B; return; }
+        out[0] = gml_seg_of(ptr, i0, 0, B);
+        out[1] = gml_seg_of(ptr, i1 - 1, out[0], B);
     };
     // ---- blocks behind the element blocks: the 128-row group records of both CSR views (gml_csr_group_info's records, computed from the
     //      same formulas the element blocks write -- no block reads another block's output), when the caller wants them
@@ -362,10 +365,14 @@ __global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc
         const int gb = (int)blockIdx.x - d.nblk_main, ngr = (d.n_pad + 127) / 128;
         const int view = gb / ngr;                           // 0: target-keyed (rowptr / col -> ginfo128), 1: source-keyed (-> ginfo_t128)
         const int64_t gidx = gb % ngr;
+        const int t = threadIdx.x;
+        const int64_t r0 = gidx * 128, r1 = min(r0 + 128, (int64_t)d.n_pad);
+        if (ANY && t == 0) narrow(nnew, r0, r1 + 1, n_real, rng);     // (rows r0 .. r1: the record reads the next group's first row too)
+        if (ANY) __syncthreads();
         auto rowptr_of = [&](int64_t r) -> int {
             if (r >= d.n_pad) return d.e2_pad;
             if (r < n_real) {
-                const int g = seg_of(nnew, r);
+                const int g = ANY ? gml_seg_of(nnew, r, rng[0], rng[1]) : gml_seg_of(nnew, r, 0, B);
                 const int64_t src = r - nnew[g] + nlo[g];
                 return (int)(enew[g] + (view ? d.rp_src[src] : d.rp_dst[src]));
             }
@@ -374,7 +381,7 @@ __global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc
         };
         auto col_of = [&](int64_t k) -> int {
             if (k < e_real) {
-                const int g = seg_of(enew, k);
+                const int g = ANY ? gml_seg_of(enew, k, rng[2], rng[3]) : gml_seg_of(enew, k, 0, B);
                 const int64_t sp = elo[g] + (k - enew[g]);
                 return view ? (int)(d.edge_index2[d.E2all + sp] + nnew[g]) : (int)(d.edge_index2[elo[g] + d.tperm[sp]] + nnew[g]);
             }
@@ -385,11 +392,11 @@ __global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc
         __shared__ int red[8];
         __shared__ unsigned char row_of_rank[128];
         __shared__ int rpl[129];
-        const int t = threadIdx.x;
-        const int64_t r0 = gidx * 128, r1 = min(r0 + 128, (int64_t)d.n_pad);
         if (t <= 128) rpl[t] = rowptr_of(min(r0 + t, (int64_t)d.n_pad));
         __syncthreads();
         const int kb = rpl[0], ke = rpl[(int)(r1 - r0)];
+        if (ANY && t == 0) narrow(enew, kb, ke, e_real, rng + 2);
+        if (ANY) __syncthreads();
         int mn = INT32_MAX, mx = -1;
         for (int k = kb + t; k < ke; k += 256) {
             const int c = col_of(k);
@@ -421,29 +428,37 @@ __global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc
         __syncthreads();
         if (t < 128) {                                       // (the dealing of rank blocks to waves: gml_k_group_info, 128-row groups)
             const int wave = t >> 4, i16 = t & 15;
-            const int a = ((wave & 3) + (int)gidx) & 3;
-            const int blk = (wave < 4) ? a : 7 - a;
+            const int aa = ((wave & 3) + (int)gidx) & 3;
+            const int blk = (wave < 4) ? aa : 7 - aa;
             reinterpret_cast<unsigned char*>(rec + 4)[t] = row_of_rank[blk * 16 + i16];
         }
         return;
     }
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t u_real = ANY && a.uid_out ? a.unew[B] : 0;
+    if constexpr (ANY) {
+        const int64_t i0 = (int64_t)blockIdx.x * blockDim.x, i1 = i0 + blockDim.x;
+        if (threadIdx.x == 0) narrow(nnew, i0, i1, n_real, rng);
+        if (threadIdx.x == 64) narrow(enew, i0, i1, e_real, rng + 2);
+        if (threadIdx.x == 128 && a.uid_out) narrow(a.unew, i0, i1, u_real, rng + 4);
+        __syncthreads();
+    }
     const int64_t ldo = d.ldx_out > d.F ? d.ldx_out : d.F;
     // ---- graphs
     if (i <= B + 1) {
-        d.ptr_out[i] = i <= B ? (int32_t)(nnew[i] < d.n_pad ? nnew[i] : d.n_pad) : d.n_pad;
+        if (!ANY || !a.exact || i <= B) d.ptr_out[i] = i <= B ? (int32_t)(nnew[i] < d.n_pad ? nnew[i] : d.n_pad) : d.n_pad;
         if (i < B) {
             const int64_t id = d.ids[i];
-            const bool has = id >= 0 && id < d.G;
+            const bool has = id >= 0 && id < d.G && (!ANY || i < a.Bv);
             d.y_out[i] = has ? d.y[id] : 0.f;
-            d.valid_out[i] = has ? 1.f : 0.f;
-        } else if (i == B) d.y_out[i] = 0.f;
+            if (!ANY || d.valid_out) d.valid_out[i] = has ? 1.f : 0.f;
+        } else if (i == B && !(ANY && a.exact)) d.y_out[i] = 0.f;
     }
     // ---- nodes
     if (i <= d.n_pad) {
         if (i == d.n_pad) { d.rowptr[i] = d.e2_pad; d.rowptr_t[i] = d.e2_pad; }
         else if (i < n_real) {
-            const int g = seg_of(nnew, i);
+            const int g = ANY ? gml_seg_of(nnew, i, rng[0], rng[1]) : gml_seg_of(nnew, i, 0, B);
             const int64_t src = i - nnew[g] + nlo[g];
             for (int f = 0; f < d.F; ++f) d.x_out[i * ldo + f] = d.x[src * d.F + f];
             for (int f = d.F; f < ldo; ++f) d.x_out[i * ldo + f] = 0.f;
@@ -460,7 +475,7 @@ __global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc
     // ---- support edges
     if (i < d.e2_pad) {
         if (i < e_real) {
-            const int g = seg_of(enew, i);
+            const int g = ANY ? gml_seg_of(enew, i, rng[2], rng[3]) : gml_seg_of(enew, i, 0, B);
             const int64_t k = i - enew[g], sp = elo[g] + k, base = nnew[g];
             for (int s = 0; s < d.S; ++s) d.ea_out[i * d.S + s] = d.edge_attr2[sp * d.S + s];
             if (d.es) {
@@ -485,6 +500,183 @@ __global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc
             d.pos_t[i] = d.perm[i] = (int32_t)i;
         }
     }
+    // ---- (ANY) the unique-row list of the edge branch, capacity e2_pad: every graph's entries offset by its first edge, then every padding
+    //      edge (a self loop) as an entry of its own -- the list gml_edge_sym_flags + compaction gives on the assembled batch
+    if constexpr (ANY) {
+        if (a.uid_out && i < d.e2_pad) {
+            if (i < u_real) {
+                const int g = gml_seg_of(a.unew, i, rng[4], rng[5]);
+                const int64_t sp = a.ulo[g] + (i - a.unew[g]);
+                const int32_t m = a.sym_mir[sp];
+                a.uid_out[i] = (int32_t)(enew[g] + a.sym_uid[sp]);
+                a.mir_out[i] = m >= 0 ? (int32_t)(enew[g] + m) : -1;
+            } else if (i < u_real + (d.e2_pad - e_real)) {
+                a.uid_out[i] = (int32_t)(e_real + (i - u_real));
+                a.mir_out[i] = -1;
+            }
+            if (i == 0) *a.count = (int32_t)(u_real + (d.e2_pad - e_real));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gml_k_batch_assemble(const gml_batch_desc d) {
+    extern __shared__ int64_t sh[];                          // nlo[B], elo[B], nnew[B + 1], enew[B + 1]
+    int64_t* nlo = sh;
+    int64_t* elo = sh + d.B;
+    int64_t* nnew = sh + 2 * d.B;
+    int64_t* enew = sh + 3 * d.B + 1;
+    const int B = d.B;
+    for (int g = threadIdx.x; g < B; g += blockDim.x) {
+        const int64_t id = d.ids[g];
+        const bool has = id >= 0 && id < d.G;
+        const int64_t ic = has ? id : 0;
+        nlo[g] = d.node_ptr[ic];
+        elo[g] = d.edge_ptr2[ic];
+        nnew[g + 1] = has ? d.node_ptr[ic + 1] - d.node_ptr[ic] : 0;
+        enew[g + 1] = has ? d.edge_ptr2[ic + 1] - d.edge_ptr2[ic] : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        nnew[0] = 0; enew[0] = 0;
+        for (int g = 0; g < B; ++g) { nnew[g + 1] += nnew[g]; enew[g + 1] += enew[g]; }
+    }
+    __syncthreads();
+    gml_batch_assemble_body<false>(d, nlo, elo, nnew, enew, GmlBatchAny{});
+}
+
+// ---------------------------------------------------------------------------------------------
+// gml_batch_assemble_any: the same batch for ANY B.  The per-graph prefixes live in the workspace (global memory), written by one
+// workgroup that scans the B graphs' node / edge / entry counts in chunks (gml_k_batch_scan), and the element kernel reads them.
+// Workspace (int64): nlo[B] elo[B] ulo[B] nnew[B + 1] enew[B + 1] unew[B + 1] Bv.
+#define GML_BSCAN_T 1024
+#define GML_BSCAN_I 8
+__global__ __launch_bounds__(GML_BSCAN_T) void gml_k_batch_scan(const gml_batch_any_desc a) {
+    const gml_batch_desc& d = a.b;
+    const int64_t B = d.B;
+    int64_t* nlo = (int64_t*)a.ws;
+    int64_t *elo = nlo + B, *ulo = nlo + 2 * B, *nnew = nlo + 3 * B, *enew = nnew + B + 1, *unew = enew + B + 1, *meta = unew + B + 1;
+    __shared__ int64_t wsum[3][GML_BSCAN_T / 64];
+    __shared__ int64_t carry[3];
+    __shared__ int first_bad;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) { carry[0] = carry[1] = carry[2] = 0; nnew[0] = enew[0] = unew[0] = 0; first_bad = (int)B; }
+    __syncthreads();
+    for (int64_t c0 = 0; c0 < B; c0 += GML_BSCAN_T * GML_BSCAN_I) {
+        const int64_t g0 = c0 + (int64_t)t * GML_BSCAN_I;
+        int64_t v[3][GML_BSCAN_I], run[3] = {0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < GML_BSCAN_I; ++j) {
+            const int64_t g = g0 + j;
+            int64_t cn = 0, ce = 0, cu = 0;
+            if (g < B) {
+                const int64_t id = d.ids[g];
+                const bool has = id >= 0 && id < d.G;
+                const int64_t ic = has ? id : 0;
+                nlo[g] = d.node_ptr[ic];
+                elo[g] = d.edge_ptr2[ic];
+                ulo[g] = a.sym_ptr ? a.sym_ptr[ic] : 0;
+                if (has) {
+                    cn = d.node_ptr[ic + 1] - d.node_ptr[ic];
+                    ce = d.edge_ptr2[ic + 1] - d.edge_ptr2[ic];
+                    cu = a.sym_ptr ? a.sym_ptr[ic + 1] - a.sym_ptr[ic] : 0;
+                }
+            }
+            run[0] += cn; run[1] += ce; run[2] += cu;
+            v[0][j] = run[0]; v[1][j] = run[1]; v[2][j] = run[2];
+        }
+        int64_t incl[3] = {run[0], run[1], run[2]};
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int64_t y = __shfl_up(incl[q], off);
+                if (lane >= off) incl[q] += y;
+            }
+        if (lane == 63)
+            for (int q = 0; q < 3; ++q) wsum[q][wave] = incl[q];
+        __syncthreads();
+        int64_t excl[3];
+        for (int q = 0; q < 3; ++q) {
+            int64_t w = carry[q];
+            for (int u = 0; u < wave; ++u) w += wsum[q][u];
+            excl[q] = w + incl[q] - run[q];
+        }
+#pragma unroll
+        for (int j = 0; j < GML_BSCAN_I; ++j) {
+            const int64_t g = g0 + j;
+            if (g < B) { nnew[g + 1] = excl[0] + v[0][j]; enew[g + 1] = excl[1] + v[1][j]; unew[g + 1] = excl[2] + v[2][j]; }
+        }
+        __syncthreads();
+        if (t == GML_BSCAN_T - 1)
+            for (int q = 0; q < 3; ++q) carry[q] = excl[q] + run[q];
+        __syncthreads();
+    }
+    // padded mode: the leading graphs that fit n_pad nodes and e2_pad edges with room for the padding edges (`dmax` per padding node).
+    // A batch past that (repeated ids can exceed the data set's bounds) keeps only those graphs -- a consistent, smaller batch -- and
+    // sets bit 2 of *bad (GraphCSR.check raises)
+    if (!a.exact) {
+        for (int64_t g = t; g < B; g += GML_BSCAN_T) {
+            const int64_t n = nnew[g + 1], e = enew[g + 1];
+            if (n > d.n_pad || e > d.e2_pad || (d.n_pad - n) * (int64_t)d.dmax < d.e2_pad - e) atomicMin(&first_bad, (int)g);
+        }
+        __syncthreads();
+        const int bv = first_bad;
+        if (bv < B) {
+            for (int64_t g = bv + t; g < B; g += GML_BSCAN_T) { nnew[g + 1] = nnew[bv]; enew[g + 1] = enew[bv]; unew[g + 1] = unew[bv]; }
+            if (t == 0 && a.bad) atomicOr(a.bad, 4);
+        }
+    }
+    if (t == 0) meta[0] = a.exact ? B : first_bad;
+}
+
+__global__ __launch_bounds__(256) void gml_k_batch_assemble_any(const gml_batch_any_desc a) {
+    const int64_t B = a.b.B;
+    const int64_t* nlo = (const int64_t*)a.ws;
+    const int64_t *elo = nlo + B, *ulo = nlo + 2 * B, *nnew = nlo + 3 * B, *enew = nnew + B + 1, *unew = enew + B + 1, *meta = unew + B + 1;
+    GmlBatchAny x;
+    x.ulo = ulo; x.unew = unew; x.Bv = meta[0];
+    x.sym_uid = a.sym_uid; x.sym_mir = a.sym_mir; x.uid_out = a.uid_out; x.mir_out = a.mir_out; x.count = a.count;
+    x.exact = a.exact;
+    gml_batch_assemble_body<true>(a.b, nlo, elo, nnew, enew, x);
+}
+
+extern "C" size_t gml_batch_any_workspace_bytes(int32_t B) {
+    return B > 0 ? (size_t)(6 * (int64_t)B + 4) * sizeof(int64_t) : 0;
+}
+
+extern "C" int gml_batch_scan(const gml_batch_any_desc* a, gml_stream_t stream) {
+    if (!a || a->b.B <= 0 || !a->b.ids || !a->b.node_ptr || !a->b.edge_ptr2 || !a->ws) return GML_E_BADARG;
+    if (a->ws_bytes < gml_batch_any_workspace_bytes(a->b.B)) return GML_E_WORKSPACE;
+    if (a->sym_ptr && (!a->sym_uid || !a->sym_mir)) return GML_E_BADARG;
+    if (!a->exact && (a->b.n_pad <= 0 || a->b.e2_pad < 0 || a->b.dmax <= 0)) return GML_E_BADARG;
+    hipLaunchKernelGGL(gml_k_batch_scan, dim3(1), dim3(GML_BSCAN_T), 0, (hipStream_t)stream, *a);
+    return gml_launch_status();
+}
+
+extern "C" int gml_batch_assemble_any(const gml_batch_any_desc* a, gml_stream_t stream) {
+    if (!a) return GML_E_BADARG;
+    const gml_batch_desc* d = &a->b;
+    if (d->B <= 0 || d->n_pad <= 0 || d->e2_pad < 0 || d->dmax <= 0 || d->F <= 0 || d->S <= 0) return GML_E_BADARG;
+    if (!d->ids || !d->node_ptr || !d->edge_ptr2 || !d->x || !d->edge_index2 || !d->edge_attr2 || !d->tperm || !d->tinv || !d->rp_src ||
+        !d->rp_dst || !d->y || !d->x_out || !d->ea_out || !d->y_out || (!a->exact && !d->valid_out) || !d->ptr_out || !d->batch_out ||
+        !d->rowptr || !d->col || !d->perm || !d->rowptr_t || !d->col_t || !d->pos_t)
+        return GML_E_BADARG;
+    if (d->es && (((uintptr_t)d->es | (uintptr_t)d->es_out) & 15)) return GML_E_BADARG;
+    if ((d->ginfo128 == nullptr) != (d->ginfo_t128 == nullptr)) return GML_E_BADARG;
+    if (a->uid_out && (!a->sym_ptr || !a->mir_out || !a->count)) return GML_E_BADARG;
+    if (!a->scanned) {
+        const int rc = gml_batch_scan(a, stream);
+        if (rc != GML_OK) return rc;
+    } else if (!a->ws || a->ws_bytes < gml_batch_any_workspace_bytes(d->B)) {
+        return GML_E_BADARG;
+    }
+    gml_batch_any_desc aa = *a;
+    const int64_t n = (d->n_pad + 1 > d->e2_pad ? d->n_pad + 1 : d->e2_pad);
+    const int64_t m = n > d->B + 2 ? n : (int64_t)d->B + 2;
+    aa.b.nblk_main = (int32_t)gml_cdiv(m, 256);
+    const int extra = d->ginfo128 ? 2 * ((d->n_pad + 127) / 128) : 0;
+    hipLaunchKernelGGL(gml_k_batch_assemble_any, dim3((unsigned)(aa.b.nblk_main + extra)), dim3(256), 0, (hipStream_t)stream, aa);
+    return gml_launch_status();
 }
 
 extern "C" int gml_batch_assemble(const gml_batch_desc* d, gml_stream_t stream) {

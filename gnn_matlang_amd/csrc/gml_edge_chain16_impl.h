@@ -169,13 +169,21 @@ struct GmlChain16WB {
 
 // SYM (round 6, gml_edge_chain_sym_impl.h): tile entry u evaluates edge uid[u] on gout[uid[u]] + gout[mir[u]] (mir < 0: alone); E is
 // then the number of entries
-template <int S, bool SYM = false>
+// DEV (with SYM): the number of entries is *ucount, clamped to [0, E] (E = the capacity the grid was sized for); every workgroup still
+// writes its partial row
+template <int S, bool SYM = false, bool DEV = false>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16_bwd(const uint32_t* __restrict__ es, const float* __restrict__ w1,
                                                                 const float* __restrict__ w2, const float* __restrict__ w3,
                                                                 const float* __restrict__ w4, const float* __restrict__ gout,
                                                                 float* __restrict__ partial, int64_t E, int64_t ntiles,
                                                                 const int32_t* __restrict__ uid = nullptr,
-                                                                const int32_t* __restrict__ mir = nullptr) {
+                                                                const int32_t* __restrict__ mir = nullptr,
+                                                                const int32_t* __restrict__ ucount = nullptr) {
+    if constexpr (DEV) {
+        const int64_t c = *ucount;
+        E = c < 0 ? 0 : (c < E ? c : E);
+        ntiles = (E + 15) / 16;
+    }
     constexpr int H2 = 2 * S, H4 = 4 * S;
     // 4 waves x 12 bf16 tile images (the transposition scratch, see gml_edge_chain_impl.h); the same bytes hold the
     // workgroup's partial sums at the end (5 accumulator tiles at a time)
@@ -222,8 +230,8 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16_bwd(const uint32_t*
     auto fetch = [&](int64_t tt) {                              // unconditional, clamped
         int64_t e = min(tt * 16 + c16, E - 1);
         if constexpr (SYM) {
-            const int32_t m = mir[e];
-            e = uid[e];
+            const int32_t m = (!DEV || e >= 0) ? mir[e] : -1;    // (DEV, an empty list: edge 0 with a zero gradient)
+            e = (!DEV || e >= 0) ? uid[e] : 0;
             const int64_t mm = m >= 0 ? m : e;                  // (no mirror: a readable row, dropped below)
             if constexpr (S % 4 == 0) g2_n = *reinterpret_cast<const f32x4*>(gout + mm * S + qc);
             else {

@@ -58,13 +58,20 @@ __device__ __forceinline__ void gml_chain16x6_load_weights(GmlChain16W6<S>& W, c
 
 // out [E, S]; out_t (optional): the same rows at tpos[e].  SYM (gml_edge_chain_sym_impl.h): tile entry u evaluates edge uid[u] and
 // stores the row to out[uid[u]] and out[mir[u]] (mir < 0: none); E is then the number of entries (tpos / out_t unused)
-template <int S, bool TA, bool SYM = false>
+// DEV (with SYM): the number of entries is *ucount, clamped to [0, E] (E = the capacity the grid was sized for)
+template <int S, bool TA, bool SYM = false, bool DEV = false>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16x6_fwd(const float* __restrict__ ea, const float* __restrict__ w1,
                                                                   const float* __restrict__ w2, const float* __restrict__ w3,
                                                                   const float* __restrict__ w4, float* __restrict__ out,
                                                                   const int32_t* __restrict__ tpos, float* __restrict__ out_t,
                                                                   int64_t E, int64_t ntiles, const int32_t* __restrict__ uid = nullptr,
-                                                                  const int32_t* __restrict__ mir = nullptr) {
+                                                                  const int32_t* __restrict__ mir = nullptr,
+                                                                  const int32_t* __restrict__ ucount = nullptr) {
+    if constexpr (DEV) {
+        const int64_t c = *ucount;
+        E = c < 0 ? 0 : (c < E ? c : E);
+        ntiles = (E + 15) / 16;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c16 = lane & 15, g = lane >> 4;
     GmlChain16W6<S> W;
@@ -80,7 +87,10 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16x6_fwd(const float* 
     auto fetch = [&](int64_t tt, Tile& T) {                     // clamped: always a readable edge
         int64_t ed = min(tt * 16 + c16, E - 1);
         T.sid = 0;
-        if constexpr (SYM) {
+        if constexpr (SYM && DEV) {                             // (an empty list: edge 0, never stored)
+            T.tp = ed >= 0 ? mir[ed] : -1;
+            ed = T.sid = ed >= 0 ? uid[ed] : 0;
+        } else if constexpr (SYM) {
             T.tp = mir[ed];
             ed = T.sid = uid[ed];
         }
@@ -173,10 +183,19 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16x6_fwd(const float* 
 
 template <int S>
 int gml_launch_edge_chain16x6_fwd_sym(const float* ea, const int32_t* uid, const int32_t* mir, int64_t U, const float* w1, const float* w2,
-                                      const float* w3, const float* w4, float* out, hipStream_t st) {
+                                      const float* w3, const float* w4, float* out, hipStream_t st, const int32_t* ucount = nullptr) {
     const int64_t ntiles = gml_cdiv(U, 16);
     int64_t grid = gml_cdiv(ntiles, 8);
     if (grid > 2 * GML_NUM_CU) grid = 2 * GML_NUM_CU;
+    if (ucount) {                                               // U = capacity: the grid covers it, the kernel reads the count
+        if (gml_chain6_accurate_tanh())
+            hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out,
+                               nullptr, nullptr, U, ntiles, uid, mir, ucount);
+        else
+            hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, false, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out,
+                               nullptr, nullptr, U, ntiles, uid, mir, ucount);
+        return gml_launch_status();
+    }
     if (gml_chain6_accurate_tanh())
         hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, nullptr, nullptr, U, ntiles, uid, mir);
     else

@@ -21,16 +21,16 @@ extern "C" int gml_edge_sym_flags(const int32_t* rowptr_t, const int32_t* col_t,
 
 template <int S, int L>
 static int sym_fwd_go(const float* ea, const int32_t* uid, const int32_t* mir, int64_t U, const float* const* w1, const float* const* w2,
-                      const float* const* w3, const float* const* w4, float* const* out, int64_t E, hipStream_t st) {
+                      const float* const* w3, const float* const* w4, float* const* out, int64_t E, hipStream_t st, const int32_t* ucount) {
     GmlChain6Stack<L> a;
     for (int l = 0; l < L; ++l) { a.w1[l] = w1[l]; a.w2[l] = w2[l]; a.w3[l] = w3[l]; a.w4[l] = w4[l]; a.out[l] = out[l]; }
-    return gml_launch_edge_chain6_fwd_sym<S, L>(ea, uid, mir, a, E, U, st);
+    return gml_launch_edge_chain6_fwd_sym<S, L>(ea, uid, mir, a, E, U, st, ucount);
 }
 
-extern "C" int gml_edge_mlp_fwd_stack6_sym(const float* ea, const int32_t* uid, const int32_t* mir, int64_t num_unique, int32_t nlayers,
-                                           const float* const* w1, const float* const* w2, const float* const* w3,
-                                           const float* const* w4, float* const* out, int64_t num_edges, int32_t S, int32_t Sout,
-                                           gml_stream_t stream) {
+// ucount != NULL: num_unique is the capacity of uid / mir and *ucount (device) the number of entries (gml_edge_mlp_fwd_stack6_sym_dev)
+static int fwd_stack6_sym(const float* ea, const int32_t* uid, const int32_t* mir, int64_t num_unique, const int32_t* ucount,
+                          int32_t nlayers, const float* const* w1, const float* const* w2, const float* const* w3,
+                          const float* const* w4, float* const* out, int64_t num_edges, int32_t S, int32_t Sout, gml_stream_t stream) {
     if (num_edges < 0 || num_unique < 0 || num_unique > num_edges || S <= 0 || Sout <= 0 || nlayers <= 0 || !w1 || !w2 || !w3 || !w4 || !out)
         return GML_E_BADARG;
     if (S != Sout || S < 2 || S > 16 || nlayers > 4 || (S != 8 && S != 4 && nlayers > 1)) return GML_E_UNSUPPORTED;
@@ -40,13 +40,28 @@ extern "C" int gml_edge_mlp_fwd_stack6_sym(const float* ea, const int32_t* uid, 
     for (int l = 0; l < nlayers; ++l)
         if (!w1[l] || !w2[l] || !w3[l] || !w4[l] || !out[l] || (S % 4 == 0 && (((uintptr_t)out[l]) & 15) != 0)) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-#define GML_SYM_GO(SV, LV) if (S == SV && nlayers == LV) return sym_fwd_go<SV, LV>(ea, uid, mir, num_unique, w1, w2, w3, w4, out, num_edges, st);
+#define GML_SYM_GO(SV, LV) if (S == SV && nlayers == LV) return sym_fwd_go<SV, LV>(ea, uid, mir, num_unique, w1, w2, w3, w4, out, num_edges, st, ucount);
     GML_SYM_GO(8, 1) GML_SYM_GO(8, 2) GML_SYM_GO(8, 3) GML_SYM_GO(8, 4)
     GML_SYM_GO(4, 1) GML_SYM_GO(4, 2) GML_SYM_GO(4, 3) GML_SYM_GO(4, 4)
     GML_SYM_GO(2, 1) GML_SYM_GO(3, 1) GML_SYM_GO(5, 1) GML_SYM_GO(6, 1) GML_SYM_GO(7, 1)
-#define GML_SYM16_GO(SV) if (S == SV) return gml_launch_edge_chain16x6_fwd_sym<SV>(ea, uid, mir, num_unique, w1[0], w2[0], w3[0], w4[0], out[0], st);
+#define GML_SYM16_GO(SV) if (S == SV) return gml_launch_edge_chain16x6_fwd_sym<SV>(ea, uid, mir, num_unique, w1[0], w2[0], w3[0], w4[0], out[0], st, ucount);
     GML_SYM16_GO(9) GML_SYM16_GO(10) GML_SYM16_GO(11) GML_SYM16_GO(12) GML_SYM16_GO(13) GML_SYM16_GO(14) GML_SYM16_GO(15) GML_SYM16_GO(16)
     return GML_E_UNSUPPORTED;
+}
+
+extern "C" int gml_edge_mlp_fwd_stack6_sym(const float* ea, const int32_t* uid, const int32_t* mir, int64_t num_unique, int32_t nlayers,
+                                           const float* const* w1, const float* const* w2, const float* const* w3,
+                                           const float* const* w4, float* const* out, int64_t num_edges, int32_t S, int32_t Sout,
+                                           gml_stream_t stream) {
+    return fwd_stack6_sym(ea, uid, mir, num_unique, nullptr, nlayers, w1, w2, w3, w4, out, num_edges, S, Sout, stream);
+}
+
+extern "C" int gml_edge_mlp_fwd_stack6_sym_dev(const float* ea, const int32_t* uid, const int32_t* mir, const int32_t* count,
+                                               int64_t capacity, int32_t nlayers, const float* const* w1, const float* const* w2,
+                                               const float* const* w3, const float* const* w4, float* const* out, int64_t num_edges,
+                                               int32_t S, int32_t Sout, gml_stream_t stream) {
+    if (!count || capacity <= 0) return GML_E_BADARG;
+    return fwd_stack6_sym(ea, uid, mir, capacity, count, nlayers, w1, w2, w3, w4, out, num_edges, S, Sout, stream);
 }
 
 extern "C" int64_t gml_edge_mlp_bwd_sym_parts(int64_t num_unique, int32_t S) {
@@ -57,13 +72,17 @@ extern "C" int64_t gml_edge_mlp_bwd_sym_parts(int64_t num_unique, int32_t S) {
 template <int S>
 static int sym_bwd16_go(const uint32_t* es, const int32_t* uid, const int32_t* mir, int64_t U, const float* w1, const float* w2,
                         const float* w3, const float* w4, const float* gout, float* dw1, float* dw2, float* dw3, float* dw4, void* ws,
-                        size_t ws_bytes, hipStream_t st) {
+                        size_t ws_bytes, hipStream_t st, const int32_t* ucount) {
     const int64_t ntiles = gml_cdiv(U, 16);
     const int64_t grid = gml_edge_chain16_bwd_groups(U);
     constexpr int NW = GML_CHAIN16_NW(S);
     if (ws_bytes < (size_t)grid * NW * sizeof(float)) return GML_E_WORKSPACE;
-    hipLaunchKernelGGL((gml_k_edge_chain16_bwd<S, true>), dim3((unsigned)grid), dim3(256), 0, st, es, w1, w2, w3, w4, gout, (float*)ws, U, ntiles,
-                       uid, mir);
+    if (ucount)
+        hipLaunchKernelGGL((gml_k_edge_chain16_bwd<S, true, true>), dim3((unsigned)grid), dim3(256), 0, st, es, w1, w2, w3, w4, gout, (float*)ws, U,
+                           ntiles, uid, mir, ucount);
+    else
+        hipLaunchKernelGGL((gml_k_edge_chain16_bwd<S, true>), dim3((unsigned)grid), dim3(256), 0, st, es, w1, w2, w3, w4, gout, (float*)ws, U, ntiles,
+                           uid, mir);
     int rc = gml_launch_status();
     if (rc != GML_OK || !dw1) return rc;
     const int n123 = 2 * S * S, n4 = S * 4 * S;
@@ -75,13 +94,17 @@ static int sym_bwd16_go(const uint32_t* es, const int32_t* uid, const int32_t* m
 template <int S>
 static int sym_bwd_go(const uint32_t* es, const int32_t* uid, const int32_t* mir, int64_t U, const float* w1, const float* w2,
                       const float* w3, const float* w4, const float* gout, float* dw1, float* dw2, float* dw3, float* dw4, void* ws,
-                      size_t ws_bytes, hipStream_t st) {
+                      size_t ws_bytes, hipStream_t st, const int32_t* ucount) {
     const int64_t ntiles = gml_cdiv(U, 16);
     const int64_t grid = gml_edge_chain_bwd_groups(U, gml_edge_chain_bwd_wgs());
     constexpr int NW = GML_CHAIN_NW(S);
     if (ws_bytes < (size_t)grid * NW * sizeof(float)) return GML_E_WORKSPACE;
-    hipLaunchKernelGGL((gml_k_edge_chain_bwd_sym<S>), dim3((unsigned)grid), dim3(256), 0, st, es, uid, mir, w1, w2, w3, w4, gout,
-                       (float*)ws, U, ntiles);
+    if (ucount)
+        hipLaunchKernelGGL((gml_k_edge_chain_bwd_sym<S, true>), dim3((unsigned)grid), dim3(256), 0, st, es, uid, mir, w1, w2, w3, w4, gout,
+                           (float*)ws, U, ntiles, ucount);
+    else
+        hipLaunchKernelGGL((gml_k_edge_chain_bwd_sym<S>), dim3((unsigned)grid), dim3(256), 0, st, es, uid, mir, w1, w2, w3, w4, gout,
+                           (float*)ws, U, ntiles);
     int rc = gml_launch_status();
     if (rc != GML_OK || !dw1) return rc;                     /* dw1 == NULL: the partials stay in ws (gml_fold_many) */
     const int n123 = 2 * S * S, n4 = S * 4 * S;
@@ -90,10 +113,10 @@ static int sym_bwd_go(const uint32_t* es, const int32_t* uid, const int32_t* mir
     return gml_launch_status();
 }
 
-extern "C" int gml_edge_mlp_bwd_sym(const void* ea_split, const int32_t* uid, const int32_t* mir, int64_t num_unique, const float* w1,
-                                    const float* w2, const float* w3, const float* w4, const float* gout, float* dw1, float* dw2,
-                                    float* dw3, float* dw4, int64_t num_edges, int32_t S, int32_t Sout, void* ws, size_t ws_bytes,
-                                    gml_stream_t stream) {
+// ucount != NULL: num_unique is the capacity of uid / mir and *ucount (device) the number of entries (gml_edge_mlp_bwd_sym_dev)
+static int bwd_sym(const void* ea_split, const int32_t* uid, const int32_t* mir, int64_t num_unique, const int32_t* ucount, const float* w1,
+                   const float* w2, const float* w3, const float* w4, const float* gout, float* dw1, float* dw2, float* dw3, float* dw4,
+                   int64_t num_edges, int32_t S, int32_t Sout, void* ws, size_t ws_bytes, gml_stream_t stream) {
     if (num_edges <= 0 || num_unique <= 0 || num_unique > num_edges || S <= 0 || Sout <= 0) return GML_E_BADARG;
     const bool nofold = !dw1 && !dw2 && !dw3 && !dw4;
     if (!w1 || !w2 || !w3 || !w4 || (!nofold && (!dw1 || !dw2 || !dw3 || !dw4))) return GML_E_BADARG;
@@ -102,10 +125,25 @@ extern "C" int gml_edge_mlp_bwd_sym(const void* ea_split, const int32_t* uid, co
     hipStream_t st = (hipStream_t)stream;
     const uint32_t* es = (const uint32_t*)ea_split;
     switch (S) {
-#define GML_SYM_BWD(SV) case SV: return sym_bwd_go<SV>(es, uid, mir, num_unique, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, ws, ws_bytes, st);
+#define GML_SYM_BWD(SV) case SV: return sym_bwd_go<SV>(es, uid, mir, num_unique, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, ws, ws_bytes, st, ucount);
         GML_SYM_BWD(2) GML_SYM_BWD(3) GML_SYM_BWD(4) GML_SYM_BWD(5) GML_SYM_BWD(6) GML_SYM_BWD(7) GML_SYM_BWD(8)
-#define GML_SYM_BWD16(SV) case SV: return sym_bwd16_go<SV>(es, uid, mir, num_unique, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, ws, ws_bytes, st);
+#define GML_SYM_BWD16(SV) case SV: return sym_bwd16_go<SV>(es, uid, mir, num_unique, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, ws, ws_bytes, st, ucount);
         GML_SYM_BWD16(9) GML_SYM_BWD16(10) GML_SYM_BWD16(11) GML_SYM_BWD16(12) GML_SYM_BWD16(13) GML_SYM_BWD16(14) GML_SYM_BWD16(15) GML_SYM_BWD16(16)
     }
     return GML_E_UNSUPPORTED;
+}
+
+extern "C" int gml_edge_mlp_bwd_sym(const void* ea_split, const int32_t* uid, const int32_t* mir, int64_t num_unique, const float* w1,
+                                    const float* w2, const float* w3, const float* w4, const float* gout, float* dw1, float* dw2,
+                                    float* dw3, float* dw4, int64_t num_edges, int32_t S, int32_t Sout, void* ws, size_t ws_bytes,
+                                    gml_stream_t stream) {
+    return bwd_sym(ea_split, uid, mir, num_unique, nullptr, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, num_edges, S, Sout, ws, ws_bytes, stream);
+}
+
+extern "C" int gml_edge_mlp_bwd_sym_dev(const void* ea_split, const int32_t* uid, const int32_t* mir, const int32_t* count, int64_t capacity,
+                                        const float* w1, const float* w2, const float* w3, const float* w4, const float* gout, float* dw1,
+                                        float* dw2, float* dw3, float* dw4, int64_t num_edges, int32_t S, int32_t Sout, void* ws,
+                                        size_t ws_bytes, gml_stream_t stream) {
+    if (!count) return GML_E_BADARG;
+    return bwd_sym(ea_split, uid, mir, capacity, count, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, num_edges, S, Sout, ws, ws_bytes, stream);
 }

@@ -80,10 +80,18 @@ __global__ __launch_bounds__(256) void gml_k_edge_sym_flags(const int32_t* __res
 
 // ------------------------------------------------------------------------------------------ forward over the unique rows
 // entry u: uid[u] = the edge to evaluate, mir[u] = its mirror (-1: none).  out[l][uid] and out[l][mir] receive the row.
-template <int S, int L, bool TA>
+// DEV: the number of entries is *ucount (read here, clamped to [0, U]; U = the capacity the grid was sized for) -- the list of a batch
+// assembled on the device (gml_batch_assemble_any), whose length the host never reads
+template <int S, int L, bool TA, bool DEV = false>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd_sym(const float* __restrict__ ea, const int32_t* __restrict__ uid,
                                                                    const int32_t* __restrict__ mir, const GmlChain6Stack<L> a,
-                                                                   int64_t E, int64_t U, int64_t ntiles) {
+                                                                   int64_t E, int64_t U, int64_t ntiles,
+                                                                   const int32_t* __restrict__ ucount = nullptr) {
+    if constexpr (DEV) {
+        const int64_t c = *ucount;
+        U = c < 0 ? 0 : (c < U ? c : U);
+        ntiles = (U + 15) / 16;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c16 = lane & 15, g = lane >> 4;
     GmlChain6W<S> W[L];
@@ -101,7 +109,9 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd_sym(const float*
         for (int v = 0; v < 2; ++v) {
             const int64_t u = (tt + v) * 16 + c16;
             const int64_t uc = u < U ? u : U - 1;
-            const int32_t e = uid[uc], m = mir[uc];
+            int32_t e, m;
+            if constexpr (DEV) { e = uc >= 0 ? uid[uc] : 0; m = uc >= 0 ? mir[uc] : -1; }     // (an empty list: edge 0, never stored)
+            else { e = uid[uc]; m = mir[uc]; }
             el[v] = e;
             st[v] = u < U ? (g < 2 ? e : m) : -1;
         }
@@ -179,10 +189,19 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd_sym(const float*
 
 template <int S, int L>
 int gml_launch_edge_chain6_fwd_sym(const float* ea, const int32_t* uid, const int32_t* mir, const GmlChain6Stack<L>& a, int64_t E,
-                                   int64_t U, hipStream_t st) {
+                                   int64_t U, hipStream_t st, const int32_t* ucount = nullptr) {
     const int64_t ntiles = gml_cdiv(U, 16);
     int64_t grid = gml_cdiv(ntiles, 8);
     if (grid > 4 * GML_NUM_CU) grid = 4 * GML_NUM_CU;
+    if (ucount) {                                            // U = capacity: the grid covers it, the kernel reads the count
+        if (gml_chain6_accurate_tanh())
+            hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U,
+                               ntiles, ucount);
+        else
+            hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, false, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U,
+                               ntiles, ucount);
+        return gml_launch_status();
+    }
     if (gml_chain6_accurate_tanh())
         hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U, ntiles);
     else
@@ -194,11 +213,17 @@ int gml_launch_edge_chain6_fwd_sym(const float* ea, const int32_t* uid, const in
 // gml_k_edge_chain_bwd<S, GIN = false, PRE = true> (gml_edge_chain_impl.h) with the index indirection: tile entry u evaluates edge
 // uid[u] on the output gradient gout[uid[u]] + gout[mir[u]].  Same arithmetic (two-piece chain, recomputed intermediates), same
 // partial-sum layout [dw1 | dw2 | dw3 | dw4] per workgroup.
-template <int S>
+// DEV: the entry count is *ucount (clamped to [0, U]), as in gml_k_edge_chain6_fwd_sym; every workgroup still writes its partial row
+template <int S, bool DEV = false>
 __global__ __launch_bounds__(256, GML_SYM_BWD_WGS) void gml_k_edge_chain_bwd_sym(
     const uint32_t* __restrict__ es, const int32_t* __restrict__ uid, const int32_t* __restrict__ mir, const float* __restrict__ w1,
     const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ w4, const float* __restrict__ gout,
-    float* __restrict__ partial, int64_t U, int64_t ntiles) {
+    float* __restrict__ partial, int64_t U, int64_t ntiles, const int32_t* __restrict__ ucount = nullptr) {
+    if constexpr (DEV) {
+        const int64_t c = *ucount;
+        U = c < 0 ? 0 : (c < U ? c : U);
+        ntiles = (U + 15) / 16;
+    }
     constexpr int H2 = 2 * S, H4 = 4 * S;
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 12 * 512];
     float (*red)[20][64] = reinterpret_cast<float (*)[20][64]>(smem);
@@ -239,7 +264,9 @@ __global__ __launch_bounds__(256, GML_SYM_BWD_WGS) void gml_k_edge_chain_bwd_sym
         const int64_t u = tt * 16 + c16;
         const int64_t uc = u < U ? u : U - 1;
         Idx r;
-        r.e = uid[uc]; r.m = mir[uc]; r.ok = u < U;
+        if constexpr (DEV) { r.e = uc >= 0 ? uid[uc] : 0; r.m = uc >= 0 ? mir[uc] : -1; }   // (an empty list: edge 0, zero gradient)
+        else { r.e = uid[uc]; r.m = mir[uc]; }
+        r.ok = u < U;
         return r;
     };
     u32x4 b1_n;

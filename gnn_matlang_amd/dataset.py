@@ -13,6 +13,43 @@ import torch
 from .graph import Batch
 
 
+def pair_support_edges(edge_index2, edge_ptr2, node_ptr, edge_attr2):
+    """Mirror pairing of every graph's support edges (torch only; CPU or GPU tensors), with the semantics of include/gml.h
+    gml_edge_sym_flags: per edge (graph-LOCAL ids, each graph's edges in its own order) flag 2 = evaluate, and its mirror (dst, src)
+    takes the same row (src < dst, the two rows bitwise equal); 0 = covered by its mirror; 1 = evaluate alone (self loops, repeated
+    edges, edges without a mirror or whose mirror differs in any bit).  The mirror is found by a sort of the (src, dst) keys, so the
+    order of the targets inside a source row does not matter.  Returns (flag [E] int32, mirror [E] int64: the mirror's position for
+    flag 2, else -1; sym_ptr [G + 1] int64, uid [U] int32, mir [U] int32): per graph g its entries sym_ptr[g] .. sym_ptr[g + 1] -- the
+    edges with flag > 0 in edge order, as graph-local positions, and their mirror's local position (-1: none)."""
+    dev = edge_index2.device
+    E, G = int(edge_index2.size(1)), int(node_ptr.numel()) - 1
+    e = edge_ptr2[1:] - edge_ptr2[:-1]
+    gid = torch.repeat_interleave(torch.arange(G, device=dev), e, output_size=E)
+    nbase, ebase = node_ptr[gid], edge_ptr2[gid]
+    src, dst = edge_index2[0] + nbase, edge_index2[1] + nbase
+    n = int(node_ptr[-1]) + 1
+    key, mkey = src * n + dst, dst * n + src
+    skey, order = torch.sort(key)
+    dup = torch.searchsorted(skey, key, right=True) - torch.searchsorted(skey, key) > 1
+    mlo = torch.searchsorted(skey, mkey)
+    one_mirror = torch.searchsorted(skey, mkey, right=True) - mlo == 1
+    mpos = order[mlo.clamp(max=max(E - 1, 0))]
+    rows = edge_attr2.contiguous().view(torch.int32)
+    pair = (src != dst) & ~dup & one_mirror
+    same = pair & (rows == rows[mpos]).all(1)
+    flag = torch.ones(E, dtype=torch.int32, device=dev)
+    flag[same & (src > dst)] = 0
+    flag[same & (src < dst)] = 2
+    mirror = torch.where(flag == 2, mpos, torch.full_like(mpos, -1))
+    sel = torch.nonzero(flag > 0, as_tuple=False).view(-1)
+    uid = (sel - ebase[sel]).int()
+    ms = mirror[sel]
+    mir = torch.where(ms >= 0, ms - ebase[sel], ms).int()
+    sym_ptr = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    sym_ptr[1:] = torch.cumsum(torch.bincount(gid[sel], minlength=G), 0)
+    return flag, mirror, sym_ptr, uid, mir
+
+
 class DeviceDataset(object):
     """x [N,F], node_ptr [G+1], edge_index / edge_index2 (graph-LOCAL node ids) with edge_ptr / edge_ptr2 [G+1],
     edge_attr2 [E2,S], y [G]; all on one device."""
@@ -23,6 +60,18 @@ class DeviceDataset(object):
 
     def __len__(self):
         return int(self.node_ptr.numel() - 1)
+
+    def tiled(self, reps):
+        """The data set repeated `reps` times (graph g + k G is graph g): a large data set of known graphs."""
+        dev = self.node_ptr.device
+        k = torch.arange(reps, device=dev).view(-1, 1)
+
+        def ptr(p):
+            return torch.cat([(p[:-1].view(1, -1) + k * p[-1]).reshape(-1), (p[-1:] * reps)])
+        two = lambda t: t.repeat(1, reps) if t is not None else None
+        return DeviceDataset(self.x.repeat(reps, 1), ptr(self.node_ptr), two(self.edge_index), ptr(self.edge_ptr), two(self.edge_index2),
+                             ptr(self.edge_ptr2) if self.edge_ptr2 is not None else None,
+                             self.edge_attr2.repeat(reps, 1) if self.edge_attr2 is not None else None, self.y.repeat(reps))
 
     @staticmethod
     def from_graphs(graphs, device):
@@ -187,6 +236,19 @@ class DeviceDataset(object):
         self._prep.update(self.adjacency_structure())
         return self
 
+    def pairing(self):
+        """The data set's mirror pairing for the edge branch (``pair_support_edges``), computed once per data set (like ``prepare()``'s
+        per-graph structure, which batch_assembled offsets the same way): dict(sym_ptr, uid, mir), or None when it does not pay -- supports of S outside 2 .. 16 (the unique-row kernels) or
+        more than 0.9 E unique rows (the rule GraphCSR.sym_index applies per batch, decided here once per data set)."""
+        if not hasattr(self, '_sym'):
+            S, E = int(self.edge_attr2.size(1)), int(self.edge_index2.size(1))
+            self._sym = None
+            if 2 <= S <= 16 and E > 0:
+                _, _, sym_ptr, uid, mir = pair_support_edges(self.edge_index2, self.edge_ptr2, self.node_ptr, self.edge_attr2)
+                if uid.numel() <= 0.9 * E:
+                    self._sym = dict(sym_ptr=sym_ptr.contiguous(), uid=uid.contiguous(), mir=mir.contiguous())
+        return self._sym
+
     def adjacency_structure(self):
         """Per graph, the structure of its raw adjacency (edge_index, any order inside a graph): the stable target AND source sorts
         of its edges (a_tperm / a_sperm: k-th sorted edge -> input position), the positions that link the two views (a_pos: target-
@@ -213,18 +275,27 @@ class DeviceDataset(object):
         out['a_sorted'] = bool((out['a_sperm'] == (ka - eabase).int()).all()) if EA else True   # input order = source order
         return out
 
-    def batch_assembled(self, ids, bounds, adjacency=False, groups64=False):
+    def batch_assembled(self, ids, bounds, adjacency=False, groups64=False, sym=False):
         """``batch_padded(ids, bounds)`` AND its index structure (Batch.csr('edge_index2')) in one kernel launch plus the two
         group-record passes, from the per-graph structure ``prepare()`` computed once: bit-identical tensors and CSR arrays
         (tests/test_gpu_parity.py), no host read, capturable.
         adjacency=True: also Batch.csr('edge_index'), both views of ``batch_padded(ids, bounds, adjacency=True)``'s raw adjacency
         (gml_batch_assemble_edges: one launch + its 128-row group records) -- what the GNNML1 models read.
         groups64=True: also the 64-row group records of the support CSR (maxima: bounds['caps64']) -- the 4-wave kernel families of
-        the exact-product layer of BatchNorm models (mutag GNNML3) read them, and a captured step cannot build them lazily."""
+        the exact-product layer of BatchNorm models (mutag GNNML3) read them, and a captured step cannot build them lazily.
+        Any B (gml_batch_assemble_any: the per-graph prefixes in global memory; up to 4096 graphs without ``sym`` the single launch above):
+        bounds=None: EXACT mode -- no padding graph, nodes or edges; bit-identical to ``batch(ids)`` + GraphCSR.from_edge_index (ptr
+        [B + 1], y [B], no graph_valid; two host reads per batch: the totals, then the group maxima).  A padded batch of this launch that
+        exceeds bounds (repeated ids) keeps its leading graphs that fit and flags it: csr('edge_index2').check() raises.
+        sym=True: also the data set's mirror pairing (``pairing()``) offset to the batch -- the list of support rows the edge branch has
+        to evaluate, its length on the device -- which GraphCSR.sym_index returns for the batch's supports (static shapes and HIP-graph
+        capture included).  A data set without a pairing gives the batch without it."""
         from . import _lib
         from .graph import GraphCSR, _ptr, _stream
         self.prepare()
         P = self._prep
+        if bounds is None or sym or int(ids.numel()) > 4096:
+            return self._assemble_any(ids, bounds, adjacency, groups64, sym)
         n_pad, e2_pad, dmax = bounds['n_pad'], bounds['e2_pad'], bounds.get('deal', bounds['dmax'])
         dev = ids.device
         B, F, S = int(ids.numel()), int(self.x.size(1)), int(self.edge_attr2.size(1))
@@ -286,6 +357,117 @@ class DeviceDataset(object):
         b._batch_i32 = batch
         return b
 
+    def _assemble_any(self, ids, bounds, adjacency, groups64, sym):
+        """batch_assembled for any B, padded (bounds) or exact (bounds=None), with or without the pairing (gml_batch_assemble_any)."""
+        from . import _lib
+        from .graph import GraphCSR, _ptr, _stream
+        import ctypes
+        P = self._prep
+        exact = bounds is None
+        dev = ids.device
+        B, F, S = int(ids.numel()), int(self.x.size(1)), int(self.edge_attr2.size(1))
+        if ids.dtype != torch.int64 or not ids.is_contiguous():
+            raise ValueError('ids: contiguous int64')
+        if B <= 0:
+            raise ValueError('batch_assembled: at least one slot')
+        if adjacency and (exact or B > 4096):
+            raise ValueError('batch_assembled: adjacency=True needs a padded batch of at most 4096 graphs (gml_batch_assemble_edges)')
+        pair = self.pairing() if sym else None
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        L = _lib.lib()
+        a = _lib.BatchAnyDesc()
+        d = a.b
+        ws = torch.empty(int(L.gml_batch_any_workspace_bytes(B)), dtype=torch.uint8, device=dev)
+        a.ws, a.ws_bytes, a.exact = _ptr(ws), ws.numel(), int(exact)
+        for name, t in (('node_ptr', self.node_ptr), ('edge_ptr2', self.edge_ptr2), ('x', P['x']), ('edge_index2', P['ei2']), ('edge_attr2', P['ea']),
+                        ('es', P['es']), ('tperm', P['tperm']), ('tinv', P['tinv']), ('rp_src', P['rp_src']), ('rp_dst', P['rp_dst']), ('y', P['y']),
+                        ('ids', ids)):
+            setattr(d, name, _ptr(t) if t is not None else None)
+        d.G, d.E2all, d.F, d.S, d.B = len(self), int(self.edge_index2.size(1)), F, S, B
+        if pair is not None:
+            a.sym_ptr, a.sym_uid, a.sym_mir = _ptr(pair['sym_ptr']), _ptr(pair['uid']), _ptr(pair['mir'])
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            if exact:
+                # the first host read: the batch's totals (nnew[B], enew[B] of the workspace, include/gml.h)
+                _lib.call('gml_batch_scan', ctypes.addressof(a), st)
+                w = ws.view(torch.int64)
+                n_pad, e2_pad = [int(v) for v in torch.stack([w[4 * B], w[5 * B + 1]]).tolist()]
+                if n_pad <= 0:
+                    raise ValueError('batch_assembled: the batch has no node')
+                a.scanned, dmax, bad = 1, 1, None
+            else:
+                n_pad, e2_pad, dmax = bounds['n_pad'], bounds['e2_pad'], bounds.get('deal', bounds['dmax'])
+                bad = torch.zeros(1, **i32)
+                a.bad = _ptr(bad)
+            d.n_pad, d.e2_pad, d.dmax = n_pad, e2_pad, dmax
+            nb = B if exact else B + 1
+            ldx = (F + 3) // 4 * 4
+            xbuf, ea = torch.empty(n_pad, ldx, **f32), torch.empty(e2_pad, S, **f32)
+            es = torch.empty(e2_pad, 8, **i32) if P['es'] is not None else None
+            y, valid = torch.empty(nb, **f32), (None if exact else torch.empty(B, **f32))
+            ptr, batch = torch.empty(nb + 1, **i32), torch.empty(n_pad, **i32)
+            g = GraphCSR()
+            g.N, g.E, g.device = n_pad, e2_pad, dev
+            g.rowptr, g.col, g.perm = torch.empty(n_pad + 1, **i32), torch.empty(e2_pad, **i32), torch.empty(e2_pad, **i32)
+            g.rowptr_t, g.col_t, g.pos_t = torch.empty(n_pad + 1, **i32), torch.empty(e2_pad, **i32), torch.empty(e2_pad, **i32)
+            ident = P.get('ident')
+            if ident is None or ident.numel() != e2_pad:
+                ident = torch.arange(e2_pad, **i32)
+                if not exact:
+                    P['ident'] = ident
+            g.perm_t, g.tpos = ident, g.perm
+            ng2 = max((n_pad + 127) // 128, 1)
+            both = torch.empty(2, ng2, int(L.gml_csr_group_record_ints(128)), **i32)
+            g.ginfo_t128, g.ginfo128 = both[0], both[1]
+            for name, t in (('x_out', xbuf), ('ea_out', ea), ('es_out', es), ('y_out', y), ('valid_out', valid), ('ptr_out', ptr), ('batch_out', batch),
+                            ('rowptr', g.rowptr), ('col', g.col), ('perm', g.perm), ('rowptr_t', g.rowptr_t), ('col_t', g.col_t), ('pos_t', g.pos_t),
+                            ('ginfo128', g.ginfo128), ('ginfo_t128', g.ginfo_t128)):
+                setattr(d, name, _ptr(t) if t is not None else None)
+            d.ldx_out = ldx
+            uid = mir = count = None
+            if pair is not None:
+                uid, mir, count = torch.empty(max(e2_pad, 1), **i32), torch.empty(max(e2_pad, 1), **i32), torch.empty(1, **i32)
+                a.uid_out, a.mir_out, a.count = _ptr(uid), _ptr(mir), _ptr(count)
+            _lib.call('gml_batch_assemble_any', ctypes.addressof(a), st)
+            if groups64:
+                ng = max((n_pad + 63) // 64, 1)
+                g64 = torch.empty(2, ng, int(L.gml_csr_group_record_ints(64)), **i32)
+                _lib.call('gml_csr_group_info2', _ptr(g.rowptr), _ptr(g.col), _ptr(g64[0]), _ptr(g.rowptr_t), _ptr(g.col_t), _ptr(g64[1]),
+                          n_pad, 64, st)
+                g._ginfo, g._ginfo_t = g64[0], g64[1]
+                if exact:
+                    m64 = torch.stack([g64[0][:, 1].max(), g64[0][:, 3].max(), g64[1][:, 1].max(), g64[1][:, 3].max()]).tolist()
+                    g._gmax, g._gmax_t = (int(m64[0]), int(m64[1])), (int(m64[2]), int(m64[3]))
+                else:
+                    g._gmax = g._gmax_t = (int(bounds['caps64'][0]), int(bounds['caps64'][1]))
+            ga = self._assemble_edges(ids, bounds, st) if adjacency else None
+        if exact:
+            # the second host read: the batch's group maxima (what GraphCSR.from_edge_index reads for a new batch)
+            mx = torch.stack([g.ginfo_t128[:, 1].max(), g.ginfo_t128[:, 3].max(), g.ginfo128[:, 1].max(), g.ginfo128[:, 3].max()]).tolist()
+            g.gmax_t128, g.gmax128 = (int(mx[0]), int(mx[1])), (int(mx[2]), int(mx[3]))
+        else:
+            g.gmax_t128 = g.gmax128 = (int(bounds['caps'][0]), int(bounds['caps'][1]))
+            g.static_shape = True
+            g._bad = bad
+        g.src_sorted = True
+        if es is not None:
+            g._val_cache[('p', ea.data_ptr(), ea._version, tuple(ea.shape))] = (ea, es)
+        if pair is not None:
+            g._sym_dev = (ea, uid, mir, count)
+        x = xbuf[:, :F]
+        if exact:
+            b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y)
+        else:
+            b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y, graph_valid=valid)
+            b.static_caps = bounds['caps']
+            b.pad_graph = True
+        b._csr['edge_index2'] = g
+        if ga is not None:
+            b._csr['edge_index'] = ga
+        b._batch_i32 = batch
+        return b
+
     def _assemble_edges(self, ids, bounds, st):
         """GraphCSR of the padded raw adjacency of the graphs ``ids`` (batch_assembled(adjacency=True))."""
         from . import _lib
@@ -329,6 +511,20 @@ class DeviceDataset(object):
         perm = torch.cat([perm, torch.full(((-G) % batch_size,), G, dtype=torch.int64, device=dev)])
         for i in range(0, perm.numel(), batch_size):
             yield self.batch_assembled(perm[i:i + batch_size].contiguous(), bd, adjacency=adjacency, groups64=groups64)
+
+    def epoch_assembled(self, batch_size, generator=None, shuffle=True, exact=True, sym=True, bounds=None):
+        """One shuffled epoch of ``batch_assembled`` batches of any size.  exact=True: fresh batches without padding (two host reads
+        each, none inside the step; the last batch holds the remaining graphs); exact=False: static padded shapes (bounds: as
+        ``epoch_static``, absent slots in the last batch).  sym: the data set's mirror pairing travels with every batch (the edge branch
+        then evaluates the unique support rows only)."""
+        G = len(self)
+        dev = self.node_ptr.device
+        bd = None if exact else (bounds if bounds is not None else self.bounds(batch_size))
+        perm = torch.randperm(G, generator=generator).to(dev) if shuffle else torch.arange(G, device=dev)
+        if not exact:
+            perm = torch.cat([perm, torch.full(((-G) % batch_size,), G, dtype=torch.int64, device=dev)])
+        for i in range(0, perm.numel(), batch_size):
+            yield self.batch_assembled(perm[i:i + batch_size].contiguous(), bd, sym=sym)
 
     def epoch(self, batch_size, generator=None, shuffle=True):
         """yields one shuffled epoch of batches (the DataLoader(shuffle=True) loop of Zinc12k.py:20,359)."""

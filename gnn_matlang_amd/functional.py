@@ -553,9 +553,13 @@ def edge_mlp_fwd_stack(ea, ea_split, weights, sym=None):
     if EDGE_FWD6 and not EDGE_VALU and (S in (4, 8) or (L == 1 and 2 <= S <= 16)) and sym is not None and EDGE_SYM:
         # the unique support rows only (gml_edge_chain_sym_impl.h): every output row is written, by its own entry or by its mirror's
         outs = [torch.empty(E, S, dtype=torch.float32, device=ea.device) for _ in range(L)]
-        rc = _lib.lib().gml_edge_mlp_fwd_stack6_sym(_ptr(ea), _ptr(sym[0]), _ptr(sym[1]), int(sym[0].numel()), L, arr([w[0] for w in weights]),
-                                                    arr([w[1] for w in weights]), arr([w[2] for w in weights]), arr([w[3] for w in weights]),
-                                                    arr(outs), int(E), int(S), int(S), _stream(ea.device))
+        ws4 = (arr([w[0] for w in weights]), arr([w[1] for w in weights]), arr([w[2] for w in weights]), arr([w[3] for w in weights]))
+        if len(sym) == 3:                                 # (uid, mir, count): the entry count lives on the device (an assembled batch)
+            rc = _lib.lib().gml_edge_mlp_fwd_stack6_sym_dev(_ptr(ea), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), int(sym[0].numel()), L, *ws4,
+                                                            arr(outs), int(E), int(S), int(S), _stream(ea.device))
+        else:
+            rc = _lib.lib().gml_edge_mlp_fwd_stack6_sym(_ptr(ea), _ptr(sym[0]), _ptr(sym[1]), int(sym[0].numel()), L, *ws4,
+                                                        arr(outs), int(E), int(S), int(S), _stream(ea.device))
         if rc != _lib.GML_E_UNSUPPORTED:
             _lib.check(rc)
             return outs
@@ -604,8 +608,13 @@ def edge_mlp_bwd(ea, w1, w2, w3, w4, gout, need_gin, ea_split=None, sym=None):
         U = int(sym[0].numel())
         nofold = fq is not None
         d = [_ptr(None)] * 4 if nofold else [_ptr(dw1), _ptr(dw2), _ptr(dw3), _ptr(dw4)]
-        rc = _lib.lib().gml_edge_mlp_bwd_sym(_ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), U, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout),
-                                             d[0], d[1], d[2], d[3], int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
+        if len(sym) == 3:                                 # (uid, mir, count): U is the capacity, the count lives on the device
+            rc = _lib.lib().gml_edge_mlp_bwd_sym_dev(_ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), U, _ptr(w1), _ptr(w2), _ptr(w3),
+                                                     _ptr(w4), _ptr(gout), d[0], d[1], d[2], d[3], int(E), int(S), int(So), _ptr(ws), ws.numel(),
+                                                     _stream(dev))
+        else:
+            rc = _lib.lib().gml_edge_mlp_bwd_sym(_ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), U, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout),
+                                                 d[0], d[1], d[2], d[3], int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
         if rc != _lib.GML_E_UNSUPPORTED:
             _lib.check(rc)
             if not nofold:

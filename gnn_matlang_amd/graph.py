@@ -37,7 +37,7 @@ def _require_cuda(t, name):
 class GraphCSR(object):
     __slots__ = ('N', 'E', 'device', 'rowptr', 'col', 'perm', 'rowptr_t', 'col_t', 'pos_t', 'perm_t', 'src_sorted',
                  '_ginfo', '_ginfo_t', '_gmax', '_gmax_t', 'ginfo_t128', 'gmax_t128', 'ginfo128', 'gmax128', 'tpos', '_val_cache', '_keep', '_r64',
-                 '_r64t', '_bad', 'static_shape')
+                 '_r64t', '_bad', 'static_shape', '_sym_dev')
 
     def __init__(self):
         self._val_cache = OrderedDict()
@@ -46,6 +46,7 @@ class GraphCSR(object):
         self._r64 = None
         self._ginfo = self._ginfo_t = self._gmax = self._gmax_t = None
         self._bad = None
+        self._sym_dev = None                                   # (supports, uid, mir, count): an assembled batch's pairing (dataset.py)
         self.static_shape = False                              # True: a static-shape batch whose tensors are refilled in place (dataset.py)
 
     @staticmethod
@@ -126,6 +127,9 @@ class GraphCSR(object):
             raise IndexError('edge_index holds node ids outside [0, %d)' % self.N)
         if v & 2:
             raise ValueError('edge_index is not sorted by source: a static-shape batch must be (SpectralDesign emits it so)')
+        if v & 4:
+            raise ValueError('the assembled batch exceeds the bounds it was padded to (repeated graph ids?): only its leading graphs '
+                             'that fit were assembled')
         return self
 
     @staticmethod
@@ -249,8 +253,14 @@ class GraphCSR(object):
         that carries bitwise the same row (-1: none) -- include/gml.h gml_edge_sym_flags.  Cached on the tensor's identity like the
         other derived arrays; None when nothing can be shared (S outside 2 .. 16, supports that carry a gradient, fewer than 10 % of the
         evaluations saved), for static-shape batches (their tensors are refilled in place by every replay of a captured step) or
-        while a HIP graph is being captured (the list's length is data)."""
+        while a HIP graph is being captured (the list's length is data).
+        A batch assembled with its data set's pairing (DeviceDataset.batch_assembled(sym=True)) carries the list for its supports in
+        source order: returned as (uid, mir, count) -- capacity E, count [1] on the device -- static shapes and capture included."""
         S = int(val.size(1))
+        sd = self._sym_dev
+        if (sd is not None and view == 'source' and 2 <= S <= 16 and not val.requires_grad and val.data_ptr() == sd[0].data_ptr()
+                and val.shape == sd[0].shape):
+            return sd[1:]
         if not (2 <= S <= 16) or val.requires_grad or self.E == 0 or self.E * S * 4 >= 0x7fffff00 or getattr(self, 'static_shape', False):
             return None
         key = ('y' + view[0], val.data_ptr(), val._version, tuple(val.shape))

@@ -195,6 +195,31 @@ typedef struct gml_batch_desc {
     int32_t* ginfo128; int32_t* ginfo_t128;
 } gml_batch_desc;
 int gml_batch_assemble(const gml_batch_desc* d, gml_stream_t stream);
+/* The same batch for ANY B (gml_batch_assemble keeps B <= 4096: its per-graph prefixes live in LDS).  gml_batch_scan (one workgroup)
+ * writes the per-graph node / edge / entry prefixes of the batch into ws, int64: nlo[B] elo[B] ulo[B] nnew[B + 1] enew[B + 1] unew[B + 1]
+ * Bv -- the totals are nnew[B], enew[B], unew[B]; gml_batch_assemble_any runs the scan (unless `scanned`: ws already holds it for
+ * these ids) and then the element launch, with the group records of both views when ginfo128 / ginfo_t128 are given.
+ *   padded mode (exact = 0): gml_batch_assemble's batch (dmax = padding edges per padding node), no host read, capturable.  A batch that
+ *     does not fit n_pad / e2_pad with room for its padding edges (repeated ids can exceed the data set's bounds) keeps its leading
+ *     Bv graphs that do (the others become absent slots) and ORs 4 into *bad;
+ *   exact mode (exact = 1): no padding graph, nodes or edges -- n_pad / e2_pad = the totals nnew[B] / enew[B] the caller read after
+ *     gml_batch_scan; ptr_out [B + 1], y_out [B], valid_out optional.  Equal to the block-diagonal batch + gml_csr_from_coo /
+ *     _from_sorted_coo / _link_transpose / gml_csr_group_info.
+ * Optional pairing (sym_ptr [G + 1], sym_uid / sym_mir: per graph its edge-branch entries, graph-LOCAL source-order edge positions,
+ * mirror -1 = none): uid_out / mir_out (capacity e2_pad) receive every graph's entries offset by its first edge in the batch, then one
+ * entry per padding edge (mirror -1), and *count their number -- gml_edge_sym_flags + compaction on the assembled batch when the
+ * per-graph lists are that pass's result on each graph. */
+typedef struct gml_batch_any_desc {
+    gml_batch_desc b;
+    int32_t exact, scanned;
+    const int64_t* sym_ptr; const int32_t* sym_uid; const int32_t* sym_mir;
+    int32_t* uid_out; int32_t* mir_out; int32_t* count;
+    int32_t* bad;
+    void* ws; size_t ws_bytes;
+} gml_batch_any_desc;
+size_t gml_batch_any_workspace_bytes(int32_t B);
+int gml_batch_scan(const gml_batch_any_desc* a, gml_stream_t stream);
+int gml_batch_assemble_any(const gml_batch_any_desc* a, gml_stream_t stream);
 /* The RAW adjacency (edge_index) of the same padded batch, both CSR views, in one launch (a descriptor of its own: gml_batch_desc
  * keeps its layout).  Data set side, per graph g its raw edges edge_ptr[g]..edge_ptr[g+1] of edge_index [2, Eall] (graph-LOCAL node
  * ids, any order) and, indexed like those edges (position edge_ptr[g] + k): tperm[.] = input position (inside the graph) of the
@@ -404,10 +429,21 @@ int gml_edge_sym_flags(const int32_t* rowptr_t, const int32_t* col_t, const floa
 int gml_edge_mlp_fwd_stack6_sym(const float* ea, const int32_t* uid, const int32_t* mir, int64_t num_unique, int32_t nlayers,
                                 const float* const* w1, const float* const* w2, const float* const* w3, const float* const* w4,
                                 float* const* out, int64_t num_edges, int32_t S, int32_t Sout, gml_stream_t stream);
+/* _dev: the same with the entry count on the device -- uid / mir hold `capacity` slots, *count (int32, device) of them are entries (read
+ * by the kernels, clamped to [0, capacity]; a list assembled on the device, gml_batch_assemble_any, whose length the host never reads).
+ * The grids are sized from capacity; the backward writes all gml_edge_mlp_bwd_sym_parts(capacity, S) partial rows (zeros where a
+ * workgroup has no entry). */
+int gml_edge_mlp_fwd_stack6_sym_dev(const float* ea, const int32_t* uid, const int32_t* mir, const int32_t* count, int64_t capacity,
+                                    int32_t nlayers, const float* const* w1, const float* const* w2, const float* const* w3,
+                                    const float* const* w4, float* const* out, int64_t num_edges, int32_t S, int32_t Sout, gml_stream_t stream);
 int64_t gml_edge_mlp_bwd_sym_parts(int64_t num_unique, int32_t S);
 int gml_edge_mlp_bwd_sym(const void* ea_split, const int32_t* uid, const int32_t* mir, int64_t num_unique, const float* w1,
                          const float* w2, const float* w3, const float* w4, const float* gout, float* dw1, float* dw2, float* dw3,
                          float* dw4, int64_t num_edges, int32_t S, int32_t Sout, void* ws, size_t ws_bytes, gml_stream_t stream);
+int gml_edge_mlp_bwd_sym_dev(const void* ea_split, const int32_t* uid, const int32_t* mir, const int32_t* count, int64_t capacity,
+                             const float* w1, const float* w2, const float* w3, const float* w4, const float* gout, float* dw1, float* dw2,
+                             float* dw3, float* dw4, int64_t num_edges, int32_t S, int32_t Sout, void* ws, size_t ws_bytes,
+                             gml_stream_t stream);
 size_t gml_edge_mlp_bwd_workspace_bytes(int64_t num_edges, int32_t S, int32_t Sout);
 /* gout: dL/dout [E, Sout].  Writes dw1..dw4 (same shapes as the weights) and, if gin != NULL,
  * dL/dea [E, S].  Intermediates are recomputed from ea. */
