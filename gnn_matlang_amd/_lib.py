@@ -118,6 +118,8 @@ SIGNATURES = {
     'gml_segment_bcast_mask': (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _i32, _p]),
     'gml_segment_max': (ctypes.c_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i32, _p]),
     'gml_segment_max_bwd': (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p]),
+    'gml_dropout_fwd': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, ctypes.c_uint64, ctypes.c_float, _p, _u32, _p]),
+    'gml_dropout_bwd': (ctypes.c_int, [_p, _i64, _p, _p, _i64, _i64, _i32, ctypes.c_float, _p]),
     'gml_dense_pack': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p]),
     'gml_dense_wimg_elems': (_sz, [_i32, _i32, _i32]),
     'gml_dense_pack_w': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p]),

@@ -1135,6 +1135,97 @@ def segment_max_bwd(g, ptr, arg, nrows):
     return out
 
 
+# ---------------------------------------------------------------------------- dropout (csrc/gml_dropout.hip)
+# The mask is a pure function of (seed, counter, site, element index): Philox4x32-10 keyed by the seed (include/gml.h).  The RNG
+# state is an int64 [2] = {seed, counter} CUDA tensor the kernel reads on the device; advancing the counter is a plain
+# `state[1:].add_(1)`, so a captured step draws fresh masks on every replay, the same ones the step would draw eagerly.
+
+def dropout_threshold(p):
+    """(t, scale) of the keep rule u >= t for a drop probability p: t = floor(p 2^32) in float64 (2^32 for p = 1: nothing is
+    kept), scale = 1 / (1 - p) (0 for p = 1), rounded to float32 once where the kernel takes it.  ValueError outside [0, 1]."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('dropout probability has to be between 0 and 1, but got %s' % p)
+    if p == 1.0:
+        return 1 << 32, 0.0
+    import math
+    return int(math.floor(p * 4294967296.0)), 1.0 / (1.0 - p)
+
+
+def dropout_state(seed, device):
+    """int64 [2] = {seed, counter 0} on `device`: the RNG state dropout() reads.  seed: any integer, taken modulo 2^64."""
+    seed = int(seed) & 0xffffffffffffffff
+    if seed >= 1 << 63:
+        seed -= 1 << 64
+    return torch.tensor([seed, 0], dtype=torch.int64, device=device)
+
+
+def _dropout_rows(x, name):
+    _require_cuda(x, name)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise TypeError('%s must be a float32 [N, C] tensor, got %s %s' % (name, x.dtype, tuple(x.shape)))
+    return x if (x.stride(1) == 1 and x.stride(0) >= x.size(1)) else x.contiguous()
+
+
+def dropout_fwd(x, p, state, site=0):
+    """(y, mask) of one dropout launch: y [N, C] float32 (rows padded to a multiple of 4 floats: what the layers read without a
+    copy), mask uint32 packed keep bits as int32 [ceil(N C / 32)] (bit e & 31 of word e >> 5)."""
+    x = _dropout_rows(x, 'x')
+    t, scale = dropout_threshold(p)
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int64 and state.numel() == 2
+            and state.is_contiguous() and state.device == x.device):
+        raise TypeError('state must be a contiguous int64 [2] CUDA tensor on the device of x (functional.dropout_state)')
+    N, C = int(x.size(0)), int(x.size(1))
+    dev = x.device
+    with torch.cuda.device(dev):
+        buf = torch.empty(N, (C + 3) // 4 * 4, dtype=torch.float32, device=dev)
+        mask = torch.empty((N * C + 31) // 32, dtype=torch.int32, device=dev)
+        with _Timed('dropout_fwd', 8 * N * C + (N * C) // 8 if PROFILE is not None else 0):
+            _lib.call('gml_dropout_fwd', _ptr(x), int(x.stride(0)), _ptr(buf), int(buf.stride(0)), _ptr(mask), N, C,
+                      ctypes.c_uint64(t), ctypes.c_float(scale), _ptr(state), ctypes.c_uint32(int(site) & 0xffffffff), _stream(dev))
+    return buf[:, :C], mask
+
+
+def dropout_bwd(g, mask, p):
+    """dx = keep ? g * scale : +0.0 from a mask of dropout_fwd (same p)."""
+    g = _dropout_rows(g, 'grad_output')
+    _, scale = dropout_threshold(p)
+    N, C = int(g.size(0)), int(g.size(1))
+    dev = g.device
+    with torch.cuda.device(dev):
+        buf = torch.empty(N, (C + 3) // 4 * 4, dtype=torch.float32, device=dev)
+        with _Timed('dropout_bwd', 8 * N * C + (N * C) // 8 if PROFILE is not None else 0):
+            _lib.call('gml_dropout_bwd', _ptr(g), int(g.stride(0)), _ptr(mask), _ptr(buf), int(buf.stride(0)), N, C,
+                      ctypes.c_float(scale), _stream(dev))
+    return buf[:, :C]
+
+
+class DropoutFunction(torch.autograd.Function):
+    """F.dropout(x, p, training=True) on csrc/gml_dropout.hip: the backward applies the mask the forward saved, so a later
+    change of the RNG state does not affect it."""
+
+    @staticmethod
+    def forward(ctx, x, p, state, site=0):
+        y, mask = dropout_fwd(x, p, state, site)
+        ctx.save_for_backward(mask)
+        ctx.p = p
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        mask, = ctx.saved_tensors
+        return dropout_bwd(g, mask, ctx.p), None, None, None
+
+
+def dropout(x, p, training, state, site=0):
+    """F.dropout(x, p, training) with the device RNG state `state` (dropout_state) and `site` (which dropout of the model: part
+    of the Philox counter).  Not training, or p == 0: x itself, nothing launched.  Otherwise a new tensor (never in place)."""
+    dropout_threshold(p)                                   # ValueError outside [0, 1], in eval mode too (as torch)
+    if not training or p == 0:
+        return x
+    return DropoutFunction.apply(x, float(p), state, int(site))
+
+
 def _bwd_plan(csr, S, Fin, Fout):
     """(flags, ginfo, (max_edges, max_window), workspace bytes) of the fused backward for this shape, or None."""
     L = _lib.lib()

@@ -9,6 +9,7 @@ edge_index2, edge_attr2, batch, ptr, y).
 import torch
 import torch.nn.functional as F
 
+from . import functional as Fn
 from .functional import segment_bcast, segment_max, segment_max_bwd, segment_sum, skip_last_mask, tall_linear, _ptr32
 from .spect_conv import ML3Layer, SpectConv
 from .dist import SyncBatchNorm1d
@@ -130,12 +131,52 @@ def global_mean_pool(x, data):
     return _SegmentPool.apply(x, data.ptr, data.batch, 1 | _pad_flag(data))
 
 
+_POOLS = dict(add=global_add_pool, mean=global_mean_pool, max=global_max_pool)
+
+
+def _pool(pool, x, data):
+    """pool: a name of _POOLS, or a tuple of names -- torch.cat of those pools in that column order (ptc.py:361: mean | max,
+    enzymes.py:384: add | max).  On a padded static batch the padding graph's max row is whatever its nodes hold: the loss masks it."""
+    if isinstance(pool, tuple):
+        return torch.cat([_POOLS[p](x, data) for p in pool], 1)
+    return _POOLS[pool](x, data)
+
+
+def _init_dropout(model, p):
+    """model.dropout = p; p > 0: the RNG state as a NON-persistent buffer `dropout_state` (int64 {seed, counter}: the reference's
+    state_dict loads with strict=True, .to() moves it), its seed drawn from torch's default generator (torch.manual_seed decides it).
+    Reset it with model.dropout_state.copy_(...) or functional.dropout_state(seed, device)."""
+    Fn.dropout_threshold(p)                                      # ValueError outside [0, 1]
+    model.dropout = float(p)
+    if model.dropout > 0:
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64))
+        model.register_buffer('dropout_state', torch.tensor([seed, 0], dtype=torch.int64), persistent=False)
+
+
+def _dropout_pass(model):
+    """True for a training forward of a model with dropout: the counter advances once (a device-side add: captured with the step,
+    so every forward, eager or replayed, draws fresh masks)."""
+    if not (model.training and model.dropout > 0):
+        return False
+    model.dropout_state[1:].add_(1)
+    return True
+
+
 class GNNML3(torch.nn.Module):
-    """head 'mlp32': fc2(relu(fc1 x)), fc1: nin->32, fc2: 32->nclass;  'tanh10': tanh(fc1 x), fc1: nin->10."""
+    """head 'mlp32': fc2(relu(fc1 x)), fc1: nin->32, fc2: 32->nclass;  'tanh10': tanh(fc1 x), fc1: nin->10;
+    'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin->hidden (hidden > 0), else log_softmax(fc2 x), fc2: .->nclass."""
 
     def __init__(self, ninp, ne, nout1, nout2, nlayers, learnedge=True, bn=False, pool='add', head='mlp32',
-                 nclass=1, readout_bn=False, dense_n=0, chain=True):
+                 nclass=1, readout_bn=False, dense_n=0, chain=True, dropout=0.0, hidden=0, pool_bn=None):
         super().__init__()
+        # head 'log_softmax' (the TU scripts: ptc.py:323-363, enzymes.py:345-386, proteins.py:259-289): [relu(fc1 x) when hidden > 0]
+        # -> fc2 -> log_softmax, after an optional BatchNorm of the pooled vector named pool_bn ('bn4': enzymes.py:362).
+        # pool: 'add' | 'mean' | 'max', or a tuple such as ('mean', 'max'): cat of those pools, in that column order.
+        # dropout > 0: F.dropout(x, p) in front of every layer in training (site = the layer index), masks from the device RNG state
+        # `dropout_state` (functional.dropout)
+        Fn.dropout_threshold(dropout)
+        if pool_bn is not None and (bn or readout_bn or head != 'log_softmax'):
+            raise ValueError("pool_bn goes with head='log_softmax' and neither bn nor readout_bn")
         # chain=False: do not declare the relu hand-over between stacked layers (ML3Layer.chain_after).  The hand-over is
         # valid only while convN+1 is the SOLE consumer of convN's output tensor: a forward hook, an auxiliary loss or a
         # feature tap on an intermediate output adds a second gradient the lower layer would then leave unmasked -- pass
@@ -155,28 +196,44 @@ class GNNML3(torch.nn.Module):
             fin = widths[i] + nout2
             if bn:
                 setattr(self, 'bn%d' % (i + 1), BatchNorm1d(fin))
-        if chain and not bn and not self.dense_n:
+        self._chain = chain and not bn and not self.dense_n
+        if self._chain:
             # x = conv2(conv1(x, ...), ...) with nothing else reading the intermediate outputs (Zinc12k.py:338-341,
-            # counting.py:361-366, sr25.py:266-270): the relu hand-over between stacked layers applies
-            for i in range(1, nlayers):
-                getattr(self, 'conv%d' % (i + 1)).chain_after(getattr(self, 'conv%d' % i))
-        nin = fin
+            # counting.py:361-366, sr25.py:266-270): the relu hand-over between stacked layers applies.  With dropout in training a
+            # dropout sits between the layers instead: forward() withdraws the declaration for such passes (_declare_chain)
+            self._declare_chain(True)
+        nin = fin * (len(pool) if isinstance(pool, tuple) else 1)
         if readout_bn:                       # TF ReadoutLayer: batch_normalization of the pooled vector
             # tf.layers.batch_normalization defaults (libs/layers_tf.py:349): epsilon 1e-3, momentum 0.99 (= 0.01 in torch's convention)
             self.bnr = SyncBatchNorm1d(nin, eps=1e-3, momentum=0.01)   # global-batch statistics under data parallelism (dist.py)
+        self.pool_bn = pool_bn
+        if pool_bn is not None:
+            setattr(self, pool_bn, torch.nn.BatchNorm1d(nin))   # torch defaults (enzymes.py:362)
         if head == 'mlp32':
             self.fc1 = torch.nn.Linear(nin, 32)
             self.fc2 = torch.nn.Linear(32, nclass)
+        elif head == 'log_softmax':
+            if hidden:
+                self.fc1 = torch.nn.Linear(nin, hidden)
+            self.fc2 = torch.nn.Linear(hidden or nin, nclass)
         else:
             self.fc1 = torch.nn.Linear(nin, 10)
+        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
+
+    def _declare_chain(self, on):
+        for i in range(1, self.nlayers):
+            getattr(self, 'conv%d' % (i + 1)).chain_after(getattr(self, 'conv%d' % i) if on else None)
 
     def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False):
         x = data.x
         padded = getattr(data, 'pad_graph', False)
-        if padded and self.training and self.readout_bn:
+        if padded and self.training and (self.readout_bn or self.pool_bn is not None):
             # the padding graph's pooled row would enter the batch statistics of the readout BatchNorm
             raise NotImplementedError('readout BatchNorm takes plain batches: a padded static batch (pad_graph) would count its padding '
                                       'row in the statistics')
+        drop = _dropout_pass(self)
+        if self._chain and self.dropout > 0:
+            self._declare_chain(not drop)
         nvalid = _node_valid(data) if padded and self.training and self.bn else None     # the bnN layers: real nodes only
         if self.dense_n:
             from .dense_block import dense_supports, spectconv_dense, _library
@@ -188,6 +245,8 @@ class GNNML3(torch.nn.Module):
         pooled = False
         for i in range(self.nlayers):
             layer = getattr(self, 'conv%d' % (i + 1))
+            if drop:
+                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i)
             if self.dense_n:
                 x = spectconv_dense(x, data._spT, layer.conv1.weight, layer.conv1.bias, self.dense_n, relu=True)
             elif i == self.nlayers - 1 and not self.bn and self.pool in ('add', 'mean') and torch.is_grad_enabled():
@@ -210,11 +269,17 @@ class GNNML3(torch.nn.Module):
                 bn = getattr(self, 'bn%d' % (i + 1))
                 x = bn(x) if nvalid is None else bn(x, valid=nvalid)
         if not pooled:
-            x = {'add': global_add_pool, 'mean': global_mean_pool, 'max': global_max_pool}[self.pool](x, data)
+            x = _pool(self.pool, x, data)
         if self.readout_bn:
             x = self.bnr(x)
+        if self.pool_bn is not None:
+            x = getattr(self, self.pool_bn)(x)
         if _features:
             return x
+        if self.head == 'log_softmax':
+            if hasattr(self, 'fc1'):
+                x = F.relu(tall_linear(x, self.fc1))
+            return F.log_softmax(tall_linear(x, self.fc2), dim=1)
         if self.head == 'mlp32':
             z1 = tall_linear(x, self.fc1)
             if _capture is not None:
@@ -282,7 +347,7 @@ class GNNML1(torch.nn.Module):
     Same attribute names as the reference, so its state_dict loads.  (mutag.py's variant -- relu on the factors, BatchNorm
     per block -- is GNNML1Mutag.)"""
 
-    def __init__(self, ninp, nout=64, concat=False, act='tanh', pool='add', head='lin10', nclass=10):
+    def __init__(self, ninp, nout=64, concat=False, act='tanh', pool='add', head='lin10', nclass=10, dropout=0.0):
         super().__init__()
         self.concat, self.pool, self.head = concat, pool, head
         self.act = {'tanh': torch.tanh, 'relu': F.relu}[act]
@@ -297,6 +362,7 @@ class GNNML1(torch.nn.Module):
             self.bn1 = torch.nn.BatchNorm1d(nin)
             self.fc1 = torch.nn.Linear(nin, 32)
             self.fc2 = torch.nn.Linear(32, nclass)
+        _init_dropout(self, dropout)           # dropout > 0: F.dropout in front of every block in training (mnist75.py:299-317)
 
     def forward(self, data):
         x = data.x
@@ -307,15 +373,18 @@ class GNNML1(torch.nn.Module):
         csr = _adjacency(data)
         ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)      # sr25.py:231
         actid = 0 if self.act is torch.tanh else 1
+        drop = _dropout_pass(self)
         for i in (1, 2, 3):
             g = lambda n: getattr(self, n % i)
+            if drop:
+                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
             y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), 1 if self.concat else 0, actid)
             if y is not None:
                 x = y
                 continue
             a, c, h = g('fc%d1')(x), g('conv%d1')(x, csr, ones), g('fc%d2')(x) * g('fc%d3')(x)
             x = torch.cat([self.act(a), self.act(c), self.act(h)], 1) if self.concat else self.act(a + c + h)
-        x = {'add': global_add_pool, 'mean': global_mean_pool, 'max': global_max_pool}[self.pool](x, data)
+        x = _pool(self.pool, x, data)
         if self.head == 'lin10':
             return tall_linear(x, self.fc1)
         x = F.relu(tall_linear(self.bn1(x), self.fc1))
@@ -326,8 +395,8 @@ def sr25_gnnml1(ninp=2):                   # sr25.py:192-246 (nout = 64, sum for
     return GNNML1(ninp, 64, concat=False, act='tanh', pool='add', head='lin10')
 
 
-def mnist75_gnnml1(ninp=3):                # mnist75.py:262-326 (relu, mean-pool, bn1, 32 -> 10; dropout p = 0.1 omitted: eval)
-    return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='bn_mlp')
+def mnist75_gnnml1(ninp=3, dropout=0.0):   # mnist75.py:262-326 (relu, mean-pool, bn1, 32 -> 10; the script's dropout: p = 0.1)
+    return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='bn_mlp', dropout=dropout)
 
 
 def zinc_gnnml3(ninp=25, ne=8):            # Zinc12k.py:316-329
@@ -349,6 +418,20 @@ def mnist_gnnml3(ninp=2, ne=6, dense_n=0):  # mnist75_gnnml3_tf.py:62, libs/mode
 
 def mutag_gnnml3(ninp=8, ne=4):            # mutag.py:272-288
     return GNNML3(ninp, ne, 24, 24, 3, learnedge=False, bn=True, pool='mean')
+
+
+def ptc_gnnml3(ninp=20, ne=11, dropout=0.2):    # ptc.py:323-363
+    return GNNML3(ninp, ne, 64, 16, 4, learnedge=True, pool=('mean', 'max'), head='log_softmax', hidden=100, nclass=2,
+                  dropout=dropout)
+
+
+def enzymes_gnnml3(ninp=4, ne=5, dropout=0.1):  # enzymes.py:345-386
+    return GNNML3(ninp, ne, 64, 0, 4, learnedge=False, pool=('add', 'max'), head='log_softmax', nclass=6, pool_bn='bn4',
+                  dropout=dropout)
+
+
+def proteins_gnnml3(ninp=4, ne=4, dropout=0.1):  # proteins.py:259-289
+    return GNNML3(ninp, ne, 64, 0, 2, learnedge=False, pool=('mean', 'max'), head='log_softmax', nclass=2, dropout=dropout)
 
 
 def zinc_loss(pre, y):                     # Zinc12k.py:365
@@ -410,3 +493,19 @@ def mutag_step_loss(model, data, valid=None):
     ``loss_fn(model, data)`` of dist.TrainStep."""
     valid = valid if valid is not None else getattr(data, 'graph_valid', None)
     return mutag_loss(model(data), data.y, valid)
+
+
+def tu_loss(pre, y, valid=None):             # ptc.py:416, enzymes.py / proteins.py: F.nll_loss(pred, data.y, reduction='sum')
+    """valid: a padded static batch's graph_valid [B] -- the NLL sum over the real graphs of its first B rows (the padding graph's
+    row and absent slots count zero)."""
+    if valid is None:
+        return F.nll_loss(pre, y.long(), reduction='sum')
+    nl = int(valid.numel())
+    l = F.nll_loss(pre[:nl], y[:nl].long().clamp(0, int(pre.size(1)) - 1), reduction='none')
+    return (l * valid).sum()
+
+
+def tu_step_loss(model, data, valid=None):
+    """tu_loss(model(data), data.y) for plain and padded batches alike -- the ``loss_fn(model, data)`` of dist.TrainStep."""
+    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
+    return tu_loss(model(data), data.y, valid)

@@ -8,6 +8,7 @@ libs/utils.py:509) inside PyG ``InMemoryDataset.process`` bodies; neither PyG no
   read_graph6   graph6 text (one graph per line, optional >>graph6<< header)
   load_mutag    libs/utils.py:192-209  (A, F, y of dataset/mutag/raw/mutag.mat -> x, edge_index, y per graph)
   load_sr       libs/utils.py:506-513  (sr251256.g6 -> x = ones, undirected edge_index, y = 0)
+  load_tu       libs/utils.py:24-174   (ptc.mat / enzymes.mat / proteins.mat -> x, edge_index, integer class label)
 
 Each returns graphs as (x [n, f] float32, edge_index [2, e] int64 in row-major ``np.where`` order, y), the input format
 of ``SpectralDesign.design_many`` / ``graph.collate``.
@@ -153,3 +154,23 @@ def load_mutag(path):
 def load_sr(path):
     """libs/utils.py:506-513: x = ones [n, 1], symmetric edges, y = 0 (sr25.py, graph8c.py)"""
     return [(np.ones((A.shape[0], 1), dtype=np.float32), _edges(A), np.float32(0)) for A in read_graph6(path)]
+
+
+# feature columns the reference's TU dataset classes keep (contfeat=False): PtcDataset all of them, EnzymesDataset and
+# ProteinsDataset F[i][:, 0:3] (libs/utils.py:51, 101, 151)
+_TU_COLS = dict(ptc=None, enzymes=3, proteins=3)
+
+
+def load_tu(path, name):
+    """libs/utils.py:24-174: graphs of ptc.mat / enzymes.mat / proteins.mat (name 'ptc' | 'enzymes' | 'proteins') as
+    (x, edge_index, y): edges where A > 0, x = the kept feature columns as float32, y = the int64 class label from Y ([G, 1] in
+    ptc.mat and proteins.mat, [1, G] in enzymes.mat)."""
+    if name not in _TU_COLS:
+        raise ValueError("load_tu: name must be 'ptc', 'enzymes' or 'proteins', got %r" % (name,))
+    a = read_mat(path)
+    A, F = a['A'].reshape(-1), a['F'].reshape(-1)
+    Y = np.asarray(a['Y']).astype(np.int64).reshape(-1)
+    if Y.size != A.size:
+        raise ValueError('%s: %d labels for %d graphs' % (path, Y.size, A.size))
+    k = _TU_COLS[name]
+    return [(np.asarray(F[i] if k is None else F[i][:, 0:k], dtype=np.float32), _edges(A[i]), np.int64(Y[i])) for i in range(A.size)]

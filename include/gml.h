@@ -549,6 +549,26 @@ int gml_segment_max(const float* x, int64_t ldx, const int32_t* ptr, float* out,
 int gml_segment_max_bwd(const float* g, int64_t ldg, const int32_t* ptr, const int32_t* argmax, float* out, int64_t ldo,
                         int64_t num_segments, int32_t F, gml_stream_t stream);
 
+/* ---------------------------------------------------------------- dropout (csrc/gml_dropout.hip)
+ * F.dropout(x, p, training=True) in front of every layer of the TU scripts (ptc.py:349-358, enzymes.py:372-381, proteins.py:282-285)
+ * and mnist75.py:299-317, with a mask that is a pure function of (seed, counter, site, e) for the logical element e = r C + c of an
+ * [N, C] input -- independent of launch geometry, strides and device:
+ *   Philox4x32-10 (Salmon et al., SC'11), key = (seed lo, seed hi), counter block = (j lo, j hi, site, counter lo) with j = e >> 2;
+ *   u = word (e & 3) of the output;  keep e  <=>  u >= t,  t = floor(p 2^32) (host, float64; 2^32 for p = 1: nothing kept).
+ * state: DEVICE pointer to int64 {seed, counter}, read by the kernel -- no host value per call, so the launch is capturable and a
+ * replay uses whatever counter the device holds then.  site: which dropout of the model (the layer index).
+ *   y[r, c] = keep ? x[r, c] * scale : +0.0     scale = float(1 / (1 - p)) rounded once; ONE fp32 multiply.
+ * A dropped element is written as +0.0 -- not x * 0 --, so a NaN / Inf input or a negative input gives +0.0 there, never NaN or -0.0.
+ * mask: packed keep bits, bit (e & 31) of word e >> 5, ceil(N C / 32) words (the unused high bits of the last word are 0).
+ * One lane per 4 consecutive elements (one Philox call); float4 loads / stores when C % 4 == 0 and ldx, ldy % 4 == 0 with 16-byte
+ * aligned bases, a scalar path otherwise.  N = 0 or C = 0: nothing to do, GML_OK.  t > 2^32, ld < C, NULL or misaligned pointers
+ * (float / uint32 4 bytes, state 8 bytes): GML_E_BADARG.
+ * gml_dropout_bwd: dx[r, c] = keep ? g[r, c] * scale : +0.0 from the saved mask; same geometry, does not touch the RNG state. */
+int gml_dropout_fwd(const float* x, int64_t ldx, float* y, int64_t ldy, uint32_t* mask, int64_t num_rows, int32_t C,
+                    uint64_t t, float scale, const int64_t* state, uint32_t site, gml_stream_t stream);
+int gml_dropout_bwd(const float* g, int64_t ldg, const uint32_t* mask, float* dx, int64_t lddx, int64_t num_rows, int32_t C,
+                    float scale, gml_stream_t stream);
+
 /* ---------------------------------------------------------------- dense-block SpectConv (equal-size graphs, near-dense masks)
  * The TF formulation of the layer, /root/reference/libs/layers_tf.py:231-236 (s0 = matmul(support[:, i], x); out += s0 . W_i),
  * for batches of B graphs of exactly n <= 96 nodes (MNIST-75: n = 75, S = 6).
