@@ -120,6 +120,12 @@ SIGNATURES = {
     'gml_segment_max_bwd': (ctypes.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p]),
     'gml_dropout_fwd': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _i32, ctypes.c_uint64, ctypes.c_float, _p, _u32, _p]),
     'gml_dropout_bwd': (ctypes.c_int, [_p, _i64, _p, _p, _i64, _i64, _i32, ctypes.c_float, _p]),
+    'gml_pair_bitmap_words': (_i64, [_i64, _i64]),
+    'gml_pair_distinct_all': (ctypes.c_int, [_p, _i64, _i64, _i32, ctypes.c_float, _p, _p]),
+    'gml_pair_distinct_list': (ctypes.c_int, [_p, _i64, _i64, _p, _i64, _i32, ctypes.c_float, _p, _p]),
+    'gml_pair_count_similar': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _p]),
+    'gml_pair_list_workspace_bytes': (_sz, [_i64, _i64]),
+    'gml_pair_list_similar': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
     'gml_dense_pack': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p]),
     'gml_dense_wimg_elems': (_sz, [_i32, _i32, _i32]),
     'gml_dense_pack_w': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p]),

@@ -395,6 +395,10 @@ def sr25_gnnml1(ninp=2):                   # sr25.py:192-246 (nout = 64, sum for
     return GNNML1(ninp, 64, concat=False, act='tanh', pool='add', head='lin10')
 
 
+def graph8c_gnnml1(ninp=2):                # graph8c.py:195-246 (nout = 64, sum form, tanh, add-pool, fc1 -> 10)
+    return GNNML1(ninp, 64, concat=False, act='tanh', pool='add', head='lin10')
+
+
 def mnist75_gnnml1(ninp=3, dropout=0.0):   # mnist75.py:262-326 (relu, mean-pool, bn1, 32 -> 10; the script's dropout: p = 0.1)
     return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='bn_mlp', dropout=dropout)
 
@@ -408,6 +412,14 @@ def counting_gnnml3(ninp=2, ne=12):        # counting.py:343-358
 
 
 def sr25_gnnml3(ninp=2, ne=6):             # sr25.py:252-262
+    return GNNML3(ninp, ne, 32, 16, 3, head='tanh10')
+
+
+def graph8c_gnnml3(ninp=2, ne=6):          # graph8c.py:252-278 (the sr25 shapes: 32 + 16 outputs, 3 layers, add-pool, tanh(fc1) -> 10)
+    return GNNML3(ninp, ne, 32, 16, 3, head='tanh10')
+
+
+def exp_gnnml3(ninp=2, ne=6):              # exp_iso.py:249-278 (the same shapes; ne = 6 supports of SpectralDesign(nfreq=5))
     return GNNML3(ninp, ne, 32, 16, 3, head='tanh10')
 
 

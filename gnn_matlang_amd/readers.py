@@ -9,6 +9,8 @@ libs/utils.py:509) inside PyG ``InMemoryDataset.process`` bodies; neither PyG no
   load_mutag    libs/utils.py:192-209  (A, F, y of dataset/mutag/raw/mutag.mat -> x, edge_index, y per graph)
   load_sr       libs/utils.py:506-513  (sr251256.g6 -> x = ones, undirected edge_index, y = 0)
   load_tu       libs/utils.py:24-174   (ptc.mat / enzymes.mat / proteins.mat -> x, edge_index, integer class label)
+  load_graph8c  libs/utils.py:453-487  (graph8c.g6 -> x = ones, undirected edge_index, y = 0)
+  load_exp      libs/utils.py:424-451  (EXP's GRAPHSAT.pkl as converted by tools/convert_exp.py -> x, edge_index, y)
 
 Each returns graphs as (x [n, f] float32, edge_index [2, e] int64 in row-major ``np.where`` order, y), the input format
 of ``SpectralDesign.design_many`` / ``graph.collate``.
@@ -154,6 +156,21 @@ def load_mutag(path):
 def load_sr(path):
     """libs/utils.py:506-513: x = ones [n, 1], symmetric edges, y = 0 (sr25.py, graph8c.py)"""
     return [(np.ones((A.shape[0], 1), dtype=np.float32), _edges(A), np.float32(0)) for A in read_graph6(path)]
+
+
+def load_graph8c(path):
+    """libs/utils.py:453-487 (Grapg8cDataset): the 11,117 connected graphs of 8 nodes of graph8c.g6, read as load_sr reads
+    sr25 -- x = ones [8, 1], both directions of every edge, y = 0 (graph8c.py:16-18)"""
+    return load_sr(path)
+
+
+def load_exp(path):
+    """libs/utils.py:424-451 (PlanarSATPairsDataset): the 1,200 graphs of EXP in file order -- graphs 2k and 2k + 1 form a pair
+    (exp_iso.py:301) -- from the npz tools/convert_exp.py writes: (x float32 [n, 1], edge_index int64 [2, e] as stored, y int64)"""
+    z = np.load(path, allow_pickle=False)
+    x, ei, y, npt, ept = z['x'], z['edge_index'], z['y'], z['node_ptr'], z['edge_ptr']
+    return [(np.asarray(x[npt[g]:npt[g + 1]], dtype=np.float32), np.asarray(ei[:, ept[g]:ept[g + 1]], dtype=np.int64), np.int64(y[g]))
+            for g in range(y.size)]
 
 
 # feature columns the reference's TU dataset classes keep (contfeat=False): PtcDataset all of them, EnzymesDataset and

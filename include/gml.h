@@ -569,6 +569,33 @@ int gml_dropout_fwd(const float* x, int64_t ldx, float* y, int64_t ldy, uint32_t
 int gml_dropout_bwd(const float* g, int64_t ldg, const uint32_t* mask, float* dx, int64_t lddx, int64_t num_rows, int32_t C,
                     float scale, gml_stream_t stream);
 
+/* ---------------------------------------------------------------- pair distinguishability (csrc/gml_pairs.hip)
+ * The isomorphism tests of sr25.py:281-300, graph8c.py:282-302 and exp_iso.py:284-304: which pairs of graph embeddings E [G, D] (rows
+ * of ldE >= D floats, 1 <= D <= 128, G <= 65536) an untrained model never separates over many seeds.  A pair (i, j) is SEPARATED when
+ *   d = sum_k |E[i, k] - E[j, k]|  >  tol            (float32 throughout; tol is the caller's float32(tol): numpy 2 casts 0.001 so)
+ * with d summed in numpy's float32 sum(axis=-1) order: D < 8 sequential from 0; 8 <= D: eight accumulators over the full 8-blocks,
+ * ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail in order.  NaN compares false and never separates.
+ * Bitmap (uint64 words, zeroed by the caller once; the kernels only OR bits in, so updates accumulate over seeds):
+ *   all pairs : G rows of W = ceil(G / 64) words; bit (j & 63) of word [i W + (j >> 6)] = pair (i, j), used for i < j < G only --
+ *               every other bit stays 0.  G W words: 0.54 GB at G = 65536.
+ *   pair list : bit (p & 63) of word [p >> 6] = pair p of pairs [P, 2] (int32); ceil(P / 64) words.  A pair with an index outside
+ *               [0, G) is not read and never separates.
+ * gml_pair_bitmap_words(G, P): words of the bitmap (P < 0: all pairs of G); -1 for G outside [0, 65536].
+ * gml_pair_count_similar: *count (int64, device) = the number of CLEAR valid bits (pairs never separated); pairs == NULL: all pairs
+ *   of G, else a list of P pairs (pairs is not read).  A memset then one accumulate launch: capturable, no host read.
+ * gml_pair_list_similar: the never-separated pairs as int64 (i, j) into out [cap, 2] in bitmap order -- ascending (i, j) for all
+ *   pairs, list order for a list -- by a scan (count, one-workgroup prefix, emit), so the order is the same on every run;
+ *   *count = the true total even when it exceeds cap.  ws: gml_pair_list_workspace_bytes(G, P) bytes (P < 0: all pairs).
+ * Arguments outside these ranges or misaligned: GML_E_BADARG. */
+int64_t gml_pair_bitmap_words(int64_t G, int64_t P);
+int gml_pair_distinct_all(const float* E, int64_t ldE, int64_t G, int32_t D, float tol, uint64_t* bits, gml_stream_t stream);
+int gml_pair_distinct_list(const float* E, int64_t ldE, int64_t G, const int32_t* pairs, int64_t P, int32_t D, float tol,
+                           uint64_t* bits, gml_stream_t stream);
+int gml_pair_count_similar(const uint64_t* bits, int64_t G, const int32_t* pairs, int64_t P, int64_t* count, gml_stream_t stream);
+size_t gml_pair_list_workspace_bytes(int64_t G, int64_t P);
+int gml_pair_list_similar(const uint64_t* bits, int64_t G, const int32_t* pairs, int64_t P, int64_t* out, int64_t cap,
+                          int64_t* count, void* ws, size_t ws_bytes, gml_stream_t stream);
+
 /* ---------------------------------------------------------------- dense-block SpectConv (equal-size graphs, near-dense masks)
  * The TF formulation of the layer, /root/reference/libs/layers_tf.py:231-236 (s0 = matmul(support[:, i], x); out += s0 . W_i),
  * for batches of B graphs of exactly n <= 96 nodes (MNIST-75: n = 75, S = 6).
