@@ -160,6 +160,8 @@ extern "C" int gml_csr_from_coo(const int64_t* key, const int64_t* other_in, int
 // Keys that are ALREADY non-decreasing (the reference's transform emits edge_index2 in row-major np.where order,
 // libs/utils.py:608-609: sorted by source): the view keyed by them needs no sort at all -- rowptr from the run
 // boundaries, perm = identity.  A decreasing pair sets bit 1 of *bad (the caller then builds this view the general way).
+// Two edges of the same row whose other ids decrease set bit 3 (value 8): the view is valid, but its columns are not ascending
+// inside every row, which the mirror search of gml_edge_sym_flags needs (a fact for the caller, not an error).
 __global__ void gml_k_sorted_view(const int64_t* __restrict__ key, const int64_t* __restrict__ other_in, int64_t E, int64_t N,
                                   int32_t* __restrict__ rowptr, int32_t* __restrict__ other, int32_t* __restrict__ perm,
                                   int32_t* __restrict__ bad) {
@@ -174,6 +176,7 @@ __global__ void gml_k_sorted_view(const int64_t* __restrict__ key, const int64_t
     // Not sorted: flagged.  rowptr was zero-filled and only ever receives values <= E, perm is the identity and other is
     // range-checked, so whatever the caller launches on these arrays before it reads the flag stays inside them.
     if (kcur < kprev) { atomicOr(bad, 2); return; }
+    if (e > 0 && e < E && kcur == kprev && other_in[e] < other_in[e - 1]) atomicOr(bad, 8);
     for (int64_t r = kprev + 1; r <= kcur; ++r) rowptr[r] = (int32_t)e;      // rows (kprev, kcur] start at e (empty rows included)
 }
 

@@ -29,7 +29,9 @@
 
 // flag / mirror of every edge of the SOURCE-keyed view (row r = source, col_t = targets ascending inside a row).  2^LPS lanes share a
 // source row and deal its edges (the row is known without a search; ZINC-like rows hold ~6 edges: 4 lanes per row), the mirror is
-// found by bisection in the target's row
+// found by bisection in the target's row.  PRECONDITION: columns ascending inside every row (the bisection, and the neighbour test
+// for repeated edges, rely on it; a row out of order leaves records unwritten or written by two lanes).  The caller checks it:
+// GraphCSR.sym_index runs this pass only on a view whose rows were recorded sorted when the index was built
 __global__ __launch_bounds__(256) void gml_k_edge_sym_flags(const int32_t* __restrict__ rowptr_t, const int32_t* __restrict__ col_t,
                                                            const uint32_t* __restrict__ val, int64_t N, int64_t E, int S, int LPS,
                                                            int32_t* __restrict__ flag, int32_t* __restrict__ mirror) {

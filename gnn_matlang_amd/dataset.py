@@ -219,6 +219,9 @@ class DeviceDataset(object):
         src, dst = self.edge_index2[0] + nbase, self.edge_index2[1] + nbase
         if E2 > 1 and not bool((src[1:] >= src[:-1]).all()):
             raise ValueError('prepare(): the support edges of every graph must be sorted by source (SpectralDesign emits them so)')
+        # targets ascending inside every source row too (SpectralDesign's row-major order; any order is accepted): the source view of an
+        # exact batch keeps each graph's edge order, and the pairing pass of GraphCSR.sym_index needs its rows sorted
+        rows_sorted = E2 <= 1 or bool(((src[1:] > src[:-1]) | (dst[1:] >= dst[:-1])).all())
         order = torch.sort(dst, stable=True)[1]                           # global stable target sort = per-graph stable target sort
         k = torch.arange(E2, device=dev)
         tperm = (order - ebase[order]).int()                              # [position in target order] -> local source-order position
@@ -231,7 +234,7 @@ class DeviceDataset(object):
             return (torch.cumsum(cnt, 0) - cnt - first).int()
         S = int(self.edge_attr2.size(1))
         es = Fn.edge_presplit(self.edge_attr2.contiguous()) if S <= 8 else None
-        self._prep = dict(tperm=tperm.contiguous(), tinv=tinv, rp_src=local_rows(src), rp_dst=local_rows(dst), es=es,
+        self._prep = dict(tperm=tperm.contiguous(), tinv=tinv, rp_src=local_rows(src), rp_dst=local_rows(dst), es=es, rows_sorted=rows_sorted,
                           x=self.x.contiguous(), ea=self.edge_attr2.contiguous(), ei2=self.edge_index2.contiguous(), y=self.y.contiguous())
         self._prep.update(self.adjacency_structure())
         return self
@@ -446,6 +449,8 @@ class DeviceDataset(object):
             # the second host read: the batch's group maxima (what GraphCSR.from_edge_index reads for a new batch)
             mx = torch.stack([g.ginfo_t128[:, 1].max(), g.ginfo_t128[:, 3].max(), g.ginfo128[:, 1].max(), g.ginfo128[:, 3].max()]).tolist()
             g.gmax_t128, g.gmax128 = (int(mx[0]), int(mx[1])), (int(mx[2]), int(mx[3]))
+            # (what from_edge_index records for the same edges: sources ascend inside every target row of the stable target sort)
+            g.col_sorted, g.col_t_sorted = True, P['rows_sorted']
         else:
             g.gmax_t128 = g.gmax128 = (int(bounds['caps'][0]), int(bounds['caps'][1]))
             g.static_shape = True

@@ -35,7 +35,7 @@ def _require_cuda(t, name):
 
 
 class GraphCSR(object):
-    __slots__ = ('N', 'E', 'device', 'rowptr', 'col', 'perm', 'rowptr_t', 'col_t', 'pos_t', 'perm_t', 'src_sorted',
+    __slots__ = ('N', 'E', 'device', 'rowptr', 'col', 'perm', 'rowptr_t', 'col_t', 'pos_t', 'perm_t', 'src_sorted', 'col_sorted', 'col_t_sorted',
                  '_ginfo', '_ginfo_t', '_gmax', '_gmax_t', 'ginfo_t128', 'gmax_t128', 'ginfo128', 'gmax128', 'tpos', '_val_cache', '_keep', '_r64',
                  '_r64t', '_bad', 'static_shape', '_sym_dev')
 
@@ -48,6 +48,9 @@ class GraphCSR(object):
         self._bad = None
         self._sym_dev = None                                   # (supports, uid, mir, count): an assembled batch's pairing (dataset.py)
         self.static_shape = False                              # True: a static-shape batch whose tensors are refilled in place (dataset.py)
+        # columns known to ascend inside every row of the target view (col) / the source view (col_t): what the mirror search of
+        # gml_edge_sym_flags needs (sym_index).  False unless a construction site established it: a site that cannot loses speed only
+        self.col_sorted = self.col_t_sorted = False
 
     @staticmethod
     def from_edge_index(edge_index, num_nodes, assume_source_sorted=True, static_caps=None):
@@ -72,8 +75,8 @@ class GraphCSR(object):
             L = _lib.lib()
             nws = max(int(L.gml_csr_workspace_bytes(N, E)), 4)
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-            bad = ws[nws - 4:].view(torch.int32)               # bit 0: a node id out of range; bit 1: source keys not sorted
-            bad.zero_()
+            bad = ws[nws - 4:].view(torch.int32)               # bit 0: a node id out of range; bit 1: source keys not sorted;
+            bad.zero_()                                        # bit 3: targets decrease inside a source row (not an error)
             src, dst = ei[0], ei[1]
             g.rowptr, g.col, g.perm = torch.empty(N + 1, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
             _lib.call('gml_csr_from_coo', _ptr(dst), _ptr(src), N, E, _ptr(g.rowptr), _ptr(g.col), _ptr(g.perm),
@@ -112,6 +115,10 @@ class GraphCSR(object):
             if mx[2] & 2:                                      # source keys were not sorted: general construction
                 return GraphCSR.from_edge_index(edge_index, num_nodes, assume_source_sorted=False)
             g.src_sorted = bool(assume_source_sorted)
+            # a stable target sort of source-sorted edges keeps the sources ascending inside every target row; the source view's
+            # targets are in input order, ascending unless the sorted-view pass saw them decrease
+            g.col_sorted = g.src_sorted
+            g.col_t_sorted = g.src_sorted and not (mx[2] & 8)
         return g
 
     def check(self):
@@ -252,8 +259,9 @@ class GraphCSR(object):
         target-sorted order (view='target': inference): the edges the edge branch has to evaluate and, per entry, the mirror edge (j, i)
         that carries bitwise the same row (-1: none) -- include/gml.h gml_edge_sym_flags.  Cached on the tensor's identity like the
         other derived arrays; None when nothing can be shared (S outside 2 .. 16, supports that carry a gradient, fewer than 10 % of the
-        evaluations saved), for static-shape batches (their tensors are refilled in place by every replay of a captured step) or
-        while a HIP graph is being captured (the list's length is data).
+        evaluations saved), for static-shape batches (their tensors are refilled in place by every replay of a captured step),
+        while a HIP graph is being captured (the list's length is data), or when the view's columns are not known to ascend inside
+        every row (col_t_sorted / col_sorted: the pairing pass finds mirrors by bisection).
         A batch assembled with its data set's pairing (DeviceDataset.batch_assembled(sym=True)) carries the list for its supports in
         source order: returned as (uid, mir, count) -- capacity E, count [1] on the device -- static shapes and capture included."""
         S = int(val.size(1))
@@ -263,6 +271,8 @@ class GraphCSR(object):
             return sd[1:]
         if not (2 <= S <= 16) or val.requires_grad or self.E == 0 or self.E * S * 4 >= 0x7fffff00 or getattr(self, 'static_shape', False):
             return None
+        if not (self.col_t_sorted if view == 'source' else self.col_sorted):
+            return None
         key = ('y' + view[0], val.data_ptr(), val._version, tuple(val.shape))
         hit = self._val_cache.get(key)
         if hit is not None:
@@ -270,8 +280,9 @@ class GraphCSR(object):
         if torch.cuda.is_current_stream_capturing():
             return None
         rp, cl = (self.rowptr_t, self.col_t) if view == 'source' else (self.rowptr, self.col)
-        flag = torch.empty(self.E, dtype=torch.int32, device=val.device)
-        mirror = torch.empty(self.E, dtype=torch.int32, device=val.device)
+        # (a record the pass leaves unwritten reads "evaluate alone")
+        flag = torch.full((self.E,), 1, dtype=torch.int32, device=val.device)
+        mirror = torch.full((self.E,), -1, dtype=torch.int32, device=val.device)
         _lib.call('gml_edge_sym_flags', _ptr(rp), _ptr(cl), _ptr(val), self.N, self.E, S, _ptr(flag), _ptr(mirror), _stream(val.device))
         idx = torch.nonzero(flag, as_tuple=False).view(-1)
         out = (idx.to(torch.int32), mirror[idx]) if idx.numel() <= 0.9 * self.E else None

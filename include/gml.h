@@ -146,7 +146,8 @@ int gml_csr_from_coo(const int64_t* key, const int64_t* other_in, int64_t num_no
 /* The same for keys that are ALREADY non-decreasing (edge_index2 as the reference's transform emits it is sorted by
  * source, libs/utils.py:608-609): no sort -- rowptr from the run boundaries, perm = identity, one pass.  If a key is
  * smaller than its predecessor, bit 1 (value 2) of the workspace's flag word is set and the outputs are unspecified: the
- * caller must then use gml_csr_from_coo for this view. */
+ * caller must then use gml_csr_from_coo for this view.  If two edges of the same row have decreasing other ids, bit 3
+ * (value 8) is set: the view is valid, but its columns are not ascending inside every row (gml_edge_sym_flags needs them so). */
 int gml_csr_from_sorted_coo(const int64_t* key, const int64_t* other_in, int64_t num_nodes, int64_t num_edges,
                             int32_t* rowptr, int32_t* other, int32_t* perm,
                             void* ws, size_t ws_bytes, gml_stream_t stream);
@@ -416,8 +417,10 @@ int gml_edge_mlp_fwd_stack6(const float* ea, int32_t nlayers, const float* const
 /* The edge branch over a batch's UNIQUE support rows (csrc/gml_edge_chain_sym_impl.h).  SpectralDesign's supports sample symmetric
  * matrices (libs/utils.py:546-610), so edge (i, j) and its mirror (j, i) mostly carry bitwise the same row and the branch
  * (libs/spect_conv.py:205-207) gives both the same output.  gml_edge_sym_flags: per edge of the SOURCE-keyed view (rowptr_t, col_t of
- * gml_csr_from_coo; val_s [num_edges, S] in that order) flag = 2 (evaluate, and the mirror at position mirror[k] takes the same
- * row: src < dst, rows bitwise equal), 0 (covered by its mirror) or 1 (evaluate alone); mirror = -1 unless flag = 2.  The caller
+ * gml_csr_from_coo; val_s [num_edges, S] in that order; PRECONDITION: columns ascending inside every row -- the mirror is found by
+ * bisection and a repeated edge by its neighbours, so a row out of order leaves records unwritten or written twice) flag = 2
+ * (evaluate, and the mirror at position mirror[k] takes the same row: src < dst, rows bitwise equal), 0 (covered by its mirror) or
+ * 1 (evaluate alone); mirror = -1 unless flag = 2.  The caller
  * compacts the edges with flag > 0 into uid / mir [num_unique] (int32).  gml_edge_mlp_fwd_stack6_sym: gml_edge_mlp_fwd_stack6 over
  * those entries, out[l][uid[u]] and out[l][mir[u]] written (every row of out is written exactly once when uid / mir come from the flags).
  * gml_edge_mlp_bwd_sym: gml_edge_mlp_bwd (no gin) with gout[uid[u]] + gout[mir[u]] as the entry's output gradient; partial rows in ws:
