@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- GNNML3 training-step throughput on ZINC-12k-shaped synthetic graphs (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--batch GRAPHS_PER_GPU | --global-batch GRAPHS] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--batch GRAPHS_PER_GPU | --global-batch GRAPHS] [--dump-outputs DIR] [--full]
 
 K is the number of timed steps.  --dump-outputs DIR writes what the last of them returned (loss, parameters, gradients) as
 DIR/<name>.npy; the inputs and the initial parameters are seeded, so two builds run with the same arguments can be compared
 output for output.
+
+A plain run does only what the headline needs: it builds the batch, warms up, settles the GPU (--min-seconds), times the K
+steps, writes --dump-outputs and prints the line.  --full adds every side measurement listed below.  The timed steps and
+their outputs are the same either way: the side measurements run after them, except the parity check at the initial
+parameters, which changes nothing the step reads.
 
 A step = forward + L1-sum loss + backward + (N>1: one flat SUM all-reduce of the gradients) + Adam,
 of the reference's ZINC GNNML3 (Zinc12k.py:310-371: 4 x ML3Layer 30+2, S = 8 supports, 25 input
@@ -19,7 +24,7 @@ arithmetic, whose trained-state gradients miss 1e-4; ``value_exact_fp32`` the st
 With --gpus N > 1 and no WORLD_SIZE in the environment bench.py starts the N ranks itself
 (python -m torch.distributed.run ...) before touching the GPU and relays rank 0's line.
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields:
+Rank 0 prints ONE JSON line.  Besides the contract's fields, with --full (and the full record in bench_extras.json):
   roofline        the dominant kernel (fused SpectConv backward), timed live with HIP events on the launch stream
   fresh_batch     the same step when every step receives a NEW batch: CSR, group records, bf16 pre-split and the
                   source-order copy are rebuilt inside the timed region (the reference reshuffles every epoch)
@@ -161,6 +166,10 @@ def parse_args():
                     'step on a copy of the model (the timed steps and their outputs are the same whatever this is)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write what the last timed step '
                     'returned to its caller as DIR/<name>.npy: the loss, the parameters the step left and their gradients')
+    ap.add_argument('--full', action='store_true', help='also take every side measurement: rooflines and '
+                    'per-kernel times, other arithmetics, sizes and configs, the reference batch size, the CPU baseline, the parity '
+                    'checks against the oracle, the data-parallel costs; writes the full record to bench_extras.json.  The '
+                    'options below narrow a --full run; a plain run takes none of these measurements')
     ap.add_argument('--cpu-graphs', type=int, default=2048)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-profile', action='store_true', help='skip the live per-kernel HIP-event timing and the extra measurements')
@@ -169,7 +178,11 @@ def parse_args():
                     '(no tiling of a pool), supports built by the device SpectralDesign; 0 = skip')
     ap.add_argument('--ref-batch', type=int, default=64, help='also time the reference batch size (Zinc12k.py:20) as a '
                     'HIP-graph-captured step; 0 = skip')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                                  # a plain run: none of the side measurements
+        args.no_cpu = args.no_profile = args.no_extras = True
+        args.distinct = args.ref_batch = 0
+    return args
 
 
 def dump_outputs(out_dir, loss, model):
@@ -564,7 +577,7 @@ def main():
     lossv = float(loss.item())
     assert np.isfinite(lossv) or os.environ.get('GML_BENCH_NOCHECK'), 'loss diverged'   # (NOCHECK: ablation builds)
     dp = None
-    if world > 1:
+    if world > 1 and args.full:
         # ---- what the collective costs (every rank runs this: collectives): each rank's own timed steps, the flat gradient
         #      all-reduce alone, and the reference's batch size per rank as ONE captured HIP graph with the all-reduce inside
         from gnn_matlang_amd.dist import TrainStep
@@ -623,14 +636,15 @@ def main():
                    final_loss=lossv, blocks=1, block_seconds=[round(own_dt, 4)],
                    n_ranks_seen=dist.get_world_size() if world > 1 else 1,
                    rccl_version='.'.join(str(v) for v in torch.cuda.nccl.version()) if (world > 1 and not share) else None)
-        try:                                                   # share of the support rows the edge branch evaluates (the rest: bitwise mirrors)
-            csr_ = data.csr('edge_index2')
-            sym_ = csr_.sym_index(data.edge_attr2) if (Fn.EDGE_SYM and csr_.src_sorted) else None
-            res['edge_unique_rows'] = dict(share=(sym_[0].numel() / csr_.E) if sym_ is not None else 1.0, enabled=bool(Fn.EDGE_SYM),
-                                           note='edge (i, j) and its mirror (j, i) carry bitwise the same supports (symmetric spectral matrices): the edge '
-                                                'branch runs once per unique row, exact (csrc/gml_edge_chain_sym_impl.h); GML_EDGE_SYM=0 evaluates every row')
-        except Exception as e_:                                # noqa: BLE001 (a context figure: never fatal)
-            res['edge_unique_rows'] = dict(error=repr(e_)[:200])
+        if args.full:
+            try:                                               # share of the support rows the edge branch evaluates (the rest: bitwise mirrors)
+                csr_ = data.csr('edge_index2')
+                sym_ = csr_.sym_index(data.edge_attr2) if (Fn.EDGE_SYM and csr_.src_sorted) else None
+                res['edge_unique_rows'] = dict(share=(sym_[0].numel() / csr_.E) if sym_ is not None else 1.0, enabled=bool(Fn.EDGE_SYM),
+                                               note='edge (i, j) and its mirror (j, i) carry bitwise the same supports (symmetric spectral matrices): the edge '
+                                                    'branch runs once per unique row, exact (csrc/gml_edge_chain_sym_impl.h); GML_EDGE_SYM=0 evaluates every row')
+            except Exception as e_:                            # noqa: BLE001 (a context figure: never fatal)
+                res['edge_unique_rows'] = dict(error=repr(e_)[:200])
         if shard_imb is not None:
             res['sharding'] = shard_imb
         if dp is not None:
@@ -1055,9 +1069,10 @@ def main():
                 if parity0 is not None:
                     res['max_rel_err_vs_oracle'] = pick(parity0)                       # (initial parameters: the pinned state)
                 res['max_rel_err_vs_oracle_after_training'] = pick(res['parity_vs_oracle_after_training'])
-        where = write_extras(res)
-        res['extras'] = 'bench_extras.json'
-        log('full record (%d characters): %s' % (len(json.dumps(res)), ', '.join(where) or 'not written'))
+        if args.full:
+            where = write_extras(res)
+            res['extras'] = 'bench_extras.json'
+            log('full record (%d characters): %s' % (len(json.dumps(res)), ', '.join(where) or 'not written'))
         sys.stdout.flush()
         print(compact_line(res), flush=True)
     if world > 1:

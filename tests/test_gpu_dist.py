@@ -81,12 +81,29 @@ def test_bench_dump_outputs_after_exactly_the_requested_steps(tmp_path):
         assert rel_err(a[k], b[k]) <= 1e-5, (k, rel_err(a[k], b[k]))
 
 
+def test_bench_plain_run_takes_no_side_measurements(tmp_path):
+    """A plain run prints the headline alone and writes no full record; --full takes the side measurements (here the per-kernel
+    profile and its rooflines) after the same timed steps, whose outputs agree with the plain run's."""
+    runs = []
+    for extra in ([], ['--full']):
+        out = tmp_path / ('full' if extra else 'plain')
+        d = _run_bench(['--gpus', '1', '--batch', '2048', '--dump-outputs', str(out)] + extra)
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and np.isfinite(d['value'])
+        runs.append((d, {f[:-4]: np.load(out / f) for f in os.listdir(out)}))
+    (plain, a), (full, b) = runs
+    for k in ('roofline', 'kernels_ms_per_step', 'edge_unique_rows', 'extras'):
+        assert k not in plain and k in full, k
+    assert set(a) == set(b)
+    for k in a:
+        assert rel_err(a[k], b[k]) <= 1e-5, (k, rel_err(a[k], b[k]))
+
+
 def test_bench_two_ranks_share_the_device_over_gloo():
     """bench.py's N > 1 code path on the 1-GPU box: two spawned ranks on cuda:0 over gloo
     (GML_BENCH_SHARE_DEVICE=1) -- sharded batch, flat all-reduce per step, per-rank times, all-reduce timing and the captured
     batch-64 step (gloo collectives cannot be captured: that record carries the error string here, the graph on RCCL)."""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu', '--no-extras', '--ref-batch', '0',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--no-cpu', '--no-extras', '--ref-batch', '0',
            '--min-seconds', '0', '--gpus', '2', '--batch', '2048']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', GML_BENCH_SHARE_DEVICE='1'))
@@ -115,7 +132,7 @@ def test_bench_strong_scaling_four_ranks_share_the_device():
     global data set cut by shard_graphs_balanced into four shards balanced by support edges, one flat all-reduce per step, per-rank
     times -- and the captured batch-64 step records an error string instead of hanging where the collective cannot be captured (gloo)."""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu', '--no-extras', '--ref-batch', '0',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--no-cpu', '--no-extras', '--ref-batch', '0',
            '--min-seconds', '0', '--gpus', '4', '--global-batch', '4096']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', GML_BENCH_SHARE_DEVICE='1'))
