@@ -1,10 +1,10 @@
 // Fused backward, bf16x3, third layout (default for S in {2,4,6,8}, Fin <= 32, 16 < Fout <= 32, and -- NOB = 1 -- for
-// counting.py's S = 12, Fout <= 16): same outputs as gml_k_spectconv_bwd / gml_k_spectconv_bwd2
+// counting.py's S = 12, Fout <= 16): same outputs as gml_k_spectconv_bwd
 //
 //   dX = sum_s A_s (G W_s^T),   dval[e,s] = < X[src] W_s, G[dst] >,   dW_s = X^T (A_s G)
 //
-// What changed against bwd2 (profiles/r02a_*: VALU 43 %, LDS 52 % busy -- half of it bank conflicts --, matrix pipe 20 %,
-// waves parked 39 % of their cycles):
+// What changed against the round-1 layout bwd2 (since removed; profiles/r02a_*: VALU 43 %, LDS 52 % busy -- half of it bank
+// conflicts --, matrix pipe 20 %, waves parked 39 % of their cycles):
 //   * ONE bf16 (hi, lo) image of W in LDS, [s][o][f], serves both projections: Z^T = W^T X^T reads its A fragments with
 //     ds_read_b128 (f contiguous), dX^T = W P^T reads the transposed fragments with ds_read_b64_tr_b16 (the hardware
 //     transposes 4 x 16 blocks) -- 32 KB instead of 64;
@@ -13,8 +13,8 @@
 //   * the row contraction of dW takes its operands from row-major bf16 images of X and P ([position][32 channels], written
 //     with one ds_write_b128 per lane and image) through ds_read_b64_tr_b16: the 36 matrix-core transposes, their 72
 //     conversions and 8-byte stores per tile are gone, four supports per slab (two barriers per slab, S/4 slabs);
-//   * NW = 8 waves / 128-row groups (one workgroup per CU) or NW = 4 waves / 64-row groups (78 KB of LDS: two
-//     independent workgroups per CU, whose matrix / LDS phases overlap each other's VALU edge phases).
+//   * NW = 8 waves / 128-row groups, one workgroup per CU (NW stays a template parameter; the 4-wave / 64-row geometry with two
+//     workgroups per CU measured slower twice and was removed, DESIGN s4.2).
 // All XOR keys of the LDS images are chosen with tools/lds_sim.py (conflict-free for every access kind that touches them).
 //
 // NOB = 1 (Fout <= 16; 12 supports fit the registers: 2 x 12 x 4 accumulators per lane): the lane (row, kq) owns outputs
@@ -32,36 +32,30 @@ __host__ __device__ __forceinline__ int gml_wkey3(int o) { return ((o >> 3) & 1)
 // and conflict-free transposing reads of 8 consecutive positions per lane group
 __host__ __device__ __forceinline__ int gml_tkey3(int pos) { return ((pos >> 2) & 1) | ((((pos >> 1) ^ (pos >> 2) ^ (pos >> 3)) & 1) << 1); }
 
-// structural variants of the ZINC shape class (A/B builds: tools/build_variant.py <name> -DGML_B3V=<bits>):
-//   1 = dval straight from the edge loop to global memory (one 8-byte store per lane and edge: no d rows in LDS, no copy-out
-//       phase, the P images of slab 0 are written right behind the edge barrier -- one workgroup barrier less per group)
-//   2 = the Z projection runs between the commit's LDS writes and the barrier that publishes them (it needs neither)
-//   4 = the next group's loads as buffer loads from per-group descriptors: the offsets are a per-lane constant plus a scalar,
-//       the hardware range check replaces the clamps (no 64-bit address arithmetic in the vector unit)
-//   8 = the waves of the second half issue the next group's loads AFTER their dX projection (the first half before): the
-//       address-unit-bound issue of one half overlaps the matrix-pipe-bound projection of the other (spills: not usable)
-//  16 = P accumulators cleared with packed moves;  64 = s_setprio 1 for the second half of the waves
-// 512 = (with 256) the NEXT group's commit (column ids, G window, row pointers -- regions dead since this group's edge barrier) sits
-//       in front of the last slab barrier of this group, which publishes it: no commit barrier at the top of a group
-// 1024 = (with 256) the edge loop software-pipelined over two register sets: the G row of edge k + 1 and the column id of edge
-//       k + 2 are requested before the arithmetic of edge k (the loop's two dependent LDS round trips leave the critical path)
-// 2048 = (with 512) the next group's loads are issued BEFORE this group's edge loop (its registers have room for them: the
-//       staging registers of the rolled form are dead there): the address-unit-bound issue overlaps the VALU-bound loop
-// 256 = (with 1) value rows from global memory in the edge loop (two rows in flight per lane, the group's lines touched at its
-//       top): no value rows in the staging registers, in the commit or in the LDS; the freed 28 KB give the images regions of
-//       their own, and with nothing aliased the barrier at the top of a group goes
-// default (round 5): 1 + 4 + 16 + 256 + 512, A/B'd step by step on single boxes (profiles/r05_bwd3_variants_ab.txt)
-#ifndef GML_B3V
-#define GML_B3V 789
-#endif
-
+// Forms of the group loop by shape class (round 5; each A/B'd step by step on single boxes, profiles/r05_bwd3_variants_ab.txt, which
+// also records the variants that lost and are no longer in this file).  The classes that take none of them -- S = 2 / 4 / 6 with
+// NFB <= 2, S = 12, NOB = 1 -- keep LDS-staged value rows, dval rows in LDS and a copy-out phase.
+//   VALG   value rows from global memory in the edge loop (two rows in flight per lane, the group's lines touched at its top): no
+//          value rows in the staging registers, in the commit or in the LDS; the freed 28 KB give the images regions of their own,
+//          and with nothing aliased the barrier at the top of a group goes.  S = 8, and the one-launch 48-feature class (S = 6 / 4,
+//          NFB = 3: its staged value rows, 24 registers, were spilling).
+//   DIRECT dval straight from the edge loop to global memory (one 8-byte store per lane and edge: no d rows in LDS, no copy-out
+//          phase, the P images of slab 0 are written right behind the edge barrier -- one workgroup barrier less per group).
+//          The classes without the dval += branch: S = 8 with NOB = 2, and VALG's.
+//   LATEC  the NEXT group's commit (column ids, G window, row pointers -- regions dead since this group's edge barrier) sits in
+//          front of the last slab barrier of this group, which publishes it: no commit barrier at the top of a group.  VALG with
+//          two dW slabs.
+//   BUFLD  the next group's loads as buffer loads from per-group descriptors: the offsets are a per-lane constant plus a scalar,
+//          the hardware range check replaces the clamps (no 64-bit address arithmetic in the vector unit).  S = 8, NOB = 2 with
+//          float4-addressable x rows (XV).
+// In every class the P accumulators are cleared with packed moves.
 template <int S, int NFB, int NW, int NOB = 2>
 struct GmlBwd3Cfg {
     static constexpr int ROWS = 16 * NW, NT = 64 * NW;
     // register-batched staging bounds (per group): 8 edges per row; 12 for counting.py's S = 12; 16 for S = 6 -- sr25.py's supports
     // have 13 entries per row (1,664 per 128 rows), and 6 supports leave the registers for it
     static constexpr int ECAP_MAX = (S > 8 ? 12 : (S == 6 ? 16 : 8)) * ROWS;
-    static constexpr int XCAP_MAX = NW == 8 ? 224 : 160;
+    static constexpr int XCAP_MAX = 224;
     static constexpr int LDG = 16 * NOB + 4;                 // G window rows (floats, b128 aligned)
     // NFB = 3 (33 .. 48 input features: sr25.py's 32 + 16, mutag.py's 24 + 24 hidden widths, round 5): a SECOND image of everything
     // that is laid out in 32-feature rows -- W [s][o][f 32 .. 63], the X rows -- with the same keys and access code; features >= Fin zero
@@ -78,17 +72,16 @@ struct GmlBwd3Cfg {
     static constexpr int PT_BYTES = 2 * SS * ROWS * 64;      // P hi, lo   [se][position][32 o]
     static constexpr int GREC = 4 + ROWS / 4;                // ints per group record (ranked)
     static constexpr bool ASHARE = NW % (NOB * NFB) == 0;    // a wave's blocks share one X fragment (fb the same for all of them)
-    static constexpr bool OK = (S % SS == 0) && (NFB >= 1 && NFB <= 3) && (NW == 4 || NW == 8) && (NOB == 1 || NOB == 2) &&
-                               (NFB < 3 || (NOB == 2 && NW == 8 && S <= 6));
+    static constexpr bool OK = (S % SS == 0) && (NFB >= 1 && NFB <= 3) && NW == 8 && (NOB == 1 || NOB == 2) &&
+                               (NFB < 3 || (NOB == 2 && S <= 6));
     __host__ __device__ static size_t stage_bytes(int ecap, int xcap) { return (size_t)ecap * S * 4 + (size_t)xcap * LDG * 4; }
     __host__ __device__ static size_t r_bytes(int ecap, int xcap) {          // staged values + G window, later the P slab
         const size_t a = stage_bytes(ecap, xcap);
         return a > (size_t)PT_BYTES ? a : (size_t)PT_BYTES;
     }
-    // VALG (GML_B3V & 256, the ZINC shape class): the value rows are read from global memory inside the edge loop, so the LDS holds
-    // column ids + G window and -- in regions of their own, aliasing nothing -- the X image and one P slab
-    // (round 5: also sr25's one-launch 48-feature class, S = 6 / NFB = 3 -- its staged value rows, 24 registers, were spilling)
-    static constexpr bool VALG = (GML_B3V & 256) && NOB == 2 && NW == 8 && (S == 8 || ((S == 6 || S == 4) && NFB == 3 && !(GML_B3V & 16384)));
+    // VALG (see the head of this file): the LDS holds column ids + G window and -- in regions of their own, aliasing nothing -- the
+    // X image and one P slab
+    static constexpr bool VALG = NOB == 2 && NW == 8 && (S == 8 || ((S == 6 || S == 4) && NFB == 3));
     __host__ __device__ static size_t lds_bytes(int ecap, int xcap) {
         if (VALG) return (size_t)W_BYTES + (ROWS + 8) * 4 + (size_t)ecap * 4 + (size_t)xcap * LDG * 4 + XT_BYTES + PT_BYTES;
         return (size_t)W_BYTES + (ROWS + 8) * 4 + (size_t)ecap * 4 + r_bytes(ecap, xcap) + XT_BYTES;
@@ -155,23 +148,15 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
     static_assert(!DZ || NOB == 2, "the dz hand-over is compiled for the ZINC shape class");
     constexpr int LDG = C::LDG, ROWS = C::ROWS, NT = C::NT, SS = C::SS, BPW = C::BPW;
     constexpr int VAL_ALIGN = (S % 4 == 0) ? 4 : ((S % 2 == 0) ? 2 : 1);
-    constexpr bool DIRECT = (GML_B3V & 1) && NOB == 2 && (S == 8 || C::VALG);      // (the shape classes without the dval += branch)
-    constexpr bool ZEARLY = (GML_B3V & 2) != 0;
-    constexpr bool PINGPONG = (GML_B3V & 8) != 0;
-    constexpr bool BUFLD = (GML_B3V & 4) && S == 8 && NOB == 2 && XV;
-    constexpr bool PKZ = (GML_B3V & 16) != 0;
+    constexpr bool VALG = C::VALG;
+    constexpr bool DIRECT = NOB == 2 && (S == 8 || VALG);
+    constexpr bool LATEC = VALG && C::NSLAB == 2;
+    constexpr bool BUFLD = S == 8 && NOB == 2 && XV;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __bf16* W_h = reinterpret_cast<__bf16*>(lds_raw);        // [s][o][f], chunks XOR gml_wkey3(o)
     __bf16* W_l = W_h + C::W_HALF;
     int* rp_l = reinterpret_cast<int*>(lds_raw + C::W_BYTES);
     int* col_l = rp_l + ROWS + 8;
-    constexpr bool VALG = C::VALG;
-    constexpr bool LATEC = VALG && (GML_B3V & 512) && C::NSLAB == 2;
-    constexpr bool PIPE = VALG && (GML_B3V & 1024);
-    // (2048 with VALG: dead -- loads return in order, the loop's first value-row wait also waits for the whole prefetch.  4096: the
-    //  same placement WITHOUT value-row loads in the loop: LDS-staged value rows, only the dval stores are in flight there)
-    constexpr bool EARLYI = (LATEC && (GML_B3V & 2048)) || (DIRECT && !VALG && (GML_B3V & 4096));
-    static_assert(!VALG || DIRECT, "VALG needs the direct dval stores (GML_B3V bit 1)");
     unsigned char* rreg = reinterpret_cast<unsigned char*>(col_l + p.ecap);
     float* ea_l = reinterpret_cast<float*>(rreg);
     float* gs = VALG ? ea_l : ea_l + (size_t)p.ecap * S;
@@ -190,23 +175,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
     const int g0 = wg * p.groups_per_wg;
     const int g1 = min(g0 + p.groups_per_wg, p.ngroups);
 
-    if constexpr ((GML_B3V & 64) != 0) {
-        if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-    }
-#ifdef GML_B3DELAY
-    // experiment (NW = 4, two workgroups per CU): two workgroups started together run IN PHASE (same code, same durations: both in
-    // their VALU-bound edge loop, then both in their matrix-pipe phases); delaying one of each pair by ~half a group puts one's
-    // edge loop beside the other's projections.  GML_B3DELAY = number of s_sleep(127) (8 k cycles each), GML_B3DELAY_ODD: which half
-    if constexpr (NW == 4) {
-#ifdef GML_B3DELAY_ODD
-        const bool late = (blockIdx.x & 1) != 0;
-#else
-        const bool late = blockIdx.x >= gridDim.x / 2;
-#endif
-        if (late)
-            for (int i = 0; i < GML_B3DELAY; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     if constexpr (DZ || HAD) {
         if (tid < 128) wm_l[tid] = ((tid >> 5) < p.nmix && (tid & 31) < p.Fin) ? ((tid >> 5) < p.nmix1 ? p.wmix[(tid >> 5) * p.Fin + (tid & 31)] : p.wmix2[((tid >> 5) - p.nmix1) * p.Fin + (tid & 31)]) : 0.f;
     }
@@ -239,7 +207,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
 #endif
     // ---- staging registers: a group's global loads are issued one phase early (after the previous group's edge phase,
     //      before its stores) and committed to LDS at the top of the group; all unconditional with clamped indices so that
-    //      the compiler can count them (see gml_spectconv_bwd2_impl.h)
+    //      the compiler can count them
     // staged value rows move as float4 (S % 4 == 0) or float2 (S = 6, 2: 8-byte aligned rows) -- round 4: before, only float4 rows were
     // prefetched and a 6-support group staged with plain global -> LDS copies at its top (sr25: the whole load latency exposed per group)
     constexpr int VW = (S % 4 == 0) ? 4 : ((S % 2 == 0) ? 2 : 1);
@@ -542,10 +510,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
 #pragma unroll
                 for (int ob = 0; ob < NOB; ++ob) { Z[s][2 * ob] = f32x2{dd[ob][0], dd[ob][1]}; Z[s][2 * ob + 1] = f32x2{dd[ob][2], dd[ob][3]}; }
 #pragma unroll
-                for (int h = 0; h < NH; ++h) {
-                    if constexpr (PKZ) asm volatile("v_pk_mov_b32 %0, 0, 0" : "=v"(P[s][h]));
-                    else P[s][h] = f32x2{0.f, 0.f};
-                }
+                for (int h = 0; h < NH; ++h) asm volatile("v_pk_mov_b32 %0, 0, 0" : "=v"(P[s][h]));   // (packed clear: one move per pair)
             }
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * NOB * NIMG, 0);
 #pragma unroll
@@ -556,7 +521,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
         }
         if constexpr (HAD) had_post();
         };
-        if constexpr (ZEARLY) zproj();                       // (needs the W image and the lane's own x row only: neither is part of the commit)
         if constexpr (!LATEC) __syncthreads();
         GML_T3(1);
         // old dx values (accumulate mode): the lane's own row, features 16 fb + 4 kq .. + 3 (D rows of dX^T);
@@ -584,12 +548,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
         const int kbeg = rvalid ? rp_l[row] - kb : 0;
         const int kend = rvalid ? rp_l[row + 1] - kb : 0;
 
-        if constexpr (!ZEARLY) zproj();
-        if constexpr (EARLYI) {
-            latch();
-            issue((GML_ABL & 1) ? g0 : min(g + 1, g1 - 1));
-        }
-
+        zproj();
         GML_T3(2);
         // ---- edge phase (fp32 VALU, packed): P += val * G[dst],  d[s] = <Z[s], G[dst]>
         // (tried and measured slower, r02: requesting edge k + 1's value row / G row and edge k + 2's column before the
@@ -661,42 +620,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
             ldg_row(col_l[k], gv);
             edge_g(k, ev, gv);
         };
-        if constexpr (PIPE) {
-            asm volatile("" :: "v"(vtouch));
-            auto ldval = [&](int k, float (&ev)[S]) {
-                const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(vrs, k * (S * 4), 0, 0);
-                ev[0] = __uint_as_float(a.x); ev[1] = __uint_as_float(a.y); ev[2] = __uint_as_float(a.z); ev[3] = __uint_as_float(a.w);
-                if constexpr (S == 8) {
-                    const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(vrs, k * (S * 4) + 16, 0, 0);
-                    ev[4] = __uint_as_float(b.x); ev[5] = __uint_as_float(b.y); ev[6] = __uint_as_float(b.z); ev[7] = __uint_as_float(b.w);
-                } else if constexpr (S == 6) {               // 24-byte rows
-                    typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
-                    const u32x2v b = __builtin_amdgcn_raw_buffer_load_b64(vrs, k * (S * 4) + 16, 0, 0);
-                    ev[4] = __uint_as_float(b.x); ev[5] = __uint_as_float(b.y);
-                }
-            };
-            int k = kbeg;
-            const int klast = kend - 1;
-            if (k < ((GML_ABL & 4) ? kbeg : kend)) {
-                float eA[S], eB[S];
-                f32x2 gA[NH], gB[NH];
-                ldval(k, eA);
-                ldg_row(col_l[k], gA);
-                int cn = col_l[min(k + 1, klast)];
-                for (;;) {
-                    const int c2 = col_l[min(k + 2, klast)];
-                    ldval(min(k + 1, klast), eB);
-                    ldg_row(cn, gB);
-                    edge_g(k, eA, gA);
-                    if (++k >= kend) break;
-                    cn = col_l[min(k + 2, klast)];
-                    ldval(min(k + 1, klast), eA);
-                    ldg_row(c2, gA);
-                    edge_g(k, eB, gB);
-                    if (++k >= kend) break;
-                }
-            }
-        } else if constexpr (VALG) {
+        if constexpr (VALG) {
             // two value rows in flight per lane (two register sets, no rotation): the row of edge k + 1 is requested before the
             // arithmetic of edge k
             asm volatile("" :: "v"(vtouch));
@@ -717,43 +641,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
             if (k < ((GML_ABL & 4) ? kbeg : kend)) {
                 float eA[S], eB[S];
                 ldval(k, eA);
-                if constexpr ((GML_B3V & 8192) != 0) {
-                    // the column id of edge k + 1 travels one trip ahead (one register, one clamp): the loop's chain column id -> G row ->
-                    // arithmetic loses its first LDS round trip (the full two-set pipeline of G rows costs more than it hides: bit 1024)
-                    auto edge_c = [&](int kk, int c, const float (&ev)[S]) {
-                        f32x2 gv[NH];
-                        ldg_row(c, gv);
-                        edge_g(kk, ev, gv);
-                    };
-                    int c = col_l[k];
-                    for (;;) {
-                        const int kn = min(k + 1, klast);
-                        const int cn = col_l[kn];
-                        ldval(kn, eB);
-                        edge_c(k, c, eA);
-                        if (++k >= kend) break;
-                        const int kn2 = min(k + 1, klast);
-                        c = col_l[kn2];
-                        ldval(kn2, eA);
-                        edge_c(k, cn, eB);
-                        if (++k >= kend) break;
-                    }
-                } else if constexpr ((GML_B3V & 32768) != 0) {
-                    // pairs: the G rows of edges k and k + 1 are both requested at the top of a two-edge trip (two fixed register sets,
-                    // no rotation): the second gather's LDS round trip runs behind the first edge's arithmetic
-                    for (;;) {
-                        f32x2 gA[NH], gB[NH];
-                        const int kn = min(k + 1, klast);
-                        ldg_row(col_l[k], gA);
-                        ldg_row(col_l[kn], gB);
-                        ldval(kn, eB);
-                        edge_g(k, eA, gA);
-                        if (++k >= kend) break;
-                        ldval(min(k + 1, klast), eA);
-                        edge_g(k, eB, gB);
-                        if (++k >= kend) break;
-                    }
-                } else {
                 for (;;) {
                     ldval(min(k + 1, klast), eB);
                     edge(k, eA);
@@ -761,7 +648,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
                     ldval(min(k + 1, klast), eA);
                     edge(k, eB);
                     if (++k >= kend) break;
-                }
                 }
             }
         } else {
@@ -833,11 +719,8 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
         if constexpr (DIRECT) {
             if (p.dw_partial && !(GML_ABL & 2)) { write_x(); write_slab(0); }
         }
-        const bool late_issue = PINGPONG && (waveo & 4) != 0;
-        if (!EARLYI && !late_issue) {
-            latch();
-            issue((GML_ABL & 1) ? g0 : min(g + 1, g1 - 1));
-        }
+        latch();
+        issue((GML_ABL & 1) ? g0 : min(g + 1, g1 - 1));
         GML_T3(8);
 
         if (!DIRECT && p.dval && !(GML_ABL & 8)) {
@@ -944,10 +827,6 @@ __global__ __launch_bounds__(64 * NW, 2) void gml_k_spectconv_bwd3(const GmlBwdP
             }
         }
 
-        if (late_issue) {
-            latch();
-            issue((GML_ABL & 1) ? g0 : min(g + 1, g1 - 1));
-        }
         GML_T3(5);
         // ---- dW += X^T P over the rows of the group.  Row-major bf16 images [position = wave*16 + r16][32 channels]
         //      (a lane's 8 channels = one 16-byte chunk, XOR gml_tkey3(position)); the contraction reads them transposed.

@@ -3,7 +3,7 @@
 //
 //   out[r, :] = act( sum_s (sum_{k in row r} val[k, s] x[col[k], :]) W_s + b )
 //
-// organised like the backward kernel (gml_spectconv_bwd2_impl.h): one 512-thread workgroup per CU, groups of 128 target
+// organised like the backward kernel (gml_spectconv_bwd3_impl.h): one 512-thread workgroup per CU, groups of 128 target
 // rows, one 16-row tile per wave, the group record's degree-ranked row order (rows of a tile run near-equal edge
 // loops; rank blocks a and 7-a on the two waves of a SIMD).  With 64 accumulators per lane instead of the backward's
 // 128 there is room to keep the NEXT group's CSR slice, value rows and X window in flight in registers while this

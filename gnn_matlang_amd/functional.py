@@ -1235,8 +1235,6 @@ def _bwd_plan(csr, S, Fin, Fout):
             continue
         if rows == 128:
             ginfo, gmax = csr.ginfo_t128, csr.gmax_t128
-        elif rows == _lib.GML_GROUPS64_RANKED:
-            ginfo, gmax = csr.ranked64_t()
         else:
             ginfo, gmax = csr.ginfo_t, csr.gmax_t
         nbytes = int(L.gml_spectconv_bwd_workspace_bytes(csr.N, int(S), int(Fin), int(Fout), gmax[0], gmax[1], flags))

@@ -37,12 +37,11 @@ def _require_cuda(t, name):
 class GraphCSR(object):
     __slots__ = ('N', 'E', 'device', 'rowptr', 'col', 'perm', 'rowptr_t', 'col_t', 'pos_t', 'perm_t', 'src_sorted', 'col_sorted', 'col_t_sorted',
                  '_ginfo', '_ginfo_t', '_gmax', '_gmax_t', 'ginfo_t128', 'gmax_t128', 'ginfo128', 'gmax128', 'tpos', '_val_cache', '_keep', '_r64',
-                 '_r64t', '_bad', 'static_shape', '_sym_dev')
+                 '_bad', 'static_shape', '_sym_dev')
 
     def __init__(self):
         self._val_cache = OrderedDict()
         self._keep = None
-        self._r64t = None
         self._r64 = None
         self._ginfo = self._ginfo_t = self._gmax = self._gmax_t = None
         self._bad = None
@@ -178,20 +177,6 @@ class GraphCSR(object):
                           _ptr(gi), _stream(self.device))
                 self._r64 = (gi, None)
         return self._r64
-
-    def ranked64_t(self):
-        """(records, (max edges, max window)) of the source view in ranked 64-row groups: the staging schedule of the
-        4-wave backward kernel (two workgroups per CU); built on first use."""
-        if self._r64t is None:
-            self._no_capture('GraphCSR: ranked 64-row group records')
-            with torch.cuda.device(self.device):
-                rec = int(_lib.lib().gml_csr_group_record_ints(_lib.GML_GROUPS64_RANKED))
-                gi = torch.zeros(max((self.N + 63) // 64, 1), rec, dtype=torch.int32, device=self.device)
-                _lib.call('gml_csr_group_info', _ptr(self.rowptr_t), _ptr(self.col_t), self.N, _lib.GML_GROUPS64_RANKED,
-                          _ptr(gi), _stream(self.device))
-                mx = torch.stack([gi[:, 1].max(), gi[:, 3].max()]).tolist()
-                self._r64t = (gi, (int(mx[0]), int(mx[1])))
-        return self._r64t
 
     # values [E, S] in input-edge order -> target-sorted order (cached: raw supports are per-batch data)
     def sort_values(self, edge_attr, cache=True):

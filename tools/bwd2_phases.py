@@ -1,4 +1,4 @@
-"""Per-phase cycle shares of gml_k_spectconv_bwd2 (library built with GML_CXXFLAGS=-DGML_BWD2_TIMING)."""
+"""Per-phase cycle shares of gml_k_spectconv_bwd3 / bwd4 (library built with GML_CXXFLAGS=-DGML_BWD2_TIMING)."""
 import ctypes
 import os
 import sys
@@ -20,8 +20,8 @@ for it in range(3):
     loss.backward()
     torch.cuda.synchronize()
     L.gml_debug_bwd2_prof(buf, 1)
-names = ['top barrier (bwd2: + dW of the previous group)', 'commit staged regs + barrier', 'Z projection', 'edge phase', 'barrier', 'dX chain + dx stores', 'tail', 'dW contraction (bwd3)',
-         'next loads issued', 'dval stores', 'P split', 'dW images + slab barriers (bwd3)', '-', '-', '-', '-']
+names = ['top barrier', 'commit staged regs + barrier', 'Z projection', 'edge phase', 'barrier', 'dX chain + dx stores', 'tail', 'dW contraction',
+         'next loads issued', 'dval stores', 'P split', 'dW images + slab barriers', '-', '-', '-', '-']
 tot = float(sum(buf))
 for n, v in zip(names, buf):
     if v:
