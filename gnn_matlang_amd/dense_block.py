@@ -12,6 +12,10 @@ library GEMM shapes, left to rocBLAS through torch.  ``GML_DENSE_LIB=1`` (or the
 this kernel does not have) evaluates the support product with torch.bmm instead: the round-1 path, kept as the A/B
 baseline of tools/bench_mnist.py.  Same parameters and values as ``SpectConv`` on the sparse path
 (tests/test_gpu_parity.py compares both with the oracle and with the TF-graph fixture).
+
+One LARGE graph (96 < n <= 1024, F <= 64: the 2-D grid of filtering.py, 900 nodes, a 40 % full mask) takes the same form on
+csrc/gml_dense_big.hip: the work is cut across (support, row block, K slice) instead of across graphs, the projection stays the
+tall GEMM (``_SupportProduct`` dispatches by n; the chained one-launch kernels are n <= 96 only).
 """
 import os
 
@@ -41,12 +45,21 @@ class DenseSupports(object):
 
     def _pack(self, blocks, transpose):
         img = torch.empty(self.B, self.S, 2, self.n, self.KP, dtype=torch.int16, device=blocks.device)
-        _lib.call('gml_dense_pack', _ptr(blocks), _ptr(img), self.B * self.S, self.n, self.KP, transpose, _stream(blocks.device))
+        _lib.call('gml_dense_big_pack' if self.n > SMALL_N else 'gml_dense_pack', _ptr(blocks), _ptr(img), self.B * self.S, self.n, self.KP, transpose, _stream(blocks.device))
         return img
 
 
 def _library():
     return USE_LIBRARY or Fn.exact_mode()
+
+
+SMALL_N = 96                 # gml_dense.hip: one workgroup per graph
+BIG_N, BIG_F = 1024, 64      # gml_dense_big.hip: ONE graph of SMALL_N < n <= BIG_N nodes, F <= BIG_F features
+
+
+def big_applies(num_graphs, n, F):
+    """True when the large-graph dense support product covers this batch (host integers only)."""
+    return num_graphs == 1 and SMALL_N < n <= BIG_N and 1 <= F <= BIG_F
 
 
 def dense_supports(edge_index2, edge_attr2, ptr, n):
@@ -56,8 +69,9 @@ def dense_supports(edge_index2, edge_attr2, ptr, n):
     S = int(edge_attr2.size(1))
     if B * n != int(ptr[-1]):
         raise ValueError('dense blocks need equal-size graphs: %d graphs, %d nodes, n=%d' % (B, int(ptr[-1]), n))
-    if n > 96:
-        raise ValueError('dense blocks are built for n <= 96 nodes per graph, got %d' % n)
+    if n > SMALL_N and not (B == 1 and n <= BIG_N):
+        raise ValueError('dense blocks are built for n <= %d nodes per graph, or one graph of up to %d nodes: got %d graphs of %d'
+                         % (SMALL_N, BIG_N, B, n))
     src, dst = edge_index2[0], edge_index2[1]
     b = torch.div(src, n, rounding_mode='floor')
     i, j = src - b * n, dst - b * n
@@ -67,9 +81,16 @@ def dense_supports(edge_index2, edge_attr2, ptr, n):
 
 
 def support_mm(img, act, sup, F, sa, so, sum_s):
-    """gml_dense_support_mm on packed images: act [B n, >= F (+ s sa)] -> [B n, F] (sum_s) or [B n, S so]."""
+    """gml_dense_support_mm on packed images: act [B n, >= F (+ s sa)] -> [B n, F] (sum_s) or [B n, S so].
+    One graph of more than SMALL_N nodes: gml_dense_big_support_mm (csrc/gml_dense_big.hip)."""
     act = act.contiguous()
     out = torch.empty(sup.B * sup.n, F if sum_s else sup.S * so, dtype=torch.float32, device=act.device)
+    if sup.n > SMALL_N:
+        nws = int(_lib.lib().gml_dense_big_workspace_bytes(sup.S, sup.n, int(F), int(bool(sum_s))))
+        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=act.device)
+        _lib.call('gml_dense_big_support_mm', _ptr(img), _ptr(act), int(act.stride(0)), int(sa), _ptr(out), int(out.stride(0)), int(so),
+                  int(bool(sum_s)), sup.S, sup.n, sup.KP, int(F), _ptr(ws), nws, _stream(act.device))
+        return out
     _lib.call('gml_dense_support_mm', _ptr(img), _ptr(act), int(act.stride(0)), int(sa), _ptr(out), int(out.stride(0)), int(so),
               int(bool(sum_s)), sup.B, sup.S, sup.n, sup.KP, int(F), _stream(act.device))
     return out
@@ -81,14 +102,14 @@ class _SupportProduct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sup):
         ctx.sup, ctx.Fin = sup, int(x.size(1))
-        Fn._path('dense', 'support product fwd (bf16x3 HIP)', sup.S, ctx.Fin, ctx.Fin)
+        Fn._path('dense', 'support product fwd (bf16x3 HIP%s)' % (', large graph' if sup.n > SMALL_N else ''), sup.S, ctx.Fin, ctx.Fin)
         return support_mm(sup.fwd, x, sup, ctx.Fin, 0, ctx.Fin, False)
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
             return None, None
-        Fn._path('dense', 'support product bwd (bf16x3 HIP)', ctx.sup.S, ctx.Fin, ctx.Fin)
+        Fn._path('dense', 'support product bwd (bf16x3 HIP%s)' % (', large graph' if ctx.sup.n > SMALL_N else ''), ctx.sup.S, ctx.Fin, ctx.Fin)
         return support_mm(ctx.sup.bwd, g, ctx.sup, ctx.Fin, ctx.Fin, 0, True), None
 
 
@@ -236,9 +257,9 @@ def spectconv_dense(x, sup, weight, bias, n, relu=False):
         h = torch.bmm(sup.blocks.view(sup.B, S * n, n), x.view(sup.B, n, Fin))
         h = h.view(sup.B, S, n, Fin).permute(0, 2, 1, 3).reshape(sup.B * n, S * Fin)
     else:
-        if Fin > 128:
-            raise ValueError('the dense-block kernel covers Fin <= 128, got %d' % Fin)
-        if CHAIN and Fout <= 128:
+        if Fin > (BIG_F if n > SMALL_N else 128):
+            raise ValueError('the dense-block kernel covers Fin <= %d at n = %d, got %d' % (BIG_F if n > SMALL_N else 128, n, Fin))
+        if CHAIN and Fout <= 128 and n <= SMALL_N:
             return _DenseConv.apply(x, weight, bias, sup, relu)
         h = _SupportProduct.apply(x, sup)
     out = _TallGemm.apply(h, weight.reshape(S * Fin, Fout), bias)

@@ -1031,6 +1031,57 @@ class HeadL1BigFunction(torch.autograd.Function):
         return gp, None, None, dw1, db1, dw2, db2, None
 
 
+class NodeHeadLossFunction(torch.autograd.Function):
+    """(loss, pre) of the node-level readout of filtering.py:268, :320: pre = fc2 x [N, 1] (fc2: nin <= 64 -> 1) and
+    loss = sum (mask (pre - y[:, task]))^2 as ONE launch forward and ONE backward (csrc/gml_node_head.hip).  stats (optional, float32
+    [4] on the device) receives {loss, ss_res, ss_tot, count} of the rows with mask == 1 in the same launch (models.r2_from_stats).
+    No host read either way: capturable.  pre is returned for inspection and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, y, mask, task=0, stats=None):
+        x = _f32c(x, 'x')
+        N, F = int(x.size(0)), int(x.size(1))
+        if w.numel() != F or y.dim() != 2 or y.size(0) != N or mask.numel() != N or not 0 <= task < y.size(1):
+            raise ValueError('node head: x %s, fc2 weight %s, y %s, mask %s, task %d' %
+                             (tuple(x.shape), tuple(w.shape), tuple(y.shape), tuple(mask.shape), task))
+        y, mask = _f32c(y, 'y'), _f32c(mask, 'mask')
+        if stats is not None and not (stats.is_cuda and stats.dtype == torch.float32 and stats.numel() >= 4 and stats.is_contiguous()):
+            raise ValueError('stats: a contiguous float32 CUDA tensor of 4 elements')
+        yt = y[:, task]
+        pre = torch.empty(N, 1, dtype=torch.float32, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        w = w.contiguous()
+        with torch.cuda.device(x.device):
+            with _Timed('node_head'):
+                _lib.call('gml_node_head_fwd', _ptr(x), int(x.stride(0)), _ptr(w), _ptr(b), _ptr(yt), int(y.stride(0)), _ptr(mask), 1,
+                          N, F, _ptr(pre), _ptr(loss), _ptr(stats), _stream(x.device))
+        ctx.save_for_backward(x, w, pre, y, mask)
+        ctx.task, ctx.has_b = int(task), b is not None
+        ctx.mark_non_differentiable(pre)
+        return loss, pre
+
+    @staticmethod
+    def backward(ctx, g, _gpre):
+        x, w, pre, y, mask = ctx.saved_tensors
+        N, F = int(x.size(0)), int(x.size(1))
+        dev = x.device
+        dx = torch.empty(N, F, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        db = torch.empty(1, dtype=torch.float32, device=dev) if ctx.has_b and ctx.needs_input_grad[2] else None
+        g = g.contiguous().float()
+        yt = y[:, ctx.task]
+        with torch.cuda.device(dev):
+            with _Timed('node_head'):
+                _lib.call('gml_node_head_bwd', _ptr(g), _ptr(x), int(x.stride(0)), _ptr(w), _ptr(pre), _ptr(yt), int(y.stride(0)),
+                          _ptr(mask), 1, N, F, _ptr(dx), F, _ptr(dw), _ptr(db), _stream(dev))
+        return dx, dw, db, None, None, None, None
+
+
+def node_head_supported(x, fc2):
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and 1 <= int(x.size(1)) <= 64 and int(fc2.weight.size(0)) == 1
+            and fc2.weight.dtype == torch.float32)
+
+
 def head_l1_big_supported(p, w1, w2):
     return (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and int(p.size(1)) == 32 and tuple(w1.shape) == (32, 32)
             and tuple(w2.shape) == (1, 32) and p.size(0) > 0 and not _os.environ.get('GML_NO_HEAD_BIG'))

@@ -346,10 +346,14 @@ class Batch(object):
         return self._csr[which]
 
 
-def collate(graphs):
+def collate(graphs, node_fields=()):
     """graphs: iterable of dicts with x [n,f], edge_index [2,e] and optionally edge_index2/edge_attr2/y
-    (numpy or torch).  Node ids are offset per graph; everything stays on the host."""
+    (numpy or torch).  Node ids are offset per graph; everything stays on the host.
+    node_fields: keys that hold PER-NODE float arrays [n, c] (filtering.py: ('y', 'mask')): concatenated along the rows like x
+    -- Batch.y [N, 3], Batch.mask [N, 1] -- instead of one value per graph."""
     graphs = list(graphs)
+    node_fields = tuple(node_fields)
+    nf = dict((k, []) for k in node_fields)
     xs, e1, e2, ea, bt, ys, ptr, off = [], [], [], [], [], [], [0], 0
     for g, d in enumerate(graphs):
         x = np.asarray(d['x'], dtype=np.float32)
@@ -360,7 +364,12 @@ def collate(graphs):
             e2.append(np.asarray(d['edge_index2'], dtype=np.int64) + off)
             ea.append(np.asarray(d['edge_attr2'], dtype=np.float32))
         bt.append(np.full(n, g, dtype=np.int64))
-        ys.append(d.get('y', 0))
+        ys.append(0 if 'y' in nf else d.get('y', 0))
+        for k in node_fields:
+            v = np.asarray(d[k], dtype=np.float32)
+            if v.shape[0] != n:
+                raise ValueError('node field %r has %d rows, the graph has %d nodes' % (k, v.shape[0], n))
+            nf[k].append(v.reshape(n, -1))
         off += n
         ptr.append(off)
     out = dict(x=torch.from_numpy(np.concatenate(xs)), edge_index=torch.from_numpy(np.concatenate(e1, 1)),
@@ -369,6 +378,8 @@ def collate(graphs):
     if e2:
         out['edge_index2'] = torch.from_numpy(np.concatenate(e2, 1))
         out['edge_attr2'] = torch.from_numpy(np.concatenate(ea))
+    for k in node_fields:
+        out[k] = torch.from_numpy(np.concatenate(nf[k]))
     return Batch(**out)
 
 

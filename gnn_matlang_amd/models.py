@@ -162,9 +162,21 @@ def _dropout_pass(model):
     return True
 
 
+# Road choice of a node-level GNNML3 on ONE large graph (GNNML3._dense_big): the dense road (dense_block.py on
+# csrc/gml_dense_big.hip) is taken from this mask fill E / N^2 upwards.  Measured (tools/bench_filtering.py,
+# profiles/filtering_twodgrid.json: one ML3 layer 48 -> 32 + 16 forward + backward on the 30 x 30 grid, S = 11, ms sparse / dense,
+# both roads alternating in one process):
+#     recfield 2, fill 0.0137: 0.405 / 0.633      recfield 3, fill 0.0412: 0.794 / 0.741
+#     recfield 4, fill 0.1319: 2.010 / 0.673      recfield 5, fill 0.3990: 6.609 / 0.797
+# The sparse road is faster at fill 0.0137, the dense road from 0.0412 upwards (1.07 x there, 3.0 x at 0.13, 8.3 x at the filtering
+# graph's own 0.40): the constant sits between the two.
+DENSE_BIG_MIN_FILL = 0.025
+
+
 class GNNML3(torch.nn.Module):
     """head 'mlp32': fc2(relu(fc1 x)), fc1: nin->32, fc2: 32->nclass;  'tanh10': tanh(fc1 x), fc1: nin->10;
-    'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin->hidden (hidden > 0), else log_softmax(fc2 x), fc2: .->nclass."""
+    'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin->hidden (hidden > 0), else log_softmax(fc2 x), fc2: .->nclass;
+    'node' (with pool=None; filtering.py:252-280): no pooling, one output row per NODE: fc2 x, fc2: nin->nclass, no fc1."""
 
     def __init__(self, ninp, ne, nout1, nout2, nlayers, learnedge=True, bn=False, pool='add', head='mlp32',
                  nclass=1, readout_bn=False, dense_n=0, chain=True, dropout=0.0, hidden=0, pool_bn=None):
@@ -183,6 +195,10 @@ class GNNML3(torch.nn.Module):
         # chain=False for such models (GML_NO_CHAIN=1 switches it off process-wide).
         # dense_n > 0: equal-size graphs of dense_n nodes with near-dense masks (MNIST-75) are evaluated as dense
         # blocks (dense_block.py: HIP batched support product + one tall GEMM per layer); same parameters, same values
+        if (head == 'node') != (pool is None):
+            raise ValueError("head='node' goes with pool=None (one output row per node) and no other head does")
+        if head == 'node' and (readout_bn or pool_bn is not None):
+            raise ValueError("head='node' has no pooled vector to normalise (readout_bn / pool_bn)")
         if dense_n and (learnedge or nout2):
             raise ValueError('the dense-block path covers plain SpectConv stacks (learnedge=False, nout2=0)')
         self.dense_n = int(dense_n)
@@ -209,7 +225,9 @@ class GNNML3(torch.nn.Module):
         self.pool_bn = pool_bn
         if pool_bn is not None:
             setattr(self, pool_bn, torch.nn.BatchNorm1d(nin))   # torch defaults (enzymes.py:362)
-        if head == 'mlp32':
+        if head == 'node':
+            self.fc2 = torch.nn.Linear(nin, nclass)
+        elif head == 'mlp32':
             self.fc1 = torch.nn.Linear(nin, 32)
             self.fc2 = torch.nn.Linear(32, nclass)
         elif head == 'log_softmax':
@@ -224,7 +242,43 @@ class GNNML3(torch.nn.Module):
         for i in range(1, self.nlayers):
             getattr(self, 'conv%d' % (i + 1)).chain_after(getattr(self, 'conv%d' % i) if on else None)
 
-    def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False):
+    def _dense_big(self, data):
+        """Road of this batch, from host integers only (number of graphs, N, E, learnedge): True = the large-graph dense road.
+        ONE graph of 96 < N <= 1024 nodes whose mask fill E / N^2 reaches DENSE_BIG_MIN_FILL, supports used as they are
+        (learnedge=False), layer inputs within the kernel's 64 features.  Node-level models only: every pooled model keeps the
+        sparse road it has always taken."""
+        from .dense_block import big_applies
+        if self.head != 'node' or self.dense_n or self.bn or getattr(data, 'pad_graph', False):
+            return False
+        N, E = int(data.x.size(0)), int(data.edge_index2.size(1))
+        fmax = max(int(getattr(self, 'conv%d' % (i + 1)).conv1.weight.size(1)) for i in range(self.nlayers))
+        if any(getattr(self, 'conv%d' % (i + 1)).learnedge for i in range(self.nlayers)):
+            return False
+        return big_applies(int(data.ptr.numel()) - 1, N, fmax) and E >= DENSE_BIG_MIN_FILL * N * N
+
+    def _forward_dense_big(self, data, x, drop):
+        """cat[relu(dense conv), tanh(fc11 x) * tanh(fc12 x)] per layer on the dense blocks of the one graph (cached on the batch
+        like the CSR).  The support product and its adjoint are gml_dense_big_support_mm, the projection and its gradients the
+        tall GEMM of dense_block.py; under exact_products() the fp32 library product serves."""
+        from .dense_block import dense_supports, spectconv_dense, _library
+        n = int(x.size(0))
+        sp = getattr(data, '_spT', None)
+        if sp is None or sp.n != n or (sp.blocks is not None) != bool(_library()):
+            sp = data._spT = dense_supports(data.edge_index2, data.edge_attr2, data.ptr, n)
+        for i in range(self.nlayers):
+            layer = getattr(self, 'conv%d' % (i + 1))
+            if drop:
+                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i)
+            a = spectconv_dense(x, sp, layer.conv1.weight, layer.conv1.bias, n, relu=True)
+            if layer.nout2 > 0:
+                Fn._path('dense', 'Hadamard half (library GEMMs + tanh)', '-', int(x.size(1)), layer.nout2)
+                a = torch.cat([a, torch.tanh(tall_linear(x, layer.fc11)) * torch.tanh(tall_linear(x, layer.fc12))], 1)
+            x = a
+        return x
+
+    def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False, _road=None):
+        """_road (tests and tools/bench_filtering.py): 'dense' / 'sparse' overrides the road choice of _dense_big for a batch both
+        roads cover; None: the choice."""
         x = data.x
         padded = getattr(data, 'pad_graph', False)
         if padded and self.training and (self.readout_bn or self.pool_bn is not None):
@@ -235,6 +289,13 @@ class GNNML3(torch.nn.Module):
         if self._chain and self.dropout > 0:
             self._declare_chain(not drop)
         nvalid = _node_valid(data) if padded and self.training and self.bn else None     # the bnN layers: real nodes only
+        big = self._dense_big(data) if _road is None else (_road == 'dense')
+        if self.head == 'node' and self._chain:
+            # the relu hand-over between stacked sparse layers is withdrawn on the dense road (as dense_n does at construction)
+            self._declare_chain(not big and not drop)
+        if big:
+            x = self._forward_dense_big(data, x, drop)
+            return x if _features else tall_linear(x, self.fc2)
         if self.dense_n:
             from .dense_block import dense_supports, spectconv_dense, _library
             sp = getattr(data, '_spT', None)                    # per-batch data, like the CSR
@@ -268,6 +329,8 @@ class GNNML3(torch.nn.Module):
             if self.bn:
                 bn = getattr(self, 'bn%d' % (i + 1))
                 x = bn(x) if nvalid is None else bn(x, valid=nvalid)
+        if self.head == 'node':
+            return x if _features else tall_linear(x, self.fc2)
         if not pooled:
             x = _pool(self.pool, x, data)
         if self.readout_bn:
@@ -403,6 +466,10 @@ def mnist75_gnnml1(ninp=3, dropout=0.0):   # mnist75.py:262-326 (relu, mean-pool
     return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='bn_mlp', dropout=dropout)
 
 
+def filtering_gnnml3(ninp=1, ne=11):      # filtering.py:252-280 (node-level: three layers 32 + 16, fc2: 48 -> 1, no pooling, no fc1)
+    return GNNML3(ninp, ne, 32, 16, 3, learnedge=False, pool=None, head='node', nclass=1)
+
+
 def zinc_gnnml3(ninp=25, ne=8):            # Zinc12k.py:316-329
     return GNNML3(ninp, ne, 30, 2, 4)
 
@@ -481,6 +548,35 @@ def zinc_step_loss(model, data, valid=None, loss_sum=None):
     if loss_sum is not None:
         loss_sum.add_(l.detach())
     return l
+
+
+def filtering_loss(pre, y, mask, ntask=0):   # filtering.py:320
+    return torch.square(mask * (pre - y[:, ntask:ntask + 1])).sum()
+
+
+def filtering_step_loss(model, data, ntask=0, stats=None, _road=None):
+    """filtering_loss(model(data), data.y, data.mask, ntask) -- the ``loss_fn(model, data)`` of dist.TrainStep -- with the readout
+    fc2, the masked loss and the sums of R^2 as ONE launch each way (functional.NodeHeadLossFunction).  stats: optional float32 [4]
+    on the device, receives {loss, ss_res, ss_tot, count} over the rows with mask == 1 (r2_from_stats); no host read."""
+    x = model.forward(data, _features=True, _road=_road)
+    if Fn.node_head_supported(x, model.fc2):
+        return Fn.NodeHeadLossFunction.apply(x, model.fc2.weight, model.fc2.bias, data.y, data.mask, int(ntask), stats)[0]
+    pre = tall_linear(x, model.fc2)
+    loss = filtering_loss(pre, data.y, data.mask, ntask)
+    if stats is not None:
+        with torch.no_grad():
+            m = (data.mask == 1).to(pre.dtype)
+            yt = data.y[:, ntask:ntask + 1]
+            cnt = m.sum()
+            ybar = (m * yt).sum() / cnt.clamp(min=1)
+            stats[:4].copy_(torch.stack([loss.detach(), (m * (yt - pre) ** 2).sum(), (m * (yt - ybar) ** 2).sum(), cnt]))
+    return loss
+
+
+def r2_from_stats(stats):
+    """sklearn's r2_score of filtering.py:324-327 from the four sums of filtering_step_loss: 1 - ss_res / ss_tot.  A tensor op on
+    whatever device stats lives on (no host read); numpy arrays and sequences work too."""
+    return 1 - stats[1] / stats[2]
 
 
 def counting_loss(pre, y):                 # counting.py:411

@@ -11,6 +11,7 @@ libs/utils.py:509) inside PyG ``InMemoryDataset.process`` bodies; neither PyG no
   load_tu       libs/utils.py:24-174   (ptc.mat / enzymes.mat / proteins.mat -> x, edge_index, integer class label)
   load_graph8c  libs/utils.py:453-487  (graph8c.g6 -> x = ones, undirected edge_index, y = 0)
   load_exp      libs/utils.py:424-451  (EXP's GRAPHSAT.pkl as converted by tools/convert_exp.py -> x, edge_index, y)
+  load_twodgrid libs/utils.py:333-355  (TwoDGrid30.mat -> train / test / val records of ONE grid: x, per-node y [n, 3], mask)
 
 Each returns graphs as (x [n, f] float32, edge_index [2, e] int64 in row-major ``np.where`` order, y), the input format
 of ``SpectralDesign.design_many`` / ``graph.collate``.
@@ -191,3 +192,25 @@ def load_tu(path, name):
         raise ValueError('%s: %d labels for %d graphs' % (path, Y.size, A.size))
     k = _TU_COLS[name]
     return [(np.asarray(F[i] if k is None else F[i][:, 0:k], dtype=np.float32), _edges(A[i]), np.int64(Y[i])) for i in range(A.size)]
+
+
+def load_twodgrid(path):
+    """libs/utils.py:333-355 (TwoDGrid30): the three records of TwoDGrid30.mat in the order train, test, val (filtering.py:20-22), as
+    dicts for ``SpectralDesign.design_many`` / ``graph.collate(node_fields=('y', 'mask'))``.  All three share ONE edge_index
+    (np.where(A > 0)) and ONE mask array; x = F[:, 0:1] | F[:, 4:5] | F[:, 8:9], y = F[:, 1:4] | F[:, 5:8] | F[:, 9:12] (band-,
+    low-, high-pass response per node), mask = F[:, 12:13] (1 = the node counts in the loss and in R^2).  Everything float32."""
+    a = read_mat(path)
+    F = np.asarray(a['F']).astype(np.float32)
+    if F.ndim != 2 or F.shape[1] < 13:
+        raise ValueError('%s: F must be [n, >= 13], got %s' % (path, F.shape))
+    ei = _edges(np.asarray(a['A']))
+    mask = np.ascontiguousarray(F[:, 12:13])
+    return [dict(x=np.ascontiguousarray(F[:, c:c + 1]), edge_index=ei, y=np.ascontiguousarray(F[:, c + 1:c + 4]), mask=mask)
+            for c in (0, 4, 8)]
+
+
+def design_twodgrid(records, design):
+    """records of load_twodgrid + a SpectralDesign -> the three designed records (dicts with edge_index2 / edge_attr2 / lmax added).
+    The three share one graph, so the eigen-decomposition runs once and they share the support arrays too."""
+    d = design.design_many([(records[0]['x'], records[0]['edge_index'], 0)])[0]
+    return [dict(d, x=np.asarray(r['x'], dtype=np.float32), y=r['y'], mask=r['mask']) for r in records]

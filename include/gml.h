@@ -614,6 +614,34 @@ int gml_dense_pack(const float* blocks, uint16_t* img, int64_t nblocks, int32_t 
 int gml_dense_support_mm(const uint16_t* dimg, const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo,
                          int32_t so, int32_t sum_s, int32_t B, int32_t S, int32_t n, int32_t KP, int32_t F,
                          gml_stream_t stream);
+/* The same product for ONE large graph: 96 < n <= 1024 nodes, F <= 64, any S >= 1 (the 30 x 30 grid of filtering.py: n = 900, a
+ * 40 % full mask, S = 11).  Images in the format above with nblocks = S (gml_dense_big_pack; KP = 32 ceil(n / 32)).
+ *   gml_dense_big_support_mm : out[r ldo + s so + f]  =  sum_k D[s][r][k] . act[k lda + s sa + f], summed over s into out[r ldo + f]
+ *                              when sum_s != 0.  Rows k >= n of act are never read; only the F columns named above are written.
+ * The work is cut across (support, 64-row block, K slice); with a K split or the sum over s the items write partial tiles into ws
+ * (gml_dense_big_workspace_bytes(S, n, F, sum_s) bytes, 16-byte aligned; 0 = none needed) and a second launch adds them in
+ * ascending (s, slice) order: no float atomics, bitwise the same result on every run.  bf16x3 products, fp32 accumulate.
+ * GML_E_UNSUPPORTED outside 96 < n <= 1024, 1 <= F <= 64, KP = 32 ceil(n / 32); GML_E_WORKSPACE when ws is too small. */
+size_t gml_dense_big_workspace_bytes(int32_t S, int32_t n, int32_t F, int32_t sum_s);
+int gml_dense_big_pack(const float* blocks, uint16_t* img, int64_t nblocks, int32_t n, int32_t KP, int32_t transpose,
+                       gml_stream_t stream);
+int gml_dense_big_support_mm(const uint16_t* dimg, const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo,
+                             int32_t so, int32_t sum_s, int32_t S, int32_t n, int32_t KP, int32_t F, void* ws, size_t ws_bytes,
+                             gml_stream_t stream);
+
+/* ---------------------------------------------------------------- node-level readout + masked squared loss (filtering.py:268, :320-327)
+ *   gml_node_head_fwd : pre[r] = x[r ldx ..] . w + b[0]  (F <= 64; b may be NULL), loss[0] = sum_r (mask[r ldm] (pre[r] - y[r ldy]))^2;
+ *                       stats (optional, 4 floats) = {loss, ss_res, ss_tot, count} over the rows with mask == 1: ss_res = sum (y - pre)^2,
+ *                       ss_tot = sum (y - ybar)^2 with ybar the mean of y over those rows, formed first (r2 = 1 - ss_res / ss_tot).
+ *   gml_node_head_bwd : g[0] = d / d loss (device scalar): dpre = g 2 mask^2 (pre - y); dx[r lddx + f] = dpre[r] w[f];
+ *                       dw[f] = sum_r dpre[r] x[r][f]; db[0] = sum_r dpre[r]  (dx / dw / db may each be NULL).
+ * One launch each, any N, fixed-order sums, no host read: capturable. */
+int gml_node_head_fwd(const float* x, int64_t ldx, const float* w, const float* b, const float* y, int64_t ldy, const float* mask,
+                      int64_t ldm, int64_t N, int32_t F, float* pre, float* loss, float* stats, gml_stream_t stream);
+int gml_node_head_bwd(const float* g, const float* x, int64_t ldx, const float* w, const float* pre, const float* y, int64_t ldy,
+                      const float* mask, int64_t ldm, int64_t N, int32_t F, float* dx, int64_t lddx, float* dw, float* db,
+                      gml_stream_t stream);
+
 /* The layer in ONE launch, as libs/layers_tf.py:231-236 forms it (matmul(support, x) then the projection by W_i): the support
  * product's accumulators are the projection's operand, Hcat never goes through a library GEMM.
  *   gml_dense_pack_w   : weight [S][Fin][Fout] fp32 -> bf16 (hi, lo) projection fragments (gml_dense_wimg_elems int16 elements)
