@@ -1031,6 +1031,101 @@ class HeadL1BigFunction(torch.autograd.Function):
         return gp, None, None, dw1, db1, dw2, db2, None
 
 
+def _head_bce_args(p, y, valid, w1, b1, w2, b2, stats):
+    """the tensors as gml_head_bce_* take them; raises on what head_bce_supported would have refused"""
+    p = _f32rows(p, 'pooled')
+    for t, name in ((y, 'y'), (valid, 'valid'), (w1, 'fc1.weight'), (b1, 'fc1.bias'), (w2, 'fc2.weight'), (b2, 'fc2.bias')):
+        if t is not None or name in ('y', 'fc1.weight', 'fc2.weight'):
+            _require_cuda(t, name)
+    if not head_bce_supported(p, w1, w2):
+        raise ValueError('head_bce: pooled %s %s, fc1 weight %s, fc2 weight %s (float32, 1 <= nin, nh <= 64, one output)' %
+                         (tuple(p.shape), p.dtype, tuple(w1.shape), tuple(w2.shape)))
+    nl = int(y.numel())
+    if nl > p.size(0) or (valid is not None and valid.numel() != nl):
+        raise ValueError('head_bce: %d labels, %s validity entries for %d pooled rows' %
+                         (nl, 'no' if valid is None else valid.numel(), p.size(0)))
+    if stats is not None and not (stats.is_cuda and stats.dtype == torch.float32 and stats.numel() >= 3 and stats.is_contiguous()):
+        raise ValueError('stats: a contiguous float32 CUDA tensor of 3 elements')
+    y = y.to(torch.float32).contiguous()
+    valid = valid.to(torch.float32).contiguous() if valid is not None else None
+    c = lambda t: t.contiguous() if t is not None else None
+    return p, y, valid, w1.contiguous(), c(b1), w2.contiguous(), c(b2)
+
+
+def _head_bce_ws(rows, nin, nh, dev):
+    nws = int(_lib.lib().gml_head_bce_workspace_floats(int(rows), int(nin), int(nh)))
+    return (torch.empty(nws, dtype=torch.float32, device=dev) if nws else None), nws
+
+
+class HeadBCEFunction(torch.autograd.Function):
+    """loss = sum_{r < len(y)} valid[r] BCE(fc2(act(fc1 p[r])), y[r]) on logits (exp_classify.py:293-295 / :260-262, :328-329) as
+    ONE pass forward and ONE backward for any number of rows (csrc/gml_head_bce.hip; act: 1 = relu, 0 = identity).  p [R, nin]
+    pooled rows (R >= len(y): further rows, the padding graph of a static batch, are ignored and get a zero gradient).  stats
+    (optional, float32 [3] on the device) accumulates {loss, correct predictions, rows with valid != 0} in the same launch
+    (models.accuracy_from_stats).  Saves nothing but its inputs -- the backward recomputes the forward --, no host read: capturable."""
+
+    @staticmethod
+    def forward(ctx, p, y, valid, w1, b1, w2, b2, act, stats=None):
+        p, y, valid, w1, b1, w2, b2 = _head_bce_args(p, y, valid, w1, b1, w2, b2, stats)
+        R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
+        ws, nws = _head_bce_ws(R, nin, nh, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _path('head', 'fused BCE head (%d -> %d -> 1, %s)' % (nin, nh, 'relu' if act else 'identity'))
+        with torch.cuda.device(dev):
+            with _Timed('head'):
+                _lib.call('gml_head_bce_fwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                          R, int(y.numel()), nin, nh, int(bool(act)), _ptr(loss), _ptr(None), _ptr(stats), _ptr(ws), nws, _stream(dev))
+        ctx.save_for_backward(p, y, valid, w1, b1, w2, b2)
+        ctx.act = int(bool(act))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        p, y, valid, w1, b1, w2, b2 = ctx.saved_tensors
+        R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
+        gp = torch.empty(R, nin, dtype=torch.float32, device=dev)
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        db1 = torch.empty_like(b1) if b1 is not None else None
+        db2 = torch.empty_like(b2) if b2 is not None else None
+        ws, nws = _head_bce_ws(R, nin, nh, dev)
+        g = g.contiguous().float()
+        with torch.cuda.device(dev):
+            with _Timed('head'):
+                _lib.call('gml_head_bce_bwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                          R, int(y.numel()), nin, nh, ctx.act, _ptr(g), _ptr(gp), nin, _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2),
+                          _ptr(ws), nws, _stream(dev))
+        return gp, None, None, dw1, db1, dw2, db2, None, None
+
+
+def head_bce_logits(p, y, valid, w1, b1, w2, b2, act):
+    """(loss, logits [R]) of the fused BCE head, forward only (inspection and tests; no gradient)"""
+    with torch.no_grad():
+        p, y, valid, w1, b1, w2, b2 = _head_bce_args(p, y, valid, w1, b1, w2, b2, None)
+        R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
+        ws, nws = _head_bce_ws(R, nin, nh, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        pre = torch.empty(R, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call('gml_head_bce_fwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                      R, int(y.numel()), nin, nh, int(bool(act)), _ptr(loss), _ptr(pre), _ptr(None), _ptr(ws), nws, _stream(dev))
+    return loss, pre
+
+
+def head_bce_supported(p, w1, w2):
+    """True when HeadBCEFunction serves these tensors: float32 CUDA tensors on one device, p [R >= 1, nin] with unit column stride
+    (any row stride >= nin), fc1 weight [nh, nin] and fc2 weight [1, nh] with 1 <= nin, nh <= 64.  The kernel asks no more than float
+    alignment, which every float32 tensor has.  False sends the caller to the torch-op road."""
+    ts = (p, w1, w2)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == p.device for t in ts):
+        return False
+    if p.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or p.size(0) < 1:
+        return False
+    nin, nh = int(p.size(1)), int(w1.size(0))
+    return (1 <= nin <= 64 and 1 <= nh <= 64 and int(w1.size(1)) == nin and tuple(w2.shape) == (1, nh)
+            and p.stride(1) == 1 and p.stride(0) >= nin and w1.is_contiguous() and w2.is_contiguous()
+            and not _os.environ.get('GML_NO_HEAD_BCE'))
+
+
 class NodeHeadLossFunction(torch.autograd.Function):
     """(loss, pre) of the node-level readout of filtering.py:268, :320: pre = fc2 x [N, 1] (fc2: nin <= 64 -> 1) and
     loss = sum (mask (pre - y[:, task]))^2 as ONE launch forward and ONE backward (csrc/gml_node_head.hip).  stats (optional, float32

@@ -175,6 +175,7 @@ DENSE_BIG_MIN_FILL = 0.025
 
 class GNNML3(torch.nn.Module):
     """head 'mlp32': fc2(relu(fc1 x)), fc1: nin->32, fc2: 32->nclass;  'tanh10': tanh(fc1 x), fc1: nin->10;
+    'mlp' (exp_classify.py:280-281, :294-295): fc2(relu(fc1 x)), fc1: nin->hidden (hidden > 0), fc2: hidden->nclass;
     'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin->hidden (hidden > 0), else log_softmax(fc2 x), fc2: .->nclass;
     'node' (with pool=None; filtering.py:252-280): no pooling, one output row per NODE: fc2 x, fc2: nin->nclass, no fc1."""
 
@@ -230,6 +231,11 @@ class GNNML3(torch.nn.Module):
         elif head == 'mlp32':
             self.fc1 = torch.nn.Linear(nin, 32)
             self.fc2 = torch.nn.Linear(32, nclass)
+        elif head == 'mlp':
+            if not hidden > 0:
+                raise ValueError("head='mlp' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)")
+            self.fc1 = torch.nn.Linear(nin, hidden)
+            self.fc2 = torch.nn.Linear(hidden, nclass)
         elif head == 'log_softmax':
             if hidden:
                 self.fc1 = torch.nn.Linear(nin, hidden)
@@ -348,6 +354,8 @@ class GNNML3(torch.nn.Module):
             if _capture is not None:
                 _capture['head_pre'] = z1.detach()            # (the parity checker takes the head's relu mask from here)
             return tall_linear(F.relu(z1), self.fc2)
+        if self.head == 'mlp':
+            return tall_linear(F.relu(tall_linear(x, self.fc1)), self.fc2)
         return torch.tanh(tall_linear(x, self.fc1))
 
     def features(self, data, pad_grad_zero=False):
@@ -406,7 +414,8 @@ class GNNML1(torch.nn.Module):
          concat=False:  x <- act( fc_i1(x) + conv_i1(x) + fc_i2(x) * fc_i3(x) )            (the scripts' setting)
          concat=True :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]
     with conv_i1 = SpectConv(K=1, selfconn=False) over the RAW adjacency with unit edge values, then pooling and
-    head 'lin10' (sr25 / graph8c: fc1: nin -> 10) or 'bn_mlp' (mnist75: bn1, relu(fc1: nin -> 32), log_softmax(fc2: 32 -> 10)).
+    head 'lin10' (sr25 / graph8c: fc1: nin -> 10), 'bn_mlp' (mnist75: bn1, relu(fc1: nin -> 32), log_softmax(fc2: 32 -> 10)) or
+    'lin2' (exp_classify.py:240-241, :261-262: fc2(fc1 x), fc1: nin -> 10, fc2: 10 -> nclass, NO activation in between).
     Same attribute names as the reference, so its state_dict loads.  (mutag.py's variant -- relu on the factors, BatchNorm
     per block -- is GNNML1Mutag.)"""
 
@@ -421,15 +430,18 @@ class GNNML1(torch.nn.Module):
                 setattr(self, 'fc%d%d' % (i, j), torch.nn.Linear(fin, nout))
         if head == 'lin10':
             self.fc1 = torch.nn.Linear(nin, nclass)
+        elif head == 'lin2':
+            self.fc1 = torch.nn.Linear(nin, 10)
+            self.fc2 = torch.nn.Linear(10, nclass)
         else:
             self.bn1 = torch.nn.BatchNorm1d(nin)
             self.fc1 = torch.nn.Linear(nin, 32)
             self.fc2 = torch.nn.Linear(32, nclass)
         _init_dropout(self, dropout)           # dropout > 0: F.dropout in front of every block in training (mnist75.py:299-317)
 
-    def forward(self, data):
+    def forward(self, data, _features=False):
         x = data.x
-        if self.head != 'lin10' and self.training and getattr(data, 'pad_graph', False):
+        if self.head not in ('lin10', 'lin2') and self.training and getattr(data, 'pad_graph', False):
             # bn1 normalises the pooled rows: the padding graph's row and absent slots would enter its statistics
             raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
                                       'graph and absent slots in the statistics of bn1')
@@ -448,10 +460,19 @@ class GNNML1(torch.nn.Module):
             a, c, h = g('fc%d1')(x), g('conv%d1')(x, csr, ones), g('fc%d2')(x) * g('fc%d3')(x)
             x = torch.cat([self.act(a), self.act(c), self.act(h)], 1) if self.concat else self.act(a + c + h)
         x = _pool(self.pool, x, data)
+        if _features:
+            return x
         if self.head == 'lin10':
             return tall_linear(x, self.fc1)
+        if self.head == 'lin2':
+            return tall_linear(tall_linear(x, self.fc1), self.fc2)
         x = F.relu(tall_linear(self.bn1(x), self.fc1))
         return F.log_softmax(tall_linear(x, self.fc2), dim=1)
+
+    def features(self, data, pad_grad_zero=False):
+        """the pooled graph features the head is applied to: [num_graphs, nin] (pad_grad_zero: accepted for symmetry with
+        GNNML3.features; the pool here masks the padding graph's gradient itself)."""
+        return self.forward(data, _features=True)
 
 
 def sr25_gnnml1(ninp=2):                   # sr25.py:192-246 (nout = 64, sum form, tanh, add-pool, fc1 -> 10)
@@ -488,6 +509,14 @@ def graph8c_gnnml3(ninp=2, ne=6):          # graph8c.py:252-278 (the sr25 shapes
 
 def exp_gnnml3(ninp=2, ne=6):              # exp_iso.py:249-278 (the same shapes; ne = 6 supports of SpectralDesign(nfreq=5))
     return GNNML3(ninp, ne, 32, 16, 3, head='tanh10')
+
+
+def exp_classify_gnnml3(ninp=2, ne=6):     # exp_classify.py:264-295 (three layers 32 + 16, learned supports, mean-pool, relu(fc1: 48 -> 10), fc2: 10 -> 1)
+    return GNNML3(ninp, ne, 32, 16, 3, learnedge=True, pool='mean', head='mlp', hidden=10, nclass=1)
+
+
+def exp_classify_gnnml1(ninp=2):           # exp_classify.py:209-262 (nout = 64, sum form, relu, mean-pool, fc1: 64 -> 10, fc2: 10 -> 1, no activation between)
+    return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='lin2', nclass=1)
 
 
 def mnist_gnnml3(ninp=2, ne=6, dense_n=0):  # mnist75_gnnml3_tf.py:62, libs/models_tf.py:223-268 (DSGCNN)
@@ -577,6 +606,61 @@ def r2_from_stats(stats):
     """sklearn's r2_score of filtering.py:324-327 from the four sums of filtering_step_loss: 1 - ss_res / ss_tot.  A tensor op on
     whatever device stats lives on (no host read); numpy arrays and sequences work too."""
     return 1 - stats[1] / stats[2]
+
+
+def exp_classify_loss(pre, y, valid=None):   # exp_classify.py:328-329
+    """F.binary_cross_entropy(sigmoid(pre), y.float().unsqueeze(-1), reduction='sum') -- the general road and the CPU.  valid: a
+    padded static batch's graph_valid [B] -- the sum over the real graphs of its first B rows, as mutag_loss masks them."""
+    if valid is None:
+        return F.binary_cross_entropy(torch.sigmoid(pre), y.to(pre.dtype).unsqueeze(-1), reduction='sum')
+    nl = int(valid.numel())
+    l = F.binary_cross_entropy(torch.sigmoid(pre[:nl, 0]), y[:nl].to(pre.dtype), reduction='none')
+    return (l * valid).sum()
+
+
+def _exp_head(model):
+    """(fc1, fc2, act) of a model whose readout is fc2(act(fc1 x)): GNNML3 head 'mlp' (relu), GNNML1 head 'lin2' (identity)"""
+    if isinstance(model, GNNML3) and model.head == 'mlp':
+        return model.fc1, model.fc2, 1
+    if isinstance(model, GNNML1) and model.head == 'lin2':
+        return model.fc1, model.fc2, 0
+    return None
+
+
+def exp_classify_step_loss(model, data, valid=None, stats=None):
+    """exp_classify_loss(model(data), data.y) -- the ``loss_fn(model, data)`` of dist.TrainStep -- with the head, the loss, the
+    number of correct predictions and their backward as ONE launch each way (functional.HeadBCEFunction) where the head is
+    fc2(act(fc1 x)) with one output and at most 64 units a side; otherwise the torch-op road.  Plain and padded static batches
+    (valid = data.graph_valid), training and evaluation under torch.no_grad() alike.  stats: optional float32 [3] on the device,
+    ACCUMULATES {loss, correct predictions, graphs counted} (accuracy_from_stats); no host read."""
+    from . import functional as Fn
+    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
+    nl = int(data.y.numel()) if valid is None else int(valid.numel())
+    head = _exp_head(model)
+    if head is not None and int(head[1].weight.size(0)) == 1:
+        fc1, fc2, act = head
+        x = model.features(data, pad_grad_zero=True)          # (both roads below give the padding graph's row a zero gradient)
+        if Fn.head_bce_supported(x, fc1.weight, fc2.weight) and nl <= x.size(0):
+            return Fn.HeadBCEFunction.apply(x, data.y[:nl], valid, fc1.weight, fc1.bias, fc2.weight, fc2.bias, act, stats)
+        Fn._path('head', 'torch ops (BCE head outside the fused kernel)')
+        h = tall_linear(x, fc1)
+        pre = tall_linear(F.relu(h) if act else h, fc2)
+    else:
+        Fn._path('head', 'torch ops (BCE on the model\'s own head)')
+        pre = model(data)
+    loss = exp_classify_loss(pre, data.y, valid)
+    if stats is not None:
+        with torch.no_grad():
+            v = valid if valid is not None else torch.ones(nl, dtype=pre.dtype, device=pre.device)
+            ok = ((pre[:nl, 0] > 0) == (data.y[:nl] == 1)).to(pre.dtype)
+            stats[:3].add_(torch.stack([loss.detach(), (ok * v).sum(), (v != 0).to(pre.dtype).sum()]))
+    return loss
+
+
+def accuracy_from_stats(stats):
+    """correct predictions / graphs counted from the sums of exp_classify_step_loss (exp_classify.py:334, :337).  A tensor op on
+    whatever device stats lives on (no host read); numpy arrays and sequences work too."""
+    return stats[1] / stats[2]
 
 
 def counting_loss(pre, y):                 # counting.py:411

@@ -174,6 +174,14 @@ def load_exp(path):
             for g in range(y.size)]
 
 
+def exp_classify_splits(graphs):
+    """exp_classify.py:19-21: (val, test, train) = graphs [0, 200), [200, 400), [400, 1200) of the EXP list in file order -- raw
+    graphs of load_exp or the designed ones, any sequence that slices.  Pairs stay whole: every bound is even."""
+    if len(graphs) != 1200:
+        raise ValueError('exp_classify_splits: EXP has 1,200 graphs, got %d' % len(graphs))
+    return graphs[0:200], graphs[200:400], graphs[400:1200]
+
+
 # feature columns the reference's TU dataset classes keep (contfeat=False): PtcDataset all of them, EnzymesDataset and
 # ProteinsDataset F[i][:, 0:3] (libs/utils.py:51, 101, 151)
 _TU_COLS = dict(ptc=None, enzymes=3, proteins=3)

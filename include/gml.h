@@ -768,6 +768,38 @@ int gml_head_l1_big_bwd(const float* p, int64_t ldp, const float* y, const float
                         const float* gscale, float* gp, int64_t ldgp, float* dw1, float* db1, float* dw2, float* db2,
                         void* ws, size_t ws_floats, gml_stream_t stream);
 
+/* Readout head + sum binary cross-entropy ON LOGITS + number of correct predictions of the EXP classification experiment
+ * (exp_classify.py:293-295 / :260-262 head, :328-329 loss, :334 accuracy; csrc/gml_head_bce.hip), one pass each way:
+ *   h = act(W1 p[r] + b1), z_r = w2 . h + b2                 p [rows, nin] pooled features, W1 [nh, nin]; act: 1 = relu, 0 = identity
+ *   l_r = y_r softplus(-z_r) + (1 - y_r) softplus(z_r),      softplus(t) = max(t, 0) + log1p(exp(-|t|)), each term capped at 100
+ *   loss[0] = sum_{r < rows_loss} valid[r] l_r               (valid NULL: all ones; labels y are 0 or 1)
+ *   ok      = sum_{r < rows_loss} valid[r] [(z_r > 0) == (y_r == 1)],   n = number of rows r < rows_loss with valid[r] != 0
+ * pre (optional): the logits of all `rows` rows.  stats (optional, 3 floats) is ACCUMULATED: stats += {loss, ok, n} -- an epoch's
+ * loss and accuracy (ok / n) with no launch and no host read of their own; the caller zeroes it.  The forward stands alone
+ * (evaluation).  The backward recomputes from p: dz_r = gscale[0] valid[r] (sigmoid(z_r) - y_r) for r < rows_loss, else 0 (gscale:
+ * device scalar, NULL = 1); gp [rows, nin] (ldgp >= nin; rows >= rows_loss -- the padding graph of a static batch -- and rows with
+ * valid == 0 receive exact zeros), dw1 [nh, nin], db1 [nh] (NULL allowed), dw2 [nh], db2 [1] (NULL allowed).
+ * 1 <= nin, nh <= 64, neither needs to be a multiple of 4 and no pointer needs more than float alignment; b1, b2, valid may be NULL;
+ * ldp >= nin; any rows >= 1.  GML_E_UNSUPPORTED outside these widths or for another act, GML_E_BADARG for a null or short argument.
+ * rows <= 256: one launch, no workspace (ws may be NULL).  Beyond: each workgroup writes one record  dw1 | db1 | dw2 | db2 | loss | ok | n
+ * (nh nin + 2 nh + 4 floats) to ws and a second small launch adds the records in ascending workgroup order;
+ * ws: gml_head_bce_workspace_floats(rows, nin, nh) floats (0 for rows <= 256 and for unserved shapes), else GML_E_WORKSPACE.
+ * No atomics, fixed summation orders: the same input gives the same bits.  Products are plain fp32 FMAs, exp / log1p the device
+ * library's.  No allocation, no sync, no host read: capturable.
+ * Two departures from the reference's F.binary_cross_entropy(torch.sigmoid(z), y, reduction='sum') and torch.round(sigmoid(z)):
+ *   1. for |z| above ~16.6 the reference's fp32 sigmoid rounds to 0 or 1: its loss then jumps to the clamp 100 and its gradient to 0.
+ *      Here the formula above holds throughout: the true loss up to the cap, the gradient sigmoid(z) - y.  The two agree wherever the
+ *      reference's own arithmetic is meaningful.
+ *   2. torch.round(sigmoid(z)) calls class 1 when sigmoid(z) > 0.5, which in fp32 differs from z > 0 only for 0 < z < 2.4e-7; here z > 0. */
+size_t gml_head_bce_workspace_floats(int64_t rows, int32_t nin, int32_t nh);
+int gml_head_bce_fwd(const float* p, int64_t ldp, const float* y, const float* valid, const float* w1, const float* b1,
+                     const float* w2, const float* b2, int64_t rows, int64_t rows_loss, int32_t nin, int32_t nh, int32_t act,
+                     float* loss, float* pre, float* stats, void* ws, size_t ws_floats, gml_stream_t stream);
+int gml_head_bce_bwd(const float* p, int64_t ldp, const float* y, const float* valid, const float* w1, const float* b1,
+                     const float* w2, const float* b2, int64_t rows, int64_t rows_loss, int32_t nin, int32_t nh, int32_t act,
+                     const float* gscale, float* gp, int64_t ldgp, float* dw1, float* db1, float* dw2, float* db2,
+                     void* ws, size_t ws_floats, gml_stream_t stream);
+
 /* GNNML1 block in one launch each way (csrc/gml_gnnml1.hip) -- /root/reference/sr25.py:231-240 (graph8c.py: the same class),
  * mnist75.py:296-318, mutag.py:253-262.  a = fc_i1(x), c = conv_i1(x) = (A^T x) Wc + bc (SpectConv, K = 1, selfconn = False,
  * libs/spect_conv.py:64-96 with one support), f2 = fc_i2(x), f3 = fc_i3(x):
