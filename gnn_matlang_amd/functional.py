@@ -724,7 +724,8 @@ def gnnml1_block_supported(x, Fin, n1, n2, n3, mode):
 class GNNML1BlockFunction(torch.autograd.Function):
     """One GNNML1 block (sr25.py:231-240, mnist75.py:296-318, mutag.py:253-262) as ONE launch forward and one launch + four gml_xty
     backward (csrc/gml_gnnml1.hip): a = fc_i1 x, c = conv_i1 x (SpectConv K = 1), f2 = fc_i2 x, f3 = fc_i3 x;
-    mode 0: act(a + c + f2 f3); 1: [act a | act c | act(f2 f3)]; 2: [act a | act c | act f2 . act f3]; act 0 tanh / 1 relu.
+    mode 0: act(a + c + f2 f3); 1: [act a | act c | act(f2 f3)]; 2: [act a | act c | act f2 . act f3]; 3: [act a | act c | tanh f2 . tanh f3]
+    (ptc.py:311); act 0 tanh / 1 relu.  Inputs up to 144 wide, parts up to 64 (gnnml1_block_supported); rows of any stride.
     val: per-edge values in TARGET order ([E] / [E, 1]) or None for ones (the scripts pass torch.ones); they carry no gradient here
     (the module takes the unfused road when edge_attr requires one).  Exact fp32 products."""
 

@@ -365,8 +365,8 @@ class GNNML3(torch.nn.Module):
 
 
 def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
-    """the block as one fused launch (functional.GNNML1BlockFunction) or None when the widths are outside the kernel (> 64) or the
-    conv is not the plain K = 1 form the scripts use.  Unit edge values (sr25.py:231, mutag.py:253: torch.ones)."""
+    """the block as one fused launch (functional.GNNML1BlockFunction) or None when the widths are outside the kernel (input > 144,
+    a part > 64) or the conv is not the plain K = 1 form the scripts use.  Unit edge values (sr25.py:231, mutag.py:253: torch.ones)."""
     from . import functional as Fn
     if conv.weight.size(0) != 1 or conv.selfconn or conv.depthwise:
         return None
@@ -473,6 +473,123 @@ class GNNML1(torch.nn.Module):
         """the pooled graph features the head is applied to: [num_graphs, nin] (pad_grad_zero: accepted for symmetry with
         GNNML3.features; the pool here masks the padding graph's gradient itself)."""
         return self.forward(data, _features=True)
+
+
+class GNNML1Blocks(torch.nn.Module):
+    """The GNNML1 of Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343 and
+    proteins.py:208-257 as one class: `nblocks` concatenating blocks
+         form 'product'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]              (kernel mode 1)
+         form 'factors'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]        (mode 2)
+         form 'tanh_factors':  x <- cat[ act(fc_i1 x), act(conv_i1 x), tanh(fc_i2 x) * tanh(fc_i3 x) ]      (mode 3, ptc.py:311)
+    of widths = (n1, n2, n3) (fc_i1 -> n1, conv_i1 = SpectConv(K = 1, selfconn=False) over the raw adjacency with unit edge values
+    -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (csrc/gml_gnnml1.hip, block inputs up to 144 wide) with the composition
+    as the road of any other shape.  bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn>
+    are DECLARED (the scripts declare some they never call: the reference's checkpoints load with strict=True).  dropout > 0:
+    F.dropout in front of every block in training.  pool: a name or a tuple of names (_pool).  head:
+         'mlp32'      : fc2(relu(fc1 x)), fc1: nin -> 32                       (Zinc12k.py:306-307, freqclass.py)
+         'lin2'       : fc2(fc1 x), fc1: nin -> hidden, NO activation          (counting.py:332-333)
+         'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)
+    A padded static batch hands _node_valid to the BatchNorms in training, as GNNML1Mutag does."""
+
+    _MODES = dict(product=1, factors=2, tanh_factors=3)
+
+    def __init__(self, ninp, widths, nblocks, form='product', act='relu', bn_after=(), nbn=0, pool='add', head='mlp32', hidden=0,
+                 nclass=1, dropout=0.0):
+        super().__init__()
+        n1, n2, n3 = (int(w) for w in widths)
+        if form not in self._MODES or act not in ('tanh', 'relu') or head not in ('mlp32', 'lin2', 'log_softmax'):
+            raise ValueError('form: %s; act: tanh / relu; head: mlp32 / lin2 / log_softmax' % ' / '.join(self._MODES))
+        if any(not 1 <= int(b) <= min(nblocks, nbn) for b in bn_after):
+            raise ValueError('bn_after names blocks 1 .. nblocks whose BatchNorm is declared (nbn)')
+        if head == 'lin2' and not hidden > 0:
+            raise ValueError("head='lin2' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)")
+        self.nblocks, self.form, self.act, self.pool, self.head = int(nblocks), form, act, pool, head
+        self.bn_after = frozenset(int(b) for b in bn_after)
+        nin = n1 + n2 + n3
+        for i in range(1, nbn + 1):
+            setattr(self, 'bn%d' % i, BatchNorm1d(nin))
+        for i, fin in enumerate([ninp] + [nin] * (nblocks - 1), start=1):
+            setattr(self, 'conv%d1' % i, SpectConv(fin, n2, 1, selfconn=False))
+            setattr(self, 'fc%d1' % i, torch.nn.Linear(fin, n1))
+            setattr(self, 'fc%d2' % i, torch.nn.Linear(fin, n3))
+            setattr(self, 'fc%d3' % i, torch.nn.Linear(fin, n3))
+        nin *= len(pool) if isinstance(pool, tuple) else 1
+        if head == 'mlp32':
+            hidden = 32
+        if hidden:
+            self.fc1 = torch.nn.Linear(nin, hidden)
+        self.fc2 = torch.nn.Linear(hidden or nin, nclass)
+        _init_dropout(self, dropout)
+
+    def _block(self, i, x, csr, ones):
+        g = lambda n: getattr(self, n % i)
+        mode, actid = self._MODES[self.form], 0 if self.act == 'tanh' else 1
+        y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), mode, actid)
+        if y is not None:
+            return y
+        A = torch.tanh if actid == 0 else F.relu
+        a, c, f2, f3 = g('fc%d1')(x), g('conv%d1')(x, csr, ones), g('fc%d2')(x), g('fc%d3')(x)
+        h = A(f2 * f3) if mode == 1 else (A(f2) * A(f3) if mode == 2 else torch.tanh(f2) * torch.tanh(f3))
+        return torch.cat([A(a), A(c), h], 1)
+
+    def forward(self, data, _features=False):
+        x = data.x
+        csr = _adjacency(data)
+        nvalid = _node_valid(data) if getattr(data, 'pad_graph', False) and self.training and self.bn_after else None
+        ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)
+        drop = _dropout_pass(self)
+        for i in range(1, self.nblocks + 1):
+            if drop:
+                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
+            x = self._block(i, x, csr, ones)
+            if i in self.bn_after:
+                bn = getattr(self, 'bn%d' % i)
+                x = bn(x) if nvalid is None else bn(x, valid=nvalid)
+        x = _pool(self.pool, x, data)
+        if _features:
+            return x
+        if self.head == 'lin2':
+            return tall_linear(tall_linear(x, self.fc1), self.fc2)
+        if hasattr(self, 'fc1'):
+            x = F.relu(tall_linear(x, self.fc1))
+        x = tall_linear(x, self.fc2)
+        return F.log_softmax(x, dim=1) if self.head == 'log_softmax' else x
+
+    def features(self, data, pad_grad_zero=False):
+        """the pooled graph features the head is applied to: [num_graphs, nin] (pad_grad_zero: accepted for symmetry with
+        GNNML3.features; the pool here masks the padding graph's gradient itself)."""
+        return self.forward(data, _features=True)
+
+
+def zinc_gnnml1(ninp=25):                  # Zinc12k.py:248-307 (four blocks 16 | 16 | 16, product form, relu, add-pool, relu(fc1: 48 -> 32), fc2: 32 -> 1)
+    return GNNML1Blocks(ninp, (16, 16, 16), 4, form='product', act='relu', pool='add', head='mlp32')
+
+
+def counting_gnnml1(ninp=2):               # counting.py:268-333 (five blocks 32 | 32 | 32, product form, relu, add-pool, fc2(fc1 x): 96 -> 32 -> 1, no activation)
+    return GNNML1Blocks(ninp, (32, 32, 32), 5, form='product', act='relu', pool='add', head='lin2', hidden=32)
+
+
+def freqclass_gnnml1(ninp=1, dropout=0.2):  # freqclass.py:235-300 (three blocks 32 | 32 | 32, product form, relu, dropout 0.2, mean-pool, relu(fc1: 96 -> 32), fc2: 32 -> 1)
+    return GNNML1Blocks(ninp, (32, 32, 32), 3, form='product', act='relu', pool='mean', head='mlp32', dropout=dropout)
+
+
+def ptc_gnnml1(ninp=20, dropout=0.1):
+    """ptc.py:273-321: two blocks 32 | 64 | 2 of [relu | relu | tanh . tanh], bn1 after block 1 only (bn2 .. bn4 declared, never
+    called), (add, max) pools, relu(fc1: 196 -> 100), log_softmax(fc2: 100 -> 2).  bn1 is 98 wide: beyond the masked BatchNorm
+    kernel (C <= 64), so a padded static batch in TRAINING raises BatchNorm1d's NotImplementedError; plain batches and evaluation
+    run."""
+    return GNNML1Blocks(ninp, (32, 64, 2), 2, form='tanh_factors', act='relu', bn_after=(1,), nbn=4, pool=('add', 'max'),
+                        head='log_softmax', hidden=100, nclass=2, dropout=dropout)
+
+
+def enzymes_gnnml1(ninp=4, dropout=0.1):   # enzymes.py:278-343 (four blocks 16 | 16 | 16, factor form, relu, a BatchNorm after each, (mean, max) pools, log_softmax(fc2: 96 -> 6))
+    return GNNML1Blocks(ninp, (16, 16, 16), 4, form='factors', act='relu', bn_after=(1, 2, 3, 4), nbn=4, pool=('mean', 'max'),
+                        head='log_softmax', nclass=6, dropout=dropout)
+
+
+def proteins_gnnml1(ninp=4, dropout=0.1):  # proteins.py:208-257 (two blocks 64 | 64 | 16, factor form, relu; bn1, bn2 declared, never called; (mean, max) pools, log_softmax(fc2: 288 -> 2))
+    return GNNML1Blocks(ninp, (64, 64, 16), 2, form='factors', act='relu', nbn=2, pool=('mean', 'max'), head='log_softmax',
+                        nclass=2, dropout=dropout)
 
 
 def sr25_gnnml1(ninp=2):                   # sr25.py:192-246 (nout = 64, sum form, tanh, add-pool, fc1 -> 10)
@@ -619,11 +736,14 @@ def exp_classify_loss(pre, y, valid=None):   # exp_classify.py:328-329
 
 
 def _exp_head(model):
-    """(fc1, fc2, act) of a model whose readout is fc2(act(fc1 x)): GNNML3 head 'mlp' (relu), GNNML1 head 'lin2' (identity)"""
+    """(fc1, fc2, act) of a model whose readout is fc2(act(fc1 x)): GNNML3 head 'mlp' (relu), GNNML1 head 'lin2' (identity),
+    GNNML1Blocks heads 'mlp32' (relu) / 'lin2' (identity)"""
     if isinstance(model, GNNML3) and model.head == 'mlp':
         return model.fc1, model.fc2, 1
     if isinstance(model, GNNML1) and model.head == 'lin2':
         return model.fc1, model.fc2, 0
+    if isinstance(model, GNNML1Blocks) and model.head in ('mlp32', 'lin2'):        # freqclass.py:298-300: relu(fc1: 96 -> 32), fc2
+        return model.fc1, model.fc2, 1 if model.head == 'mlp32' else 0
     return None
 
 

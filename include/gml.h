@@ -800,17 +800,18 @@ int gml_head_bce_bwd(const float* p, int64_t ldp, const float* y, const float* v
                      const float* gscale, float* gp, int64_t ldgp, float* dw1, float* db1, float* dw2, float* db2,
                      void* ws, size_t ws_floats, gml_stream_t stream);
 
-/* GNNML1 block in one launch each way (csrc/gml_gnnml1.hip) -- /root/reference/sr25.py:231-240 (graph8c.py: the same class),
+/* GNNML1 block in one launch each way (csrc/gml_gnnml1.hip, inputs wider than 64 and mode 3: csrc/gml_gnnml1_wide.hip) -- /root/reference/sr25.py:231-240 (graph8c.py: the same class),
  * mnist75.py:296-318, mutag.py:253-262.  a = fc_i1(x), c = conv_i1(x) = (A^T x) Wc + bc (SpectConv, K = 1, selfconn = False,
  * libs/spect_conv.py:64-96 with one support), f2 = fc_i2(x), f3 = fc_i3(x):
  *   mode 0: out [N, n] = act(a + c + f2 * f3)   (n1 = n2 = n3 = n)        mode 1: out [N, n1 + n2 + n3] = [act(a) | act(c) | act(f2 * f3)]
  *   mode 2: out = [act(a) | act(c) | act(f2) * act(f3)]  (mutag.py)       act: 0 = tanh, 1 = relu
+ *   mode 3: out = [act(a) | act(c) | tanh(f2) * tanh(f3)]  (ptc.py:311: the factors always tanh, act on the first two parts)
  * w1, w2, w3: Linear weights [n, Fin] row-major, b*: [n] or NULL; wc: the SpectConv weight [Fin, n2]; val: one value per edge in the
- * order of `col` (NULL: ones, the scripts' torch.ones edge_attr).  Exact fp32 products.  Fin, n1, n2, n3 <= 64 (gml_gnnml1_supported),
+ * order of `col` (NULL: ones, the scripts' torch.ones edge_attr).  Exact fp32 products.  Fin <= 144, n1, n2, n3 <= 64 (gml_gnnml1_supported),
  * else GML_E_UNSUPPORTED and the caller composes the block from gml_spectconv_fwd and library Linears.
  * Backward (source-keyed view rowptr_t / col_t / val_t; `out` = the saved forward output, gout = dL/dout):
  *   dx (optional) = da W1 + df2 W2 + df3 W3 + (A dc) Wc^T                    da, dc, df2, df3 = gradients at a, c, f2, f3
- *   g4 [N, ldg4 >= gml_gnnml1_g4_cols()] = [da | dc (modes 1, 2 only: dc = da in mode 0) | df2 | df3], each block 16 ceil(n / 16) columns wide
+ *   g4 [N, ldg4 >= gml_gnnml1_g4_cols()] = [da | dc (modes 1 .. 3 only: dc = da in mode 0) | df2 | df3], each block 16 ceil(n / 16) columns wide
  *   q  [N, ldq >= 16 ceil(n2 / 16)]      = A dc
  * from which the caller forms dW1 = da^T x, dW2 = df2^T x, dW3 = df3^T x, dWc = x^T q (gml_xty) and the bias gradients (column sums). */
 int gml_gnnml1_supported(int32_t Fin, int32_t n1, int32_t n2, int32_t n3, int32_t mode);
