@@ -182,7 +182,7 @@ class BatchEdgesDesc(ctypes.Structure):
 
 
 GML_OK, GML_E_BADARG, GML_E_UNSUPPORTED, GML_E_WORKSPACE = 0, -1, -2, -3
-GML_RELU, GML_ACCUM, GML_F32_MFMA, GML_GROUPS128, GML_GROUPS64R, GML_DMA_RING, GML_FWD_CHUNKED, GML_DVAL_ACCUM = 1, 2, 4, 8, 16, 32, 64, 128
+GML_RELU, GML_ACCUM, GML_F32_MFMA, GML_GROUPS128, GML_DMA_RING, GML_FWD_CHUNKED, GML_DVAL_ACCUM = 1, 2, 4, 8, 32, 64, 128     # (16: unused)
 GML_POOL_SKIP_LAST = 2
 GML_FWD_ONEWIN = 256
 GML_F16X3 = 1024                # gml_spectconv_fwd / gml_ml3_fwd, ring kernel: f16 (hi, lo) pieces under power-of-two scales
@@ -199,7 +199,6 @@ GML_ADAM_MAX_JOBS = 64
 class FoldJob(ctypes.Structure):
     """gml_fold_job of include/gml.h"""
     _fields_ = [('partial', _p), ('nparts', _i64), ('n', _i64), ('dst', _p * 5), ('ndst', _i64 * 5)]
-GML_GROUPS64_RANKED = 1064      # group kind of gml_csr_group_info: 64-row groups with rank bytes
 
 _lib = None
 

@@ -1,5 +1,3 @@
 // explicit instantiations of the fused forward kernel families (SC supports x FPL features/lane)
 #include "gml_spectconv_impl.h"
-GML_DEFINE_FWD_FAMILY(1, 8)
-GML_DEFINE_FWD_FAMILY(2, 8)
-GML_DEFINE_FWD_FAMILY(3, 8)
+GML_FWD_FAMILY_SHAPES_A(GML_DEFINE_FWD_FAMILY)

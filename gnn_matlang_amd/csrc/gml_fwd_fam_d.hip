@@ -1,5 +1,3 @@
 // explicit instantiations of the fused forward kernel families (SC supports x FPL features/lane)
 #include "gml_spectconv_impl.h"
-GML_DEFINE_FWD_FAMILY(2, 4)
-GML_DEFINE_FWD_FAMILY(3, 4)
-GML_DEFINE_FWD_FAMILY(4, 4)
+GML_FWD_FAMILY_SHAPES_D(GML_DEFINE_FWD_FAMILY)

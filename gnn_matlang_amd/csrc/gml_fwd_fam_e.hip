@@ -1,4 +1,3 @@
 // explicit instantiations of the fused forward kernel families (SC supports x FPL features/lane)
 #include "gml_spectconv_impl.h"
-GML_DEFINE_FWD_FAMILY(6, 4)
-GML_DEFINE_FWD_FAMILY(8, 4)
+GML_FWD_FAMILY_SHAPES_E(GML_DEFINE_FWD_FAMILY)

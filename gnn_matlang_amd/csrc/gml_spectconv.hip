@@ -1,4 +1,15 @@
 // Dispatch of the fused forward kernel families + the unfused SpMM / SDDMM kernels.
+//
+// Which kernel serves a conv forward is decided in plan_fwd / fwd_kernel below and nowhere else:
+//   64-row family (gml_spectconv_impl.h): any shape, exact fp32 or bf16x3, 64-row records -- all that the 128-row kernels do not take.
+//   fwd3 (gml_spectconv_fwd3_impl.h): S in {4, 8}, Fin, Fout <= 32, the ZINC-class default.  An LDS-DMA landing ring, hence its three
+//       conditions: float4-addressable x rows, no accumulate mode, 32-bit byte offsets into x.  Has the ConCat / depthwise epilogues
+//       and the fused Hadamard branch; groups beyond its staging gather from global memory.
+//   fwd2 (gml_spectconv_fwd2_impl.h): S in {4, 8, 12}, Fin, Fout <= 32, register-staged.  S = 12 (counting.py) always; S in {4, 8} when
+//       a call misses one of fwd3's conditions.  NOB = 0 is the stand-alone SpMM.
+//   fwd4 (gml_spectconv_fwd4_impl.h): the ring kernel walking a group in edge chunks.  The only 128-row kernel for 6 supports and for
+//       33 .. 48 input features (sr25.py, mutag.py); serves fwd3's shapes when the caller sets GML_FWD_CHUNKED.  fwd3's conditions, no
+//       Hadamard branch, and a bound on the column window (gml_spectconv_fwd_stage_window): it has no global-gather road.
 #include "gml_spectconv_impl.h"
 #include "gml_spectconv_fwd2_impl.h"
 #include "gml_spectconv_fwd3_impl.h"
@@ -6,175 +17,153 @@
 #include "gml_spmm3_impl.h"
 
 #define GML_DECL_FWD2(S, B) template <> int gml_launch_fwd2<S, B>(const GmlFwdParams&, dim3, hipStream_t, bool, bool);
-GML_DECL_FWD2(8, 2) GML_DECL_FWD2(8, 1) GML_DECL_FWD2(4, 2) GML_DECL_FWD2(4, 1)
-GML_DECL_FWD2(8, 0) GML_DECL_FWD2(4, 0)            /* NOB = 0: the stand-alone SpMM instantiation */
-GML_DECL_FWD2(12, 2) GML_DECL_FWD2(12, 1) GML_DECL_FWD2(12, 0)  /* counting.py's 12 supports */
-
+#define GML_DECL_SPMM2(S) GML_DECL_FWD2(S, 0)
 #define GML_DECL_FWD3(S, B) template <> int gml_launch_fwd3<S, B>(const GmlFwdParams&, dim3, hipStream_t, bool);
-GML_DECL_FWD3(8, 2) GML_DECL_FWD3(8, 1) GML_DECL_FWD3(4, 2) GML_DECL_FWD3(4, 1)
-
-#if GML_F4DBG & (8 | 64)
-static unsigned long long* f4dbg_buf() {
-    static unsigned long long* b = [] { unsigned long long* q = nullptr; (void)hipMalloc(&q, 64); (void)hipMemset(q, 0, 64); return q; }();
-    return b;
-}
-extern "C" int gml_debug_f4_counts(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpy(out, f4dbg_buf(), 64, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && reset) e = hipMemset(f4dbg_buf(), 0, 64);
-    return (int)e;
-}
-#endif
 #define GML_DECL_FWD4(S, FB, B) template <> int gml_launch_fwd4<S, FB, B>(const GmlFwdParams&, dim3, hipStream_t);
-GML_DECL_FWD4(4, 0, 2) GML_DECL_FWD4(4, 1, 2) GML_DECL_FWD4(6, 0, 2) GML_DECL_FWD4(6, 1, 2) GML_DECL_FWD4(8, 0, 2)
+#define GML_DECL_FAM(SC, FPL) template <> int gml_launch_fwd_family<SC, FPL>(const GmlFwdParams&, int, bool, bool, dim3, size_t, hipStream_t);
+GML_FWD2_SHAPES(GML_DECL_FWD2)
+GML_SPMM2_SHAPES(GML_DECL_SPMM2)
+GML_FWD3_SHAPES(GML_DECL_FWD3)
+GML_FWD4_SHAPES(GML_DECL_FWD4)
+GML_FWD_FAMILY_SHAPES(GML_DECL_FAM)
 
-// GML_FWD_DMA=0: the register-staged 8-wave kernel (fwd2) instead of the LDS-DMA ring (fwd3), for A/B runs
-static bool fwd3_env() { static const bool v = [] { const char* e = getenv("GML_FWD_DMA"); return !(e && e[0] == '0'); }(); return v; }
-
-// shapes only the chunked ring kernel (fwd4) serves on 128-row records: 6 supports (sr25.py) and / or 33 .. 48 input features
-// (the hidden layers of sr25.py:252-262 and mutag.py:272-288); x must be float4-addressable there
-static bool fwd4_only_shape(int S, int Fin, int Fout, uint32_t flags) {
-    static const bool off = [] { const char* e = getenv("GML_FWD4"); return e && e[0] == '0'; }();   // A/B: the r03 roads
-    if (off || (flags & GML_F32_MFMA) || Fout > 32) return false;
-    return (S == 6 && Fin <= 48) || (S == 4 && Fin > 32 && Fin <= 48);     /* (8 supports x 48 features: no script has it; its instantiation spilled) */
-}
-// GML_FWD4=1: every shape of the ring kernels on the chunked one (A/B against fwd3)
-static bool fwd4_all_env() { static const bool v = [] { const char* e = getenv("GML_FWD4"); return e && e[0] == '1'; }(); return v; }
-
-static bool fwd2_shape(int S, int Fin, int Fout, uint32_t flags) {
-#ifdef GML_NO_FWD2
-    return false;
-#endif
-    // S % 4 == 0: the register-staged value rows are float4 (other S keep the 64-row kernel, which stages any S)
-    return ((flags & GML_F32_MFMA) == 0 && (S == 4 || S == 8 || S == 12) && Fin <= 32 && Fout <= 32) || fwd4_only_shape(S, Fin, Fout, flags);
-}
-
-// GML_FWD_NW=4: the 8-wave kernel family in its 4-wave / 64-row geometry (two workgroups per CU)
-static int fwd2_nw_env() { static const int v = [] { const char* e = getenv("GML_FWD_NW"); return e ? atoi(e) : 8; }(); return v == 4 ? 4 : 8; }
-extern "C" int32_t gml_spectconv_fwd_group_rows(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
-    if (!fwd2_shape(S, Fin, Fout, flags)) return 64;
-    return fwd2_nw_env() == 4 ? GML_GROUPS64_RANKED : 128;
-}
-
-// edges of one 128-row group the ring kernel of this shape keeps in LDS at once (one work item); 0: the shape is on no ring kernel.
-// Larger groups: fwd3 shapes gather them from global memory, or -- GML_FWD_CHUNKED -- run on the chunked ring kernel; the shapes only
-// the chunked kernel serves walk them in edge chunks (functional.FWD_CHUNKS: on by default since the fix of DESIGN s4.1c).
-extern "C" int32_t gml_spectconv_fwd_stage_edges(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
-    if (!fwd2_shape(S, Fin, Fout, flags)) return 0;
-    if (fwd4_only_shape(S, Fin, Fout, flags)) {                /* one work item of the chunked ring kernel (its gathering form: the smaller one) */
-        const int fb = Fin > 32 ? 1 : 0;
-        if (S == 6) return (fb ? GmlFwd4Cfg<6, 1, true>::ECAP : GmlFwd4Cfg<6, 0, true>::ECAP) - 3;
-        return GmlFwd4Cfg<4, 1, true>::ECAP - 3;
-    }
-    if (!fwd3_env()) return 0;
-    return S == 8 ? GmlFwd3Cfg<8>::ECAP - 3 : (S == 4 ? GmlFwd3Cfg<4>::ECAP - 3 : 0);
-}
-
-// widest column window (int 3 of a 128-row group record) the chunked ring kernel serves for this shape; 0 = no bound (the shape's
-// kernel has its own road for wider groups).  Batches with a wider group must stay on the 64-row family (group_rows 64): the chunked
-// kernel has no global-gather road and marks the rows of such a group NaN.
-extern "C" int32_t gml_spectconv_fwd_stage_window(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
-    if (!fwd2_shape(S, Fin, Fout, flags)) return 0;
-    if (!(fwd4_only_shape(S, Fin, Fout, flags) || (flags & GML_FWD_CHUNKED) || fwd4_all_env())) return 0;
-    return Fin > 32 ? GmlFwd4Cfg<4, 1, false>::XCAP - 15 : GmlFwd4Cfg<4, 0, false>::XCAP - 7;
-}
-
-// ---- families defined in gml_fwd_fam_*.hip ---------------------------------------------------
-#define GML_DECL_FAM(SC, FPL) \
-    template <> int gml_launch_fwd_family<SC, FPL>(const GmlFwdParams&, int, bool, bool, dim3, size_t, hipStream_t);
-GML_DECL_FAM(1, 8) GML_DECL_FAM(2, 8) GML_DECL_FAM(3, 8) GML_DECL_FAM(4, 8) GML_DECL_FAM(6, 8) GML_DECL_FAM(8, 8)
-GML_DECL_FAM(1, 4) GML_DECL_FAM(2, 4) GML_DECL_FAM(3, 4) GML_DECL_FAM(4, 4) GML_DECL_FAM(6, 4) GML_DECL_FAM(8, 4)
-GML_DECL_FAM(12, 4) GML_DECL_FAM(16, 4)
-
-static int launch_family(int SC, int FPL, const GmlFwdParams& p, int NB, bool xvec, bool bf, dim3 grid, size_t lds,
-                         hipStream_t st) {
-#define GML_FAM(SCV, FPLV) \
-    if (SC == SCV && FPL == FPLV) return gml_launch_fwd_family<SCV, FPLV>(p, NB, xvec, bf, grid, lds, st);
-    GML_FAM(1, 8) GML_FAM(2, 8) GML_FAM(3, 8) GML_FAM(4, 8) GML_FAM(6, 8) GML_FAM(8, 8)
-    GML_FAM(1, 4) GML_FAM(2, 4) GML_FAM(3, 4) GML_FAM(4, 4) GML_FAM(6, 4) GML_FAM(8, 4)
-    GML_FAM(12, 4) GML_FAM(16, 4)
-    return GML_E_UNSUPPORTED;
-}
-
-static const int kSC8[] = {8, 6, 4, 3, 2, 1};
-static const int kSC4[] = {16, 12, 8, 6, 4, 3, 2, 1};
-
-extern "C" int gml_node_mix_fwd(const float* x, int64_t ldx, const float* w11, const float* b11, const float* w12,
-                                const float* b12, float* out, int64_t ldo, int64_t num_rows, int32_t Fin,
-                                int32_t F2, gml_stream_t stream);
-
-#ifdef GML_FWD2_TIMING
-static unsigned long long* fwd2_prof_buf() {
+#if defined(GML_FWD2_TIMING) || (GML_F4DBG & (8 | 64))
+/* GmlFwdParams::prof of the measuring builds: 256 bytes of counters.  -DGML_FWD2_TIMING: [0,16) fwd2, [16,32) fwd3 phase cycles */
+static unsigned long long* prof_buf() {
     static unsigned long long* b = [] { unsigned long long* q = nullptr; (void)hipMalloc(&q, 256); (void)hipMemset(q, 0, 256); return q; }();
     return b;
 }
-extern "C" int gml_debug_fwd2_prof(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpy(out, fwd2_prof_buf(), 256, hipMemcpyDeviceToHost);   /* [0,16): fwd2, [16,32): fwd3 */
-    if (e == hipSuccess && reset) e = hipMemset(fwd2_prof_buf(), 0, 256);
+static int prof_read(unsigned long long* out, size_t bytes, int reset) {
+    hipError_t e = hipMemcpy(out, prof_buf(), bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && reset) e = hipMemset(prof_buf(), 0, bytes);
     return (int)e;
 }
+#ifdef GML_FWD2_TIMING
+extern "C" int gml_debug_fwd2_prof(unsigned long long* out, int reset) { return prof_read(out, 256, reset); }
+#else
+extern "C" int gml_debug_f4_counts(unsigned long long* out, int reset) { return prof_read(out, 64, reset); }
+#endif
 #endif
 
-// conv (+ optionally the Hadamard branch of the same rows) on the 8-wave kernel; 128-row group records
+enum FwdKernel { FWD_FAMILY64, FWD2, FWD3, FWD4, FWD_UNSUPPORTED };
+
+/* the shape class of a conv forward: a function of (S, Fin, Fout, flags) alone */
+struct FwdPlan {
+    int rows;            /* group records the shape's kernels read: 128 (fwd2 / fwd3 / fwd4) or 64 (the 64-row family) */
+    bool staged;         /* fwd2 is compiled for it; with S in {4, 8} (ring) fwd3 is too */
+    bool ring;
+    bool chunked_only;   /* 6 supports and / or 33 .. 48 input features: only fwd4 serves it on 128-row records */
+    bool chunked;        /* fwd4 is asked for: chunked_only, or the caller set GML_FWD_CHUNKED */
+    int fb, nob;         /* fwd4's feature blocks beyond 32 (0 / 1); 16-wide output blocks (1 / 2) */
+};
+
+static FwdPlan plan_fwd(int S, int Fin, int Fout, uint32_t flags) {
+    FwdPlan pl = {};
+    const bool bf = (flags & GML_F32_MFMA) == 0 && Fout <= 32;
+    /* S % 4 == 0: fwd2's register-staged value rows are float4 (other S keep the 64-row kernel, which stages any S) */
+    pl.staged = bf && (S == 4 || S == 8 || S == 12) && Fin <= 32;
+    pl.ring = pl.staged && S != 12;
+    pl.chunked_only = bf && ((S == 6 && Fin <= 48) || (S == 4 && Fin > 32 && Fin <= 48));
+    pl.rows = (pl.staged || pl.chunked_only) ? 128 : 64;
+    pl.chunked = pl.chunked_only || (pl.rows == 128 && (flags & GML_FWD_CHUNKED));
+    pl.fb = Fin > 32 ? 1 : 0;
+    pl.nob = Fout > 16 ? 2 : 1;
+    return pl;
+}
+
+static bool x_float4(const float* x, int64_t ldx) { return (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0); }
+
+/* the kernel that serves ONE call on 128-row records: what only a launch knows added to the plan.  mix: the Hadamard branch rides
+   along (gml_ml3_fwd); epilogue: gml_spectconv_fwd_epi (fwd3 has the only epilogues). */
+static FwdKernel fwd_kernel(const FwdPlan& pl, int S, const float* x, int64_t ldx, int64_t num_rows, uint32_t flags, bool mix, bool epilogue) {
+    if (pl.rows != 128) return FWD_FAMILY64;
+    /* the ring kernels: LDS-DMA of float4-addressable x rows, no accumulate mode, 32-bit buffer offsets
+       (value rows beyond 4 GB are handled inside the kernels: they read the edge count themselves) */
+    const bool ring_ok = x_float4(x, ldx) && !(flags & GML_ACCUM) && (num_rows + 16) * ldx * 4 < (int64_t)INT32_MAX;
+    if (pl.chunked && !epilogue) {
+        bool have4 = false;
+#define GML_FWD4_HAVE(SV, FBV, B) have4 = have4 || (S == SV && pl.fb == FBV);
+        GML_FWD4_SHAPES(GML_FWD4_HAVE)
+        if (have4 && ring_ok && !mix) return FWD4;
+        if (pl.chunked_only) return FWD_UNSUPPORTED;         /* (unaligned x rows, accumulate mode: the caller takes the 64-row family) */
+    }
+    if (pl.ring && ring_ok) return FWD3;
+    return (pl.staged && !epilogue) ? FWD2 : FWD_UNSUPPORTED;
+}
+
+extern "C" int32_t gml_spectconv_fwd_group_rows(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) { return plan_fwd(S, Fin, Fout, flags).rows; }
+
+// edges of one 128-row group the ring kernel of this shape keeps in LDS at once (one work item); 0: the shape is on no ring kernel
+extern "C" int32_t gml_spectconv_fwd_stage_edges(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
+    const FwdPlan pl = plan_fwd(S, Fin, Fout, flags);
+    /* one work item of the chunked ring kernel (its gathering form: the smaller one) */
+#define GML_FWD4_ECAP(SV, FBV, B) if (pl.chunked_only && S == SV && pl.fb == FBV) return GmlFwd4Cfg<SV, FBV, true>::ECAP - 3;
+    GML_FWD4_SHAPES(GML_FWD4_ECAP)
+#define GML_FWD3_ECAP(SV, B) if (pl.ring && S == SV) return GmlFwd3Cfg<SV>::ECAP - 3;
+    GML_FWD3_SHAPES(GML_FWD3_ECAP)
+    return 0;
+}
+
+// widest column window (int 3 of a 128-row group record) the chunked ring kernel serves; 0 = no bound (fwd4 is not asked for).
+// Non-zero without GML_FWD_CHUNKED exactly for the shapes only the chunked kernel serves (functional.fwd_groups relies on it).
+extern "C" int32_t gml_spectconv_fwd_stage_window(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
+    const FwdPlan pl = plan_fwd(S, Fin, Fout, flags);
+    if (!pl.chunked) return 0;
+    return pl.fb ? GmlFwd4Cfg<4, 1, false>::XCAP - 15 : GmlFwd4Cfg<4, 0, false>::XCAP - 7;
+}
+
+/* persistent workgroups, each a contiguous range of groups: at most `wgs` of them; returns the grid */
+static int persistent_grid(int ngroups, int wgs, int32_t* groups_per_wg) {
+    const int grid = ngroups < wgs ? ngroups : wgs;
+    *groups_per_wg = (int)gml_cdiv(ngroups, grid);
+    return (int)gml_cdiv(ngroups, *groups_per_wg);
+}
+
+/* the fields every forward launch fills the same way: graph, x, weights, output, shape, one pass over all supports */
+static GmlFwdParams fwd_params(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo, const int32_t* epos, const float* val,
+                               const float* x, int64_t ldx, const float* w, int64_t w_ss, int64_t w_si, int64_t w_so, const float* bias,
+                               float* out, int64_t ldo, int64_t num_rows, int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
+    GmlFwdParams p = {};
+    p.rowptr = rowptr; p.col = col; p.ginfo = ginfo; p.epos = epos; p.val = val; p.x = x; p.ldx = ldx;
+    p.w = w; p.w_ss = w_ss; p.w_si = w_si; p.w_so = w_so; p.bias = bias; p.out = out; p.ldo = ldo;
+    p.nrows = num_rows; p.S = S; p.Fin = Fin; p.Fout = Fout; p.flags = flags; p.npass = 1; p.nchunks = 1; p.val_vec = 1;
+    return p;
+}
+
+/* one launch of the 128-row kernel `k` (one 8-wave workgroup per CU) */
+static int launch128(FwdKernel k, const FwdPlan& pl, GmlFwdParams& p, bool mix, hipStream_t st) {
+    const int S = p.S;
+    const bool xv = x_float4(p.x, p.ldx);
+    p.ngroups = (int)gml_cdiv(p.nrows, 128);
+    const dim3 grid(persistent_grid(p.ngroups, GML_NUM_CU, &p.groups_per_wg));
+#define GML_FWD4_GO(SV, FBV, B) if (k == FWD4 && S == SV && pl.fb == FBV) return gml_launch_fwd4<SV, FBV, B>(p, grid, st);
+    GML_FWD4_SHAPES(GML_FWD4_GO)
+#define GML_FWD3_GO(SV, B) if (k == FWD3 && S == SV && pl.nob == B) return gml_launch_fwd3<SV, B>(p, grid, st, mix);
+    GML_FWD3_SHAPES(GML_FWD3_GO)
+#define GML_FWD2_GO(SV, B) if (k == FWD2 && S == SV && pl.nob == B) return gml_launch_fwd2<SV, B>(p, grid, st, xv, mix);
+    GML_FWD2_SHAPES(GML_FWD2_GO)
+    return GML_E_UNSUPPORTED;
+}
+
+// conv (+ optionally the Hadamard branch of the same rows, F2 > 0) on 128-row group records
 static int launch_fwd2(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo, const int32_t* epos, const float* val, const float* x,
                        int64_t ldx, const float* w, int64_t w_ss, int64_t w_si, int64_t w_so, const float* bias,
                        const float* w11, const float* b11, const float* w12, const float* b12, float* out, int64_t ldo,
                        int64_t num_rows, int32_t S, int32_t Fin, int32_t Fout, int32_t F2, uint32_t flags, hipStream_t st) {
-    const bool xv = (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    GmlFwdParams p = {};
-    p.rowptr = rowptr; p.col = col; p.ginfo = ginfo; p.epos = epos; p.val = val; p.x = x; p.ldx = ldx;
-    p.w = w; p.w_ss = w_ss; p.w_si = w_si; p.w_so = w_so; p.bias = bias; p.out = out; p.ldo = ldo;
-    p.nrows = num_rows; p.S = S; p.Fin = Fin; p.Fout = Fout; p.flags = flags; p.s0 = 0; p.npass = 1; p.nchunks = 1;
-    p.val_vec = 1;
+    const FwdPlan pl = plan_fwd(S, Fin, Fout, flags);
+    GmlFwdParams p = fwd_params(rowptr, col, ginfo, epos, val, x, ldx, w, w_ss, w_si, w_so, bias, out, ldo, num_rows, S, Fin, Fout, flags);
     p.w11 = w11; p.b11 = b11; p.w12 = w12; p.b12 = b12; p.F2 = F2; p.mix_col = Fout;
-#ifdef GML_FWD2_TIMING
-    p.prof = fwd2_prof_buf();
-#endif
-#if GML_F4DBG & (8 | 64)
-    p.prof = f4dbg_buf();
+#if defined(GML_FWD2_TIMING) || (GML_F4DBG & (8 | 64))
+    p.prof = prof_buf();
 #endif
 #if GML_F4DBG & 256
     { const char* e = getenv("GML_F4_HOUT"); p.hout = e ? (float*)(uintptr_t)strtoull(e, nullptr, 0) : nullptr; }
 #endif
-    p.nw = (flags & GML_GROUPS64R) ? 4 : 8;
-    if (p.nw == 4 && !xv) return GML_E_UNSUPPORTED;
-    const int wgs = p.nw == 4 ? 2 * GML_NUM_CU : GML_NUM_CU;         // one 512-thread or two 256-thread workgroups per CU
-    p.ngroups = (int)gml_cdiv(num_rows, 16 * p.nw);
-    int grid = p.ngroups < wgs ? p.ngroups : wgs;
-    p.groups_per_wg = (int)gml_cdiv(p.ngroups, grid);
-    grid = (int)gml_cdiv(p.ngroups, p.groups_per_wg);
-    const int nob = Fout > 16 ? 2 : 1;
-    const bool mix = F2 > 0;
-    // chunked ring kernel (fwd4): the shapes only it serves, groups with more edges than fwd3 stages (GML_FWD_CHUNKED: the caller
-    // knows the largest group), or everything (GML_FWD4=1)
-    const bool only4 = fwd4_only_shape(S, Fin, Fout, flags);
-    if (only4 || ((flags & GML_FWD_CHUNKED) || fwd4_all_env())) {
-        const bool ok4 = p.nw == 8 && xv && !mix && !(flags & GML_ACCUM) && (num_rows + 16) * ldx * 4 < (int64_t)INT32_MAX &&
-                         (S == 4 || S == 6 || S == 8) && Fin <= 48 && !(S == 8 && Fin > 32);
-        if (ok4) {
-            const int fb = Fin > 32 ? 1 : 0;
-#define GML_FWD4_GO(SV, FBV) if (S == SV && fb == FBV) return gml_launch_fwd4<SV, FBV, 2>(p, dim3(grid), st);
-            GML_FWD4_GO(4, 0) GML_FWD4_GO(4, 1) GML_FWD4_GO(6, 0) GML_FWD4_GO(6, 1) GML_FWD4_GO(8, 0)
-        }
-        if (only4) return GML_E_UNSUPPORTED;             /* (unaligned x rows, accumulate mode: the caller takes the 64-row family) */
-    }
-    // LDS-DMA landing ring: float4-addressable x, no accumulate mode, 32-bit buffer offsets
-    // (value rows beyond 4 GB are handled inside the kernel: it reads the edge count itself)
-    if (p.nw == 8 && xv && fwd3_env() && (S == 8 || S == 4) && !(flags & GML_ACCUM) &&
-        (num_rows + 16) * ldx * 4 < (int64_t)INT32_MAX) {
-#define GML_FWD3_GO(SV, B) if (S == SV && nob == B) return gml_launch_fwd3<SV, B>(p, dim3(grid), st, mix);
-        GML_FWD3_GO(8, 2) GML_FWD3_GO(8, 1) GML_FWD3_GO(4, 2) GML_FWD3_GO(4, 1)
-    }
-#define GML_FWD2_GO(SV, B) if (S == SV && nob == B) return gml_launch_fwd2<SV, B>(p, dim3(grid), st, xv, mix);
-    GML_FWD2_GO(8, 2) GML_FWD2_GO(8, 1) GML_FWD2_GO(4, 2) GML_FWD2_GO(4, 1) GML_FWD2_GO(12, 2) GML_FWD2_GO(12, 1)
-    return GML_E_UNSUPPORTED;
+    return launch128(fwd_kernel(pl, S, x, ldx, num_rows, flags, F2 > 0, false), pl, p, F2 > 0, st);
 }
 
-// SpectConCatConv / depthwise SpectConv forward on the ring kernel's epilogues (see GmlFwdParams::epl).  epilogue = 1: out has
-// (S + self_term) column blocks of Fout, support s writes block s + self_term (+ bias of that block; block 0 of a selfconn layer,
-// x W_last, is the caller's GEMM); epilogue = 2: w is ONE [Fin, Fout] matrix (w_ss ignored), ds [S + self_term, Fin] the
-// per-feature scales (row 0 = 1 + DSweight[0]; last row = the self term's scale when self_term): out = (sum_s ds_s . H_s +
-// ds_self . x) W + bias.  GML_E_UNSUPPORTED outside the kernel's shape class (S in {4, 8}, Fin, Fout <= 32, float4-addressable
-// x): the caller then uses the weight-transform mapping onto gml_spectconv_fwd.
+// SpectConCatConv (epilogue 1) / depthwise SpectConv (2) forward on fwd3's epilogues (gml.h; GmlFwdParams::epl).  GML_E_UNSUPPORTED
+// wherever fwd3 does not serve the call: the caller then uses the weight-transform mapping onto gml_spectconv_fwd.
 extern "C" int gml_spectconv_fwd_epi(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo128, const float* val,
                                      const float* x, int64_t ldx, const float* w, int64_t w_ss, int64_t w_si, int64_t w_so,
                                      const float* bias, float* out, int64_t ldo, int64_t num_rows, int32_t S, int32_t Fin,
@@ -186,25 +175,21 @@ extern "C" int gml_spectconv_fwd_epi(const int32_t* rowptr, const int32_t* col, 
     if (ldo < (epilogue == 1 ? (int64_t)(S + (self_term ? 1 : 0)) * Fout : Fout)) return GML_E_BADARG;
     if (num_rows == 0) return GML_OK;
     if (!rowptr || !ginfo128 || !x || !w || !out) return GML_E_BADARG;
-    const bool xv = (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    if (!fwd2_shape(S, Fin, Fout, flags) || !(S == 8 || S == 4) || !xv || !fwd3_env() || (flags & GML_ACCUM) ||
-        (((uintptr_t)val & 15) != 0) || (num_rows + 16) * ldx * 4 >= (int64_t)INT32_MAX)
-        return GML_E_UNSUPPORTED;
-    GmlFwdParams p = {};
-    p.rowptr = rowptr; p.col = col; p.ginfo = ginfo128; p.val = val; p.x = x; p.ldx = ldx;
-    p.w = w; p.w_ss = w_ss; p.w_si = w_si; p.w_so = w_so; p.bias = bias; p.out = out; p.ldo = ldo;
-    p.nrows = num_rows; p.S = S; p.Fin = Fin; p.Fout = Fout; p.flags = flags; p.npass = 1; p.nchunks = 1; p.val_vec = 1;
-    p.nw = 8; p.epl = epilogue; p.ds = ds; p.ds_self = self_term ? 1 : 0; p.cc_off = self_term ? 1 : 0;
-    p.ngroups = (int)gml_cdiv(num_rows, 128);
-    int grid = p.ngroups < GML_NUM_CU ? p.ngroups : GML_NUM_CU;
-    p.groups_per_wg = (int)gml_cdiv(p.ngroups, grid);
-    grid = (int)gml_cdiv(p.ngroups, p.groups_per_wg);
-    const int nob = Fout > 16 ? 2 : 1;
-    hipStream_t st = (hipStream_t)stream;
-#define GML_FWD3_EPI(SV, B) if (S == SV && nob == B) return gml_launch_fwd3<SV, B>(p, dim3(grid), st, false);
-    GML_FWD3_EPI(8, 2) GML_FWD3_EPI(8, 1) GML_FWD3_EPI(4, 2) GML_FWD3_EPI(4, 1)
+    const FwdPlan pl = plan_fwd(S, Fin, Fout, flags);
+    if (fwd_kernel(pl, S, x, ldx, num_rows, flags, false, true) != FWD3 || (((uintptr_t)val & 15) != 0)) return GML_E_UNSUPPORTED;
+    GmlFwdParams p = fwd_params(rowptr, col, ginfo128, nullptr, val, x, ldx, w, w_ss, w_si, w_so, bias, out, ldo, num_rows, S, Fin, Fout, flags);
+    p.epl = epilogue; p.ds = ds; p.ds_self = self_term ? 1 : 0; p.cc_off = self_term ? 1 : 0;
+    return launch128(FWD3, pl, p, false, (hipStream_t)stream);
+}
+
+static int launch_family(int SC, int FPL, const GmlFwdParams& p, int NB, bool xvec, bool bf, dim3 grid, size_t lds, hipStream_t st) {
+#define GML_FAM(SCV, FPLV) if (SC == SCV && FPL == FPLV) return gml_launch_fwd_family<SCV, FPLV>(p, NB, xvec, bf, grid, lds, st);
+    GML_FWD_FAMILY_SHAPES(GML_FAM)
     return GML_E_UNSUPPORTED;
 }
+
+static const int kSC8[] = {8, 6, 4, 3, 2, 1};
+static const int kSC4[] = {16, 12, 8, 6, 4, 3, 2, 1};
 
 extern "C" int gml_spectconv_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo, const int32_t* epos,
                                  const float* val, const float* x, int64_t ldx,
@@ -218,21 +203,18 @@ extern "C" int gml_spectconv_fwd(const int32_t* rowptr, const int32_t* col, cons
     if (num_rows > (int64_t)INT32_MAX - 16) return GML_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
 
-    if (flags & (GML_GROUPS128 | GML_GROUPS64R)) {
-        // 128-row / 8-wave kernel (or its 64-row / 4-wave geometry): the caller passes 128-row group records (gml_spectconv_fwd_group_rows said 128)
-        if (!fwd2_shape(S, Fin, Fout, flags) || (((uintptr_t)val & (S % 4 == 0 ? 15 : 7)) != 0)) return GML_E_BADARG;
+    if (flags & GML_GROUPS128) {
+        // the 128-row kernels: the caller passes 128-row group records (gml_spectconv_fwd_group_rows said 128)
+        if (plan_fwd(S, Fin, Fout, flags).rows != 128 || (((uintptr_t)val & (S % 4 == 0 ? 15 : 7)) != 0)) return GML_E_BADARG;
         return launch_fwd2(rowptr, col, ginfo, epos, val, x, ldx, w, w_ss, w_si, w_so, bias, nullptr, nullptr, nullptr, nullptr,
                            out, ldo, num_rows, S, Fin, Fout, 0, flags, st);
     }
 
-    // features per lane per chunk: 8 unless 4 pads the contraction less
+    // features per lane per chunk: 8 unless 4 pads the contraction less.  The bf16x3 projection needs 8, so outside the exact-fp32
+    // mode the wider padding is taken beyond Fin = 32 (Fin = 48: sr25 / mutag forward -22 % / -15 %); Fin <= 16 keeps 4 per lane =
+    // exact products (so few terms per output do not average the split's 2^-17: mutag GNNML1's gradients left the 1e-4 bar)
     const int pad8 = (Fin + 31) / 32 * 32, pad4 = (Fin + 15) / 16 * 16;
-    // The bf16x3 projection needs 8 features per lane, so outside the exact-fp32 mode the wider padding is taken even where
-    // 4 per lane would pad less (Fin = 48: sr25 / mutag GNNML3 forward -22 % / -15 %; GML_FWD_FPL4=1 restores the old choice)
-    static const bool fpl4 = [] { const char* e = getenv("GML_FWD_FPL4"); return e && e[0] == '1'; }();
-    // (narrow inputs, Fin <= 16, keep 4 per lane = exact products: with so few terms per output the split's 2^-17 is not
-    //  averaged and mutag GNNML1's batch-normalised gradients left the 1e-4 bar, 1.5e-4)
-    const int FPL = (pad4 < pad8 && (fpl4 || (flags & GML_F32_MFMA) || Fin <= 32)) ? 4 : 8;
+    const int FPL = (pad4 < pad8 && ((flags & GML_F32_MFMA) || Fin <= 32)) ? 4 : 8;
     const int CH = 4 * FPL;
     const int nchunks = (Fin + CH - 1) / CH;
     const bool xvec = (Fin % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
@@ -259,9 +241,8 @@ extern "C" int gml_spectconv_fwd(const int32_t* rowptr, const int32_t* col, cons
 
     // persistent workgroups, each a contiguous range of 64-row groups; 2 resident per CU (LDS bound)
     const int ngroups = (int)gml_cdiv(num_rows, GML_GROUP);
-    int grid = ngroups < GML_NUM_CU * 2 ? ngroups : GML_NUM_CU * 2;
-    const int groups_per_wg = (int)gml_cdiv(ngroups, grid);
-    grid = (int)gml_cdiv(ngroups, groups_per_wg);
+    int32_t groups_per_wg;
+    const int grid = persistent_grid(ngroups, GML_NUM_CU * 2, &groups_per_wg);
 
     for (int ip = 0; ip < nparts; ++ip) {
         const int SC = parts[ip].sc;
@@ -270,15 +251,11 @@ extern "C" int gml_spectconv_fwd(const int32_t* rowptr, const int32_t* col, cons
             const int fo = (Fout - o0 < colgrp) ? Fout - o0 : colgrp;
             const int nb16 = (fo + 15) / 16;
             const int NB = nb16 <= 1 ? 1 : (nb16 <= 2 ? 2 : (nb16 <= 4 ? 4 : 8));
-            GmlFwdParams p = {};
-            p.rowptr = rowptr; p.col = col; p.ginfo = ginfo; p.epos = epos;
-            p.val = val; p.x = x; p.ldx = ldx;
-            p.w = w + (int64_t)o0 * w_so; p.w_ss = w_ss; p.w_si = w_si; p.w_so = w_so;
-            p.out = out + o0; p.ldo = ldo; p.nrows = num_rows; p.S = S; p.Fin = Fin; p.Fout = fo;
+            const bool last = (ip == nparts - 1), first = (ip == 0);
+            GmlFwdParams p = fwd_params(rowptr, col, ginfo, epos, val, x, ldx, w + (int64_t)o0 * w_so, w_ss, w_si, w_so,
+                                        (last && bias) ? bias + o0 : nullptr, out + o0, ldo, num_rows, S, Fin, fo, 0);
             p.s0 = parts[ip].s0; p.npass = parts[ip].count / SC; p.nchunks = nchunks;
             p.ngroups = ngroups; p.groups_per_wg = groups_per_wg;
-            const bool last = (ip == nparts - 1), first = (ip == 0);
-            p.bias = (last && bias) ? bias + o0 : nullptr;
             p.flags = (first ? (flags & GML_ACCUM) : GML_ACCUM) | (last ? (flags & GML_RELU) : 0u) | (flags & 0xff00u);
             const size_t wblk = (size_t)SC * FPL * NB * 64 * sizeof(float);
             const size_t all = wblk * p.npass * nchunks;
@@ -304,15 +281,14 @@ extern "C" int gml_ml3_fwd(const int32_t* rowptr, const int32_t* col, const int3
                            float* out, int64_t ldo, int64_t num_rows, int32_t S, int32_t Fin, int32_t nout1,
                            int32_t F2, uint32_t flags, gml_stream_t stream) {
     if (F2 < 0 || ldo < nout1 + F2 || (F2 > 0 && (!w11 || !w12))) return GML_E_BADARG;
-#ifndef GML_NO_MIXFUSE
-    if (num_rows > 0 && F2 > 0 && F2 <= 8 && (flags & (GML_GROUPS128 | GML_GROUPS64R)) && fwd2_shape(S, Fin, nout1, flags) &&
-        !fwd4_only_shape(S, Fin, nout1, flags) && !(flags & GML_FWD_CHUNKED) && !fwd4_all_env() &&
+    const FwdPlan pl = plan_fwd(S, Fin, nout1, flags);
+    /* fused: fwd3 / fwd2 carry the Hadamard branch (the chunked kernel does not) */
+    if (num_rows > 0 && F2 > 0 && F2 <= 8 && (flags & GML_GROUPS128) && pl.rows == 128 && !pl.chunked &&
         (((uintptr_t)val & 15) == 0) && !(flags & GML_ACCUM)) {
         if (!rowptr || !ginfo || !x || !w || !out) return GML_E_BADARG;
         return launch_fwd2(rowptr, col, ginfo, epos, val, x, ldx, w, w_ss, w_si, w_so, bias, w11, b11, w12, b12, out, ldo,
                            num_rows, S, Fin, nout1, F2, flags, (hipStream_t)stream);
     }
-#endif
     int rc = gml_spectconv_fwd(rowptr, col, ginfo, epos, val, x, ldx, w, w_ss, w_si, w_so, bias, out, ldo, num_rows, S,
                                Fin, nout1, flags, stream);
     if (rc != GML_OK || F2 == 0) return rc;
@@ -363,9 +339,6 @@ static int launch_spmm(const int32_t* rowptr, const int32_t* col, const int32_t*
     return gml_launch_status();
 }
 
-extern "C" int gml_spmm_fwd_ex(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo128, const int32_t* epos,
-                               const float* val, const float* x, int64_t ldx, float* h, int64_t num_rows, int32_t S,
-                               int32_t Fin, int32_t max_group_edges, gml_stream_t stream);
 extern "C" int gml_spmm_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo128, const int32_t* epos,
                             const float* val, const float* x, int64_t ldx, float* h, int64_t num_rows, int32_t S,
                             int32_t Fin, gml_stream_t stream) {
@@ -380,25 +353,21 @@ extern "C" int gml_spmm_fwd_ex(const int32_t* rowptr, const int32_t* col, const 
     if (!rowptr || !x || !h) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     // ring kernel (gml_spmm3_impl.h): any S (chunks of 4, 2, 1 supports), any Fin (chunks of 32 features), degrees up to ~16 per
-    // row on average staged in LDS.  GML_SPMM3=0: the r02 paths below, for A/B runs.
-    static const bool spmm3_on = [] { const char* e = getenv("GML_SPMM3"); return !(e && e[0] == '0'); }();
-    // Shapes the register-staged 8-wave kernel (fwd2, NOB = 0) covers keep it while every group fits its 1024-edge staging
-    // (ZINC: 0.65 vs 0.61 of the roof at 131,072 graphs); unknown group sizes (max_group_edges < 0): as before r03.
-    const bool fwd2_fits = fwd2_shape(S, Fin, 16, 0) && (((uintptr_t)val & 15) == 0) && (max_group_edges < 0 || max_group_edges <= GML_FWD2_ECAP);
-    if (spmm3_on && !fwd2_fits && ginfo128 != nullptr && epos == nullptr && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0) && Fin % 4 == 0 &&
+    // row on average staged in LDS.  Shapes of the conv's 128-row class (plan_fwd) keep fwd2's NOB = 0 form, or the loop below, while
+    // every group fits fwd2's 1024-edge staging (ZINC: 0.65 vs 0.61 of the roof at 131,072 graphs) or the group sizes are unknown (< 0)
+    const bool rows128 = plan_fwd(S, Fin, 16, 0).rows == 128;
+    const bool fwd2_fits = rows128 && (((uintptr_t)val & 15) == 0) && (max_group_edges < 0 || max_group_edges <= GML_FWD2_ECAP);
+    if (!fwd2_fits && ginfo128 != nullptr && epos == nullptr && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0) && Fin % 4 == 0 &&
         (((uintptr_t)h & 15) == 0) && (((uintptr_t)val & 3) == 0) && (num_rows + 16) * ldx * 4 < (int64_t)INT32_MAX &&
         (int64_t)128 * S * Fin * 4 < (int64_t)INT32_MAX && (int64_t)S * 4 * 24 <= GmlSpmm3Cfg::VAL_BYTES) {
         GmlSpmm3Params q = {};
         q.rowptr = rowptr; q.col = col; q.ginfo = ginfo128; q.val = val; q.ldx = ldx; q.h = h; q.nrows = num_rows; q.S = S; q.hs = Fin;
         q.ngroups = (int)gml_cdiv(num_rows, 128);
-        int grid = q.ngroups < GML_NUM_CU ? q.ngroups : GML_NUM_CU;
-        q.groups_per_wg = (int)gml_cdiv(q.ngroups, grid);
-        grid = (int)gml_cdiv(q.ngroups, q.groups_per_wg);
-        static const bool w48_on = [] { const char* e = getenv("GML_SPMM3_W48"); return !(e && e[0] == '0'); }();
+        const int grid = persistent_grid(q.ngroups, GML_NUM_CU, &q.groups_per_wg);
         for (int f0 = 0; f0 < Fin;) {                           // feature chunks: separate launches, the value rows are read again
             const int left = Fin - f0;
             // a remainder of 36 .. 48 features is ONE launch of the 192-byte-row form (sr25 / mutag hidden width 48); else chunks of 32
-            const bool w48 = w48_on && left > 32 && left <= 48 && (int64_t)S * 4 * 24 <= GmlSpmm3CfgT<true>::VAL_BYTES;
+            const bool w48 = left > 32 && left <= 48 && (int64_t)S * 4 * 24 <= GmlSpmm3CfgT<true>::VAL_BYTES;
             q.x = x + f0; q.Fin = w48 ? left : (left < 32 ? left : 32); q.hf0 = f0;
             int rc;
             if (w48) rc = (S % 4 == 0) ? gml_launch_spmm3<4, true>(q, dim3(grid), st)
@@ -410,20 +379,15 @@ extern "C" int gml_spmm_fwd_ex(const int32_t* rowptr, const int32_t* col, const 
         }
         return GML_OK;
     }
-    if (ginfo128 != nullptr && epos == nullptr && fwd2_shape(S, Fin, 16, 0) && (((uintptr_t)val & 15) == 0) &&
-        (((uintptr_t)h & 15) == 0)) {
+    if (ginfo128 != nullptr && epos == nullptr && rows128 && (((uintptr_t)val & 15) == 0) && (((uintptr_t)h & 15) == 0)) {
         // the 8-wave kernel's staged, degree-ranked aggregation; H written straight from the accumulators
-        const bool xv = (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
-        GmlFwdParams p = {};
-        p.rowptr = rowptr; p.col = col; p.ginfo = ginfo128; p.val = val; p.x = x; p.ldx = ldx;
-        p.nrows = num_rows; p.S = S; p.Fin = Fin; p.Fout = 16; p.npass = 1; p.nchunks = 1; p.val_vec = 1; p.hout = h;
+        GmlFwdParams p = fwd_params(rowptr, col, ginfo128, nullptr, val, x, ldx, nullptr, 0, 0, 0, nullptr, nullptr, 0, num_rows, S, Fin, 16, 0);
+        p.hout = h;
         p.ngroups = (int)gml_cdiv(num_rows, GML_FWD2_ROWS);
-        int grid = p.ngroups < GML_NUM_CU ? p.ngroups : GML_NUM_CU;
-        p.groups_per_wg = (int)gml_cdiv(p.ngroups, grid);
-        grid = (int)gml_cdiv(p.ngroups, p.groups_per_wg);
-        if (S == 8) return gml_launch_fwd2<8, 0>(p, dim3(grid), st, xv, false);
-        if (S == 4) return gml_launch_fwd2<4, 0>(p, dim3(grid), st, xv, false);
-        if (S == 12) return gml_launch_fwd2<12, 0>(p, dim3(grid), st, xv, false);
+        const dim3 grid(persistent_grid(p.ngroups, GML_NUM_CU, &p.groups_per_wg));
+#define GML_SPMM2_GO(SV) if (S == SV) return gml_launch_fwd2<SV, 0>(p, grid, st, x_float4(x, ldx), false);
+        GML_SPMM2_SHAPES(GML_SPMM2_GO)
+        /* (the shapes only the chunked conv kernel serves have no NOB = 0 instantiation: the loop below) */
     }
     int s0 = 0;
     while (s0 < S) {

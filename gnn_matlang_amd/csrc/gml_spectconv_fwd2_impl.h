@@ -35,15 +35,11 @@ struct GmlFwd2Cfg {
     static constexpr int W_HALF = S * 32 * 32;                 // bf16 elements of one (hi or lo) W image [s][o][f]
     static constexpr int TILE_BYTES = 8 * 16 * 36 * 4;         // stand-alone SpMM: one [16][36] output tile per wave
     static constexpr int W_BYTES = 2 * W_HALF * 2 > TILE_BYTES ? 2 * W_HALF * 2 : TILE_BYTES;   // (shares the W area)
-    // NW = 8 waves / 128-row groups (one workgroup per CU) or NW = 4 waves / 64-row groups (two independent workgroups
-    // per CU: each one's per-group latency chain -- record, data, commit, barrier -- overlaps the other's arithmetic)
-    static constexpr int rows(int nw) { return 16 * nw; }
-    static constexpr int ecap(int nw) { return (S > 8 ? 12 : 8) * rows(nw); }   // staged edges per group (S = 12, counting.py: 7 edges per row)
-    static constexpr int xcap(int nw) { return nw == 8 ? GML_FWD2_XCAP : 144; }   // 64 rows + 2 x the largest graph
-    static constexpr size_t lds_bytes(int nw = 8) {
-        return (size_t)W_BYTES + (rows(nw) + 8) * 4 + (size_t)ecap(nw) * 4 + (size_t)ecap(nw) * S * 4 +
-               (size_t)xcap(nw) * LDX * 4;
-    }
+    // 8 waves / 128-row groups, one workgroup per CU
+    static constexpr int ROWS = GML_FWD2_ROWS;
+    static constexpr int ECAP = (S > 8 ? 12 : 8) * ROWS;       // staged edges per group (S = 12, counting.py: 7 edges per row)
+    static constexpr int XCAP = GML_FWD2_XCAP;
+    static constexpr size_t LDS_BYTES = (size_t)W_BYTES + (ROWS + 8) * 4 + (size_t)ECAP * 4 + (size_t)ECAP * S * 4 + (size_t)XCAP * LDX * 4;
 };
 
 // XVEC: the X rows are float4-addressable (ldx % 4 == 0, aligned base); else the window is staged element-wise
@@ -55,29 +51,26 @@ struct GmlFwd2Cfg {
 // 37 % of its time (profiles/r02_g_edge_fwd_ablation.txt).  The positions are loaded with the other prefetch loads, the
 // value rows they address after the aggregation loop (the positions have arrived by then: no exposed dependent latency).
 // F16 (round 6, GML_F16X3: see gml_spectconv_fwd3_impl.h): projection and Hadamard branch on f16 (hi, lo) pieces under power-of-two
-// scales -- the conv instantiations of the 8-wave geometry (counting.py's 12 supports, every shape fwd3 does not take)
+// scales -- the conv instantiations (counting.py's 12 supports, every call fwd3 does not take)
+// NW: always 8 (the 4-wave / 64-row geometry was removed; the parameter keeps the kernel names of the profiles)
 template <int S, int NOB, bool XVEC, bool MIX, bool EP = false, int NW = 8, bool F16 = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void gml_k_spectconv_fwd2(const GmlFwdParams p) {
+__global__ __launch_bounds__(64 * NW, 1) void gml_k_spectconv_fwd2(const GmlFwdParams p) {
     using C = GmlFwd2Cfg<S>;
     using FT = typename GmlPiece<F16>::T;
     constexpr bool HOUT = (NOB == 0);
-    static_assert(!F16 || (NOB != 0 && NW == 8), "f16 pieces: conv instantiations, 8-wave geometry");
+    static_assert(NW == 8, "one geometry: 8 waves, 128-row groups");
+    static_assert(!F16 || NOB != 0, "f16 pieces: conv instantiations");
     static_assert(!(EP && NOB == 0), "the stand-alone SpMM instantiations take contiguous value rows");
-    static_assert(NW == 8 || (NW == 4 && NOB != 0), "4-wave geometry: conv instantiations only");
-    constexpr int NT = 64 * NW, ECAP = C::ecap(NW), XCAP = C::xcap(NW);
+    constexpr int NT = 64 * NW, ECAP = C::ECAP, XCAP = C::XCAP;
     constexpr int NOBA = HOUT ? 1 : NOB;
     constexpr bool H32 = HOUT && MIX;                          // SpMM instantiations reuse the MIX slot: Fin == 32 (full-line stores)
     constexpr bool MIXB = MIX && !HOUT;
     constexpr bool ROT = HOUT;                                 // loop shape, see below
-    // group records one stage ahead of the data they describe: only in the rotated shape.  Measured again in round 2
-    // (-DGML_FWD2_REC_AHEAD, tools/ab.sh): with the record prefetched the conv instantiations run 10 % SLOWER (2.34 vs 2.12
-    // ms/step), although the dependent record -> data round trip disappears from the issue burst.
-#ifdef GML_FWD2_REC_AHEAD
-    constexpr bool RECPRE = true;
-#else
+    // group records one stage ahead of the data they describe: only in the rotated shape.  With the record prefetched the conv
+    // instantiations measured 10 % SLOWER (2.34 vs 2.12 ms/step, round 2), although the dependent record -> data round trip
+    // disappears from the issue burst.
     constexpr bool RECPRE = ROT;
-#endif
-    constexpr int LDX = C::LDX, ROWS = C::rows(NW);
+    constexpr int LDX = C::LDX, ROWS = C::ROWS;
     constexpr int VAL_ALIGN = (S % 4 == 0) ? 4 : ((S % 2 == 0) ? 2 : 1);
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __bf16* Wof_h = reinterpret_cast<__bf16*>(lds_raw);       // [s][o][f], 16-byte chunks XOR-swizzled by gml_wkey(o)
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void gml_k_spectconv_fwd2
     int row_n = 0;
     uint32_t outrows_n = 0;
     auto load_rec = [&](int g) {
-        const int32_t* rec = p.ginfo + (int64_t)g * GML_GREC_INTS(NW == 8 ? 128 : GML_GROUPS64_RANKED);
+        const int32_t* rec = p.ginfo + (int64_t)g * GML_GREC_INTS(128);
         rec_gi = *reinterpret_cast<const int4*>(rec);
         rec_row = reinterpret_cast<const unsigned char*>(rec + 4)[wave * 16 + r16];
         rec_outrows = reinterpret_cast<const uint32_t*>(rec + 4)[wave * 4 + kq];
@@ -558,53 +551,44 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void gml_k_spectconv_fwd2
 template <int S, int NOB>
 int gml_launch_fwd2(const GmlFwdParams& p, dim3 grid, hipStream_t st, bool xvec, bool mix);
 
-#define GML_FWD2_LAUNCH_N(SV, NOBV, XV, MX, EPV, NWV)                                                        \
+#define GML_FWD2_LAUNCH_F(SV, NOBV, XV, MX, EPV, F16V)                                                       \
     {                                                                                                        \
-        GML_ALLOW_BIG_LDS(rc_, (&gml_k_spectconv_fwd2<SV, NOBV, XV, MX, EPV, NWV>), 160 * 1024)              \
+        GML_ALLOW_BIG_LDS(rc_, (&gml_k_spectconv_fwd2<SV, NOBV, XV, MX, EPV, 8, F16V>), 160 * 1024)          \
         if (rc_ != hipSuccess) return (int)rc_;                                                              \
-        hipLaunchKernelGGL((gml_k_spectconv_fwd2<SV, NOBV, XV, MX, EPV, NWV>), grid, dim3(64 * NWV),         \
-                           GmlFwd2Cfg<SV>::lds_bytes(NWV), st, p);                                           \
-        return gml_launch_status();                                                                          \
-    }
-#define GML_FWD2_LAUNCH_F(SV, NOBV, XV, MX, EPV)                                                             \
-    {                                                                                                        \
-        GML_ALLOW_BIG_LDS(rc_, (&gml_k_spectconv_fwd2<SV, NOBV, XV, MX, EPV, 8, true>), 160 * 1024)          \
-        if (rc_ != hipSuccess) return (int)rc_;                                                              \
-        hipLaunchKernelGGL((gml_k_spectconv_fwd2<SV, NOBV, XV, MX, EPV, 8, true>), grid, dim3(512),          \
-                           GmlFwd2Cfg<SV>::lds_bytes(8), st, p);                                             \
+        hipLaunchKernelGGL((gml_k_spectconv_fwd2<SV, NOBV, XV, MX, EPV, 8, F16V>), grid, dim3(512),          \
+                           GmlFwd2Cfg<SV>::LDS_BYTES, st, p);                                                \
         return gml_launch_status();                                                                          \
     }
 #define GML_FWD2_LAUNCH_E(SV, NOBV, XV, MX, EPV)                                                             \
     {                                                                                                        \
-        if constexpr (NOBV != 0) { if (p.flags & GML_F16X3) GML_FWD2_LAUNCH_F(SV, (NOBV != 0 ? NOBV : 1), XV, MX, EPV) }  \
-        GML_FWD2_LAUNCH_N(SV, NOBV, XV, MX, EPV, 8)                                                          \
+        if constexpr (NOBV != 0) { if (p.flags & GML_F16X3) GML_FWD2_LAUNCH_F(SV, (NOBV != 0 ? NOBV : 1), XV, MX, EPV, true) }  \
+        GML_FWD2_LAUNCH_F(SV, NOBV, XV, MX, EPV, false)                                                      \
     }
-#define GML_FWD2_LAUNCH(SV, NOBV, XV, MX) GML_FWD2_LAUNCH_E(SV, NOBV, XV, MX, false)
 #define GML_DEFINE_SPMM2(SV)                                                                                 \
     template <>                                                                                              \
     int gml_launch_fwd2<SV, 0>(const GmlFwdParams& p, dim3 grid, hipStream_t st, bool xvec, bool) {          \
-        if (xvec && p.Fin == 32) GML_FWD2_LAUNCH(SV, 0, true, true)                                          \
-        if (xvec) GML_FWD2_LAUNCH(SV, 0, true, false)                                                        \
-        GML_FWD2_LAUNCH(SV, 0, false, false)                                                                 \
+        if (xvec && p.Fin == 32) GML_FWD2_LAUNCH_E(SV, 0, true, true, false)                                 \
+        if (xvec) GML_FWD2_LAUNCH_E(SV, 0, true, false, false)                                               \
+        GML_FWD2_LAUNCH_E(SV, 0, false, false, false)                                                        \
+    }
+#define GML_FWD2_LAUNCH_XM(SV, NOBV, EPV)   /* the (XVEC, MIX) choice */                                     \
+    {                                                                                                        \
+        if (xvec && mix) GML_FWD2_LAUNCH_E(SV, NOBV, true, true, EPV)                                        \
+        if (xvec) GML_FWD2_LAUNCH_E(SV, NOBV, true, false, EPV)                                              \
+        if (mix) GML_FWD2_LAUNCH_E(SV, NOBV, false, true, EPV)                                               \
+        GML_FWD2_LAUNCH_E(SV, NOBV, false, false, EPV)                                                       \
     }
 #define GML_DEFINE_FWD2(SV, NOBV)                                                                            \
     template <>                                                                                              \
     int gml_launch_fwd2<SV, NOBV>(const GmlFwdParams& p, dim3 grid, hipStream_t st, bool xvec, bool mix) {   \
-        if (p.nw == 4) {   /* 4-wave geometry: float4-addressable x only (the dispatcher checks) */          \
-            if (!xvec) return GML_E_UNSUPPORTED;                                                             \
-            if (p.epos != nullptr && mix) GML_FWD2_LAUNCH_N(SV, NOBV, true, true, true, 4)                   \
-            if (p.epos != nullptr) GML_FWD2_LAUNCH_N(SV, NOBV, true, false, true, 4)                         \
-            if (mix) GML_FWD2_LAUNCH_N(SV, NOBV, true, true, false, 4)                                       \
-            GML_FWD2_LAUNCH_N(SV, NOBV, true, false, false, 4)                                               \
-        }                                                                                                    \
-        if (p.epos != nullptr) {                                                                             \
-            if (xvec && mix) GML_FWD2_LAUNCH_E(SV, NOBV, true, true, true)                                   \
-            if (xvec) GML_FWD2_LAUNCH_E(SV, NOBV, true, false, true)                                         \
-            if (mix) GML_FWD2_LAUNCH_E(SV, NOBV, false, true, true)                                          \
-            GML_FWD2_LAUNCH_E(SV, NOBV, false, false, true)                                                  \
-        }                                                                                                    \
-        if (xvec && mix) GML_FWD2_LAUNCH(SV, NOBV, true, true)                                               \
-        if (xvec) GML_FWD2_LAUNCH(SV, NOBV, true, false)                                                     \
-        if (mix) GML_FWD2_LAUNCH(SV, NOBV, false, true)                                                      \
-        GML_FWD2_LAUNCH(SV, NOBV, false, false)                                                              \
+        if (p.epos != nullptr) GML_FWD2_LAUNCH_XM(SV, NOBV, true)                                            \
+        GML_FWD2_LAUNCH_XM(SV, NOBV, false)                                                                  \
     }
+
+/* the compiled shapes, written ONCE, one list per gml_fwd2_fam*.hip; the dispatch derives from them.  Conv: (S, NOB); SpMM (NOB = 0): (S) */
+#define GML_FWD2_SHAPES_A(X) X(8, 2) X(8, 1) X(4, 2) X(4, 1)
+#define GML_FWD2_SHAPES_B(X) X(12, 2) X(12, 1)                 /* counting.py's 12 supports */
+#define GML_FWD2_SHAPES(X) GML_FWD2_SHAPES_A(X) GML_FWD2_SHAPES_B(X)
+#define GML_SPMM2_SHAPES_A(X) X(8) X(4)
+#define GML_SPMM2_SHAPES_B(X) X(12)
+#define GML_SPMM2_SHAPES(X) GML_SPMM2_SHAPES_A(X) GML_SPMM2_SHAPES_B(X)

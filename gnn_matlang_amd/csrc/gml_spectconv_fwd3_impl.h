@@ -715,3 +715,8 @@ int gml_launch_fwd3(const GmlFwdParams& p, dim3 grid, hipStream_t st, bool mix);
         if (mix) GML_FWD3_LAUNCH(SV, NOBV, true, false)                                                      \
         GML_FWD3_LAUNCH(SV, NOBV, false, false)                                                              \
     }
+
+/* the compiled shapes (S, NOB), written ONCE, one list per gml_fwd3_fam_*.hip; the dispatch derives from them */
+#define GML_FWD3_SHAPES_A(X) X(8, 2) X(8, 1)
+#define GML_FWD3_SHAPES_B(X) X(4, 2) X(4, 1)
+#define GML_FWD3_SHAPES(X) GML_FWD3_SHAPES_A(X) GML_FWD3_SHAPES_B(X)

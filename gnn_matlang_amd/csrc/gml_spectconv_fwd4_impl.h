@@ -834,7 +834,7 @@ int gml_launch_fwd4(const GmlFwdParams& p, dim3 grid, hipStream_t st);
         if (p.flags & GML_F16X3) GML_FWD4_LAUNCH_F(SV, FBV, NOBV, EPV, X1V, true)                            \
         GML_FWD4_LAUNCH_F(SV, FBV, NOBV, EPV, X1V, false)                                                    \
     }
-// GML_FWD_ONEWIN (48-feature shapes only): the single-window form, for batches whose groups need edge chunks
+// flag GML_FWD_ONEWIN (48-feature shapes only): the single-window form, for batches whose groups need edge chunks
 #define GML_DEFINE_FWD4(SV, FBV, NOBV)                                                                       \
     template <>                                                                                              \
     int gml_launch_fwd4<SV, FBV, NOBV>(const GmlFwdParams& p, dim3 grid, hipStream_t st) {                   \
@@ -847,3 +847,9 @@ int gml_launch_fwd4(const GmlFwdParams& p, dim3 grid, hipStream_t st);
         if (p.epos != nullptr) GML_FWD4_LAUNCH(SV, FBV, NOBV, true, false)                                   \
         GML_FWD4_LAUNCH(SV, FBV, NOBV, false, false)                                                         \
     }
+
+/* the compiled shapes (S, FB, NOB), written ONCE, one list per gml_fwd4_fam_*.hip (8 supports x 48 features: no script has it; it spilled) */
+#define GML_FWD4_SHAPES_A(X) X(4, 0, 2) X(4, 1, 2)
+#define GML_FWD4_SHAPES_B(X) X(6, 0, 2) X(6, 1, 2)
+#define GML_FWD4_SHAPES_C(X) X(8, 0, 2)
+#define GML_FWD4_SHAPES(X) GML_FWD4_SHAPES_A(X) GML_FWD4_SHAPES_B(X) GML_FWD4_SHAPES_C(X)

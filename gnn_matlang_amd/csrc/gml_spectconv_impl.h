@@ -48,7 +48,7 @@ struct GmlFwdParams {
     int32_t F2, mix_col;
     float* hout;          // stand-alone SpMM on the 8-wave kernel: H [N, S, Fin] receives the aggregate, no projection
     unsigned long long* prof;   // timing build (-DGML_FWD2_TIMING): per-phase cycle sums
-    int32_t nw;           // 8-wave kernel family: waves per workgroup (8: 128-row groups, 4: ranked 64-row groups)
+    int32_t reserved0;    // (was nw, the 4-wave geometry's switch: the slot stays so that every kernel's argument offsets do)
     // epilogues of the ring kernel (gml_spectconv_fwd_epi): 0 = sum_s H_s W_s; 1 = SpectConCatConv: H_s W_s written to column block
     // s + cc_off (libs/spect_conv.py:137-158); 2 = depthwise: (sum_s ds[s] . H_s + ds[S] . x) W_0 (libs/spect_conv.py:81-91)
     const float* ds;      // depthwise: [S (+ 1 if ds_self), Fin] scales (row 0 already holds 1 + DSweight[0])
@@ -515,3 +515,13 @@ int gml_launch_fwd_family(const GmlFwdParams& p, int NB, bool xvec, bool bf, dim
         }                                                                                             \
         return GML_E_UNSUPPORTED;                                                                     \
     }
+
+/* the compiled (SC supports per pass, FPL features per lane) families, written ONCE, one list per gml_fwd_fam_*.hip */
+#define GML_FWD_FAMILY_SHAPES_A(X) X(1, 8) X(2, 8) X(3, 8)
+#define GML_FWD_FAMILY_SHAPES_B(X) X(4, 8) X(6, 8)
+#define GML_FWD_FAMILY_SHAPES_C(X) X(8, 8) X(1, 4)
+#define GML_FWD_FAMILY_SHAPES_D(X) X(2, 4) X(3, 4) X(4, 4)
+#define GML_FWD_FAMILY_SHAPES_E(X) X(6, 4) X(8, 4)
+#define GML_FWD_FAMILY_SHAPES_F(X) X(12, 4) X(16, 4)
+#define GML_FWD_FAMILY_SHAPES(X) GML_FWD_FAMILY_SHAPES_A(X) GML_FWD_FAMILY_SHAPES_B(X) GML_FWD_FAMILY_SHAPES_C(X) \
+    GML_FWD_FAMILY_SHAPES_D(X) GML_FWD_FAMILY_SHAPES_E(X) GML_FWD_FAMILY_SHAPES_F(X)

@@ -297,9 +297,8 @@ def _fused_conv(rowptr, col, ginfo, epos, val, x, ldx, w, w_strides, bias, out, 
 
 
 def conv_epilogue_applies(S, Fin, Fout):
-    """shape class of gml_spectconv_fwd_epi (the ring kernel's ConCat / depthwise epilogues); GML_NO_EPILOGUE=1: the mapping"""
-    return (not exact_mode()) and S in (4, 8) and Fin <= 32 and Fout <= 32 and not _os.environ.get('GML_NO_EPILOGUE') \
-        and not _os.environ.get('GML_FWD64') and _os.environ.get('GML_FWD_DMA', '1') != '0'
+    """shape class of gml_spectconv_fwd_epi (the ring kernel's ConCat / depthwise epilogues)"""
+    return (not exact_mode()) and S in (4, 8) and Fin <= 32 and Fout <= 32
 
 
 def conv_epilogue(csr, x, val, w, bias, S, epilogue, ds, self_term, ncols):
@@ -331,28 +330,24 @@ def fwd_groups(csr, x, S, Fin, Fout):
     """(group records, extra flags) the forward kernel wants for this shape: the 8-wave kernel on 128-row records when
     the shape is compiled for it, else the 64-row kernel."""
     flags = _lib.GML_F32_MFMA if exact_mode() else 0
-    if _os.environ.get('GML_FWD64'):                         # experiments: force the 4-wave / 64-row kernel family
-        return csr.ginfo, 0
-    rows = int(_lib.lib().gml_spectconv_fwd_group_rows(int(S), int(Fin), int(Fout), flags))
     L = _lib.lib()
+    rows = int(L.gml_spectconv_fwd_group_rows(int(S), int(Fin), int(Fout), flags))
+    # a window bound without GML_FWD_CHUNKED: only the chunked ring kernel (fwd4) serves the shape on 128-row records
+    win4 = int(L.gml_spectconv_fwd_stage_window(int(S), int(Fin), int(Fout), flags))
     gm_known = getattr(csr, 'gmax128', None) is not None
     gm_e, gm_w = csr.gmax128 if gm_known else (0, 0)
     x4 = x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
     # the chunked ring kernel (fwd4) addresses x with 32-bit byte offsets and needs the real group maxima to check its window: without
     # either, the 64-row family (any size, global gathers where a group does not fit) -- ADVICE r04
     small32 = (int(csr.N) + 16) * int(x.stride(0)) * 4 < 2 ** 31
-    if rows == 128 and (S == 6 or (S == 4 and Fin > 32)) and not (gm_known and small32):
-        rows = 64
     if rows == 128:
         cap = int(L.gml_spectconv_fwd_stage_edges(int(S), int(Fin), int(Fout), flags))      # edges of one work item of the ring kernel
-        only4 = S == 6 or (S == 4 and Fin > 32)   # 6 supports / 48 features exist only on the chunked ring kernel: float4 rows, windows it can stage
-        if only4:
-            win = int(L.gml_spectconv_fwd_stage_window(int(S), int(Fin), int(Fout), flags))
-            if not x4 or (win > 0 and gm_w > win) or (gm_e > cap and not FWD_CHUNKS):
+        if win4:                                  # fwd4 alone: known maxima, 32-bit offsets, float4 rows, windows it can stage
+            if not (gm_known and small32 and x4) or gm_w > win4 or (gm_e > cap and not FWD_CHUNKS):
                 rows = 64
             elif gm_e > cap:
                 # 48 features: one staged X window instead of two -> twice the edges per chunk (sr25: 2 chunks per group instead of 4)
-                onewin = _lib.GML_FWD_ONEWIN if (Fin > 32 and _os.environ.get('GML_FWD_ONEWIN', '1') != '0') else 0
+                onewin = _lib.GML_FWD_ONEWIN if Fin > 32 else 0
                 _path('conv_fwd', 'fused 8-wave bf16x3, edge chunks%s' % (', one X window' if onewin else ''), S, Fin, Fout)
                 return csr.ginfo128, _lib.GML_GROUPS128 | onewin
         elif cap > 0 and gm_e > cap and FWD_CHUNKS and x4 and small32:
@@ -364,23 +359,14 @@ def fwd_groups(csr, x, S, Fin, Fout):
     if rows == 128:
         _path('conv_fwd', 'fused 8-wave bf16x3', S, Fin, Fout)
         return csr.ginfo128, _lib.GML_GROUPS128
-    if rows == _lib.GML_GROUPS64_RANKED:
-        if x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0:
-            _path('conv_fwd', 'fused 4-wave geometry of the 8-wave kernel, 2 workgroups per CU, bf16x3', S, Fin, Fout)
-            return csr.ranked64()[0], _lib.GML_GROUPS64R
-        _path('conv_fwd', 'fused 8-wave bf16x3', S, Fin, Fout)
-        return csr.ginfo128, _lib.GML_GROUPS128
     _path('conv_fwd', 'fused 4-wave (%s)' % ('f32 MFMA' if (exact_mode() or Fin <= 16 or Fout > 32) else 'bf16x3'), S, Fin, Fout)
     return csr.ginfo, 0
 
 
 def fwd_gathers(S, Fin, Fout):
-    """True when the forward of this shape runs on the 8-wave kernel, which can take its value rows through a position map
-    (GML_EDGE_DUAL=1 keeps the round-1 scheme -- edge branch in target order, second copy scattered -- for A/B)."""
-    if _os.environ.get('GML_FWD64') or _os.environ.get('GML_EDGE_DUAL'):
-        return False
+    """True when the forward of this shape runs on the 8-wave kernel, which can take its value rows through a position map."""
     flags = _lib.GML_F32_MFMA if exact_mode() else 0
-    return int(_lib.lib().gml_spectconv_fwd_group_rows(int(S), int(Fin), int(Fout), flags)) in (128, _lib.GML_GROUPS64_RANKED)
+    return int(_lib.lib().gml_spectconv_fwd_group_rows(int(S), int(Fin), int(Fout), flags)) == 128
 
 
 def ml3_edge_in_source_order(csr, S, Fin, Fout):

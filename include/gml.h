@@ -52,8 +52,8 @@ enum {
                          bf16x3 split on the bf16 matrix cores (fp32-class: ~1e-6 of the output scale)       */
     GML_GROUPS128 = 8, /* gml_spectconv_fwd: `ginfo` holds 128-row group records (gml_spectconv_fwd_group_rows() = 128):
                          the 8-wave forward kernel                                                            */
-    GML_GROUPS64R = 16, /* gml_spectconv_fwd: `ginfo` holds ranked 64-row records (gml_spectconv_fwd_group_rows() =
-                         GML_GROUPS64_RANKED): the same kernel in its 4-wave geometry, two workgroups per CU     */
+    /* 16: unused (was GML_GROUPS64R, the 8-wave kernel's 4-wave geometry on ranked 64-row records; removed, 5a81d54 is the last
+                         commit that has it) */
     GML_FWD_CHUNKED = 64, /* gml_spectconv_fwd / gml_ml3_fwd with GML_GROUPS128: some 128-row group holds more edges than the ring
                          kernel stages at once (the caller knows the maximum from its group records): take the chunked ring kernel
                          (gml_k_spectconv_fwd4), which walks such groups in edge chunks instead of gathering from global memory */
@@ -62,7 +62,7 @@ enum {
     GML_FWD_ONEWIN = 256, /* gml_spectconv_fwd, 48-feature shapes on the chunked ring kernel: ONE staged X window instead of two, twice the
                          edges per work item -- for batches whose groups need edge chunks (the caller knows the batch's largest group) */
     GML_DMA_RING = 32,  /* gml_spectconv_bwd / _bwd_mix: take the LDS-DMA landing-ring kernel (bwd4) where it applies; the
-                         forward uses its ring kernel (fwd3) by default (GML_FWD_DMA=0 in the environment turns it off)   */
+                         forward uses its ring kernel (fwd3) by default                                                  */
     GML_F16X3 = 1024,   /* gml_spectconv_fwd / gml_ml3_fwd on the 8-wave kernels (fwd3, its register-staged form fwd2, the chunked ring kernel fwd4): project with f16 (hi, lo) pieces under per-tile /
                          per-column power-of-two scales instead of bf16 pairs: residual 2^-24 instead of 2^-17 per operand, same
                          instruction count on the matrix pipe (csrc/gml_common.h "f16x3").  Ignored by the 64-row kernel family. */
@@ -161,11 +161,8 @@ int gml_csr_link_transpose(const int32_t* perm_fwd, const int32_t* perm_t, int64
  *   {first edge, #edges, smallest column id, column-window width},
  *   128-row groups: then 128 bytes, the local row each lane position of the backward kernel works on -- rows ranked
  *   by degree so that the 16 rows of a tile run near-equal edge loops, rank blocks dealt to the waves so the SIMDs
- *   stay balanced (which lane serves a row never changes the row's result);
- *   group_rows = GML_GROUPS64_RANKED (1064): 64-row groups that carry the same rank bytes (64 of them) -- the staging
- *   schedule of the forward kernel in its 4-wave geometry (GML_GROUPS64R), which runs two workgroups per CU.
+ *   stay balanced (which lane serves a row never changes the row's result).
  * Callers size LDS with the maxima of ints 1 and 3 over the records.  gml_csr_group_record_ints = int32 per record. */
-#define GML_GROUPS64_RANKED 1064
 int32_t gml_csr_group_record_ints(int32_t group_rows);
 int gml_csr_group_info(const int32_t* rowptr, const int32_t* col, int64_t num_rows, int32_t group_rows,
                        int32_t* ginfo, gml_stream_t stream);
@@ -258,7 +255,7 @@ int gml_scatter_rows(const float* in, const int32_t* perm, float* out, int64_t r
  * W element (s, i, o) lives at w[s*w_ss + i*w_si + o*w_so] so the transposed weights of the
  * backward pass need no copy.  bias may be NULL.  Used for: forward (CSR by target, x = X),
  * d/dX (CSR by source, x = dOut, W transposed view, epos = pos_t). */
-/* group size (64 | 128) whose records the forward wants for this shape and arithmetic; 128 additionally needs
+/* group size (64 or 128) whose records the forward wants for this shape and arithmetic; 128 additionally needs
  * epos == NULL -- the caller then passes those records and GML_GROUPS128 */
 int32_t gml_spectconv_fwd_group_rows(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags);
 /* edges of one 128-row group the ring kernel of this shape keeps in LDS at once (0: not applicable).  When the largest group of the

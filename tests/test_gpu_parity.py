@@ -229,6 +229,34 @@ def test_eight_wave_forward_staged_and_global_paths(dev, S, fin, fout, deg):
     close(m.weight.grad, wo.grad, what='g_weight')
 
 
+def test_register_staged_forward_through_the_raw_abi(dev, monkeypatch):
+    """The register-staged 8-wave kernel (fwd2) at S = 4 / 8, where the ring kernel (fwd3) is the default: reached only through
+    the C ABI, (a) by x rows that are not float4-addressable (ldx = Fin = 25; functional always pads them) and (b) in accumulate
+    mode (aligned x, out pre-filled: out0 + conv).  128-row records, N = 300: the third group is partial.  Both projections
+    (f16 pieces, the default, and bf16 pairs)."""
+    from gnn_matlang_amd import _lib, functional as Fn
+    from gnn_matlang_amd.graph import GraphCSR
+    from oracle import spect_conv_oracle as O
+    rng = np.random.default_rng(300)
+    torch.manual_seed(300)
+    N = 300
+    ei = _random_graph(rng, N, 5)
+    csr = GraphCSR.from_edge_index(T(ei).to(dev), N)
+    for S, fout in ((8, 30), (4, 9)):
+        ea = torch.randn(ei.shape[1], S)
+        val = csr.sort_values(ea.to(dev))
+        for fin, accum in ((25, False), (32, True)):
+            x, w, b, out0 = torch.randn(N, fin), torch.randn(S, fin, fout) / fin ** 0.5, torch.rand(fout) - 0.5, torch.randn(N, fout)
+            yo = O.spectconv_forward(x, T(ei), ea, w, b, False) + (out0 if accum else 0)
+            xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
+            for f16 in (True, False):
+                monkeypatch.setattr(Fn, 'FWD_F16', f16)
+                out = out0.to(dev) if accum else torch.full((N, fout), float('nan'), device=dev)
+                Fn._fused_conv(csr.rowptr, csr.col, csr.ginfo128, None, val, xd, fin, wd, (fin * fout, fout, 1), bd, out, fout, N,
+                               S, fin, fout, _lib.GML_GROUPS128 | (_lib.GML_ACCUM if accum else 0), 0)
+                close(out, yo, what='S=%d fin=%d accum=%s f16=%s' % (S, fin, accum, f16))
+
+
 @pytest.mark.parametrize('S,fin,fout,selfconn,depthwise', [(4, 1, 4, False, True), (4, 21, 30, False, True), (4, 3, 4, True, True),
                                                            (8, 32, 30, True, True), (8, 7, 16, False, True),
                                                            (4, 20, 30, True, False), (8, 32, 16, False, False)])

@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
-"""Is the device code of the conv-backward kernels the same as at <commit>?
+"""Is the device code of the conv kernels the same as at <commit>?
 
-    python tools/isa_same.py <commit> [--work DIR] [file.hip ...]
+    python tools/isa_same.py <commit> [--forward] [--kernels] [--work DIR] [file.hip ...]
 
 Compiles each source to gfx950 device assembly (the flags of gnn_matlang_amd/_build.py plus -S --cuda-device-only), once from
 `git archive <commit>` and once from the working tree, and compares the two files after dropping the lines that contain
 `__hip_cuid_` (a hash of the source text: the only thing that differs when dead code is deleted).  One line per file; exit
-status 1 when any differs.  Without file arguments: every gml_bwd*_fam_*.hip and gml_spectconv_bwd.hip that both trees have.
+status 1 when any differs.  Without file arguments: every gml_bwd*_fam_*.hip and gml_spectconv_bwd.hip that both trees have, or,
+with --forward, every gml_fwd*_fam*.hip and gml_spectconv.hip.
+--kernels compares kernel by kernel (a refactor that deletes SOME instantiations of a file): each assembly is cut at its kernel
+symbols, kernels that both sides have are compared, kernels that one side alone has are listed and are no difference.
 --work DIR keeps the assembly there and reuses <commit>'s side on the next call (a refactor in several steps)."""
 import argparse
 import glob
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -19,6 +23,8 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CSRC = os.path.join('gnn_matlang_amd', 'csrc')
+BACKWARD = ('gml_bwd*_fam*.hip', 'gml_spectconv_bwd.hip')
+FORWARD = ('gml_fwd*_fam*.hip', 'gml_spectconv.hip')
 
 
 def asm(tree, src, out):
@@ -31,13 +37,50 @@ def asm(tree, src, out):
     return [l for l in open(out) if '__hip_cuid_' not in l]
 
 
+_LOCAL = re.compile(r'(\.L|\b)(BB|func_begin|func_end|tmp)\d+(?=_|\b)')
+_NEXT = re.compile(r'\s*\.(protected|globl|weak|hidden|type|section\s+\.text)\b')
+_LABEL = re.compile(r'([A-Za-z_$][\w$.]*):')
+
+
+def kernels(lines):
+    """{kernel symbol: lines} of a device assembly: label .. kernel descriptor (up to the next symbol's directives) + its metadata
+    entry; the function index in local labels and comments, and the comment columns that move with it, are dropped."""
+    names = set(l.split()[1] for l in lines if l.lstrip().startswith('.amdhsa_kernel '))
+    out = {n: [] for n in names}
+    cur, closed, meta = None, False, None
+    for l in lines:
+        if l.startswith('amdhsa.kernels:'):
+            cur, meta = None, []
+            continue
+        if meta is not None:                                   # entries start with '  - .key', end at the next top-level key
+            if l.startswith('  - ') or not l.startswith(' '):
+                name = [m.split()[-1] for m in meta if m.strip().startswith('.name:')]
+                if name and name[0] in out:
+                    out[name[0]] += meta
+                meta = [] if l.startswith('  - ') else None
+            if meta is not None:
+                meta.append(l)
+            continue
+        label = _LABEL.match(l)
+        if label and label.group(1) in names:
+            cur, closed = label.group(1), False
+        elif cur and closed and _NEXT.match(l) and cur not in l:
+            cur = None
+        if cur:
+            out[cur].append(' '.join(_LOCAL.sub(lambda m: m.group(1) + m.group(2), l).split()))
+            closed = closed or l.lstrip().startswith('.end_amdhsa_kernel')
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('commit')
     ap.add_argument('--work', help='directory for the assembly files (kept; the side of <commit> is reused)')
     ap.add_argument('--jobs', type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument('--forward', action='store_true', help='default file list: the conv forward instead of the backward')
+    ap.add_argument('--kernels', action='store_true', help='compare kernel by kernel; list the kernels only one side has')
     ap.add_argument('files', nargs='*')
-    a = ap.parse_args()
+    a = ap.parse_intermixed_args()
     rev = subprocess.run(['git', '-C', ROOT, 'rev-parse', '--short', a.commit], capture_output=True, text=True, check=True).stdout.strip()
     tmp = None if a.work else tempfile.TemporaryDirectory()
     work = os.path.abspath(a.work) if a.work else tmp.name
@@ -48,7 +91,7 @@ def main():
         subprocess.run(['tar', '-x', '-C', base], stdin=ar.stdout, check=True)
         if ar.wait():
             raise RuntimeError('git archive %s failed' % rev)
-    files = a.files or sorted(os.path.basename(f) for pat in ('gml_bwd*_fam*.hip', 'gml_spectconv_bwd.hip')
+    files = a.files or sorted(os.path.basename(f) for pat in (FORWARD if a.forward else BACKWARD)
                               for f in glob.glob(os.path.join(ROOT, CSRC, pat)))
     files = [os.path.basename(f) for f in files]
     gone = [f for f in files if not os.path.exists(os.path.join(base, CSRC, f))]
@@ -59,15 +102,26 @@ def main():
         old_s = os.path.join(base, src[:-4] + '.s')
         old = [l for l in open(old_s) if '__hip_cuid_' not in l] if os.path.exists(old_s) else asm(base, src, old_s)
         new = asm(ROOT, src, os.path.join(work, 'new', src[:-4] + '.s'))
-        return src, old == new, len(old), len(new)
+        return src, old, new
 
     with ThreadPoolExecutor(a.jobs) as ex:
         res = list(ex.map(one, files))
-    for src, same, n_old, n_new in res:
-        print('%-28s %s  (%d lines at %s, %d now)' % (src, 'same' if same else 'DIFFERENT', n_old, rev, n_new))
+    bad = 0
+    for src, old, new in res:
+        if not a.kernels:
+            bad += old != new
+            print('%-28s %s  (%d lines at %s, %d now)' % (src, 'same' if old == new else 'DIFFERENT', len(old), rev, len(new)))
+            continue
+        ko, kn = kernels(old), kernels(new)
+        lists = (('DIFFERENT', sorted(k for k in set(ko) & set(kn) if ko[k] != kn[k])), ('only at ' + rev, sorted(set(ko) - set(kn))),
+                 ('only now', sorted(set(kn) - set(ko))))
+        bad += bool(lists[0][1])
+        print('%-28s %d kernels on both sides, %d differ; %d only at %s, %d only now' %
+              (src, len(set(ko) & set(kn)), len(lists[0][1]), len(lists[1][1]), rev, len(lists[2][1])))
+        for tag, ks in lists:
+            print(''.join('    %-14s %s\n' % (tag, k) for k in ks), end='')
     for f in gone:
         print('%-28s not at %s' % (f, rev))
-    bad = sum(not same for _, same, _, _ in res)
     print('%d of %d files differ from %s' % (bad, len(res), rev))
     if tmp:
         tmp.cleanup()
