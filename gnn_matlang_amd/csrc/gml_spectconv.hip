@@ -355,7 +355,8 @@ extern "C" int gml_spmm_fwd_ex(const int32_t* rowptr, const int32_t* col, const 
     // ring kernel (gml_spmm3_impl.h): any S (chunks of 4, 2, 1 supports), any Fin (chunks of 32 features), degrees up to ~16 per
     // row on average staged in LDS.  Shapes of the conv's 128-row class (plan_fwd) keep fwd2's NOB = 0 form, or the loop below, while
     // every group fits fwd2's 1024-edge staging (ZINC: 0.65 vs 0.61 of the roof at 131,072 graphs) or the group sizes are unknown (< 0)
-    const bool rows128 = plan_fwd(S, Fin, 16, 0).rows == 128;
+    const FwdPlan pl = plan_fwd(S, Fin, 16, 0);
+    const bool rows128 = pl.rows == 128;
     const bool fwd2_fits = rows128 && (((uintptr_t)val & 15) == 0) && (max_group_edges < 0 || max_group_edges <= GML_FWD2_ECAP);
     if (!fwd2_fits && ginfo128 != nullptr && epos == nullptr && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0) && Fin % 4 == 0 &&
         (((uintptr_t)h & 15) == 0) && (((uintptr_t)val & 3) == 0) && (num_rows + 16) * ldx * 4 < (int64_t)INT32_MAX &&
@@ -379,8 +380,10 @@ extern "C" int gml_spmm_fwd_ex(const int32_t* rowptr, const int32_t* col, const 
         }
         return GML_OK;
     }
-    if (ginfo128 != nullptr && epos == nullptr && rows128 && (((uintptr_t)val & 15) == 0) && (((uintptr_t)h & 15) == 0)) {
-        // the 8-wave kernel's staged, degree-ranked aggregation; H written straight from the accumulators
+    if (ginfo128 != nullptr && epos == nullptr && pl.staged && (((uintptr_t)val & 15) == 0) && (((uintptr_t)h & 15) == 0)) {
+        // the 8-wave kernel's staged, degree-ranked aggregation; H written straight from the accumulators.  pl.staged, not rows128:
+        // a lane of fwd2 holds features 8 kq .. 8 kq + 7 < 32, so S = 4 with 33 .. 48 features (128-row class through fwd4 alone)
+        // would leave H[:, :, 32:] unwritten on the S = 4 instantiation
         GmlFwdParams p = fwd_params(rowptr, col, ginfo128, nullptr, val, x, ldx, nullptr, 0, 0, 0, nullptr, nullptr, 0, num_rows, S, Fin, 16, 0);
         p.hout = h;
         p.ngroups = (int)gml_cdiv(num_rows, GML_FWD2_ROWS);

@@ -253,7 +253,9 @@ int gml_scatter_rows(const float* in, const int32_t* perm, float* out, int64_t r
  * rowptr/col: CSR keyed by the OUTPUT row (ginfo: gml_csr_group_info of it); pos(k) = epos ? epos[k] : k
  * (epos = NULL, i.e. values stored in the order of this CSR, is the fast path); val is [E, S] (S contiguous).
  * W element (s, i, o) lives at w[s*w_ss + i*w_si + o*w_so] so the transposed weights of the
- * backward pass need no copy.  bias may be NULL.  Used for: forward (CSR by target, x = X),
+ * backward pass need no copy.  bias may be NULL.  GML_ACCUM with GML_RELU: the activation sees the accumulated value,
+ * out = relu(out + sum + bias), on every kernel (the 64-row family's own support passes accumulate this way).
+ * Used for: forward (CSR by target, x = X),
  * d/dX (CSR by source, x = dOut, W transposed view, epos = pos_t). */
 /* group size (64 or 128) whose records the forward wants for this shape and arithmetic; 128 additionally needs
  * epos == NULL -- the caller then passes those records and GML_GROUPS128 */
