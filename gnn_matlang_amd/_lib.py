@@ -106,6 +106,7 @@ SIGNATURES = {
     'gml_gnnml1_bwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _i32,
                                       _p, _i64, _p, _i64, _p, _i64, _p]),
     'gml_edge_mlp_bwd_parts': (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    'gml_edge_mlp_plan': (_i32, [_i32, _i32, _i32, _i32, _u32]),
     'gml_edge_mlp_wide_fwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     'gml_edge_mlp_wide_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     'gml_edge_mlp_wide_bwd_h2r': (ctypes.c_int32, [_i32]),
@@ -188,6 +189,11 @@ GML_FWD_ONEWIN = 256
 GML_F16X3 = 1024                # gml_spectconv_fwd / gml_ml3_fwd, ring kernel: f16 (hi, lo) pieces under power-of-two scales
 GML_NO_FOLD = 512               # gml_spectconv_bwd*: leave the dW partials in ws (gml_fold_many)
 GML_FOLD_MAX_JOBS = 16
+# gml_edge_mlp_plan: direction, flags and the kernel families it answers (include/gml.h)
+GML_EDGE_FWD, GML_EDGE_BWD = 0, 1
+GML_EDGE_TWO_PIECE, GML_EDGE_THREE_PIECE, GML_EDGE_EXACT, GML_EDGE_HAS_SPLIT, GML_EDGE_WANT_GIN, GML_EDGE_DUAL, GML_EDGE_UNIQUE = 0, 1, 2, 4, 8, 16, 32
+(GML_EDGE_FAM_NONE, GML_EDGE_FAM_VALU, GML_EDGE_FAM_CHAIN, GML_EDGE_FAM_CHAIN16, GML_EDGE_FAM_CHAIN6, GML_EDGE_FAM_CHAIN16X6, GML_EDGE_FAM_SYM6,
+ GML_EDGE_FAM_SYM16X6, GML_EDGE_FAM_SYM_CHAIN, GML_EDGE_FAM_SYM_CHAIN16) = range(10)
 
 
 class AdamJob(ctypes.Structure):

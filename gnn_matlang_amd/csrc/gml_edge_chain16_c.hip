@@ -1,4 +1,3 @@
 // explicit instantiations of the matrix-core edge-branch kernels for 8 < S = Sout <= 16
 #include "gml_edge_chain16_impl.h"
-GML_DEFINE_EDGE_CHAIN16(13)
-GML_DEFINE_EDGE_CHAIN16(14)
+GML_ECHAIN16_S_C(GML_DEFINE_EDGE_CHAIN16)

@@ -16,6 +16,14 @@
 #pragma once
 #include "gml_edge_chain_impl.h"
 
+// the S = Sout each fam file instantiates (gml_edge_chain16_a.hip .. _d.hip); the three-piece forward and the unique-row forms of
+// 8 < S <= 16 walk the same list
+#define GML_ECHAIN16_S_A(X) X(9) X(10)
+#define GML_ECHAIN16_S_B(X) X(11) X(12)
+#define GML_ECHAIN16_S_C(X) X(13) X(14)
+#define GML_ECHAIN16_S_D(X) X(15) X(16)
+#define GML_ECHAIN16_S(X) GML_ECHAIN16_S_A(X) GML_ECHAIN16_S_B(X) GML_ECHAIN16_S_C(X) GML_ECHAIN16_S_D(X)
+
 template <int S>
 struct GmlChain16W {
     bf16x8 a1a[3][2], a1b[3][2];   // layer 1: [Whi | Whi] and [Wlo | 0] of W1..W3, row tiles 0 / 1
@@ -356,14 +364,6 @@ int gml_launch_edge_chain16_bwd(const uint32_t* es, const float* w1, const float
                                 const float* gout, float* dw1, float* dw2, float* dw3, float* dw4, int64_t E, void* ws,
                                 size_t ws_bytes, hipStream_t st);
 
-// persistent workgroups: 2 per CU (<= 256 VGPRs)
-static inline int64_t gml_edge_chain16_bwd_groups(int64_t E) {
-    const int64_t ntiles = gml_cdiv(E, 16);
-    int64_t grid = gml_cdiv(ntiles, 4);
-    if (grid > 2 * GML_NUM_CU) grid = 2 * GML_NUM_CU;
-    return grid < 1 ? 1 : grid;
-}
-
 #define GML_DEFINE_EDGE_CHAIN16(SV)                                                                              \
     template <>                                                                                                  \
     int gml_launch_edge_chain16_fwd<SV>(const uint32_t* es, const float* w1, const float* w2, const float* w3,   \
@@ -386,11 +386,5 @@ static inline int64_t gml_edge_chain16_bwd_groups(int64_t E) {
         if (ws_bytes < (size_t)grid * NW * sizeof(float)) return GML_E_WORKSPACE;                                \
         hipLaunchKernelGGL((gml_k_edge_chain16_bwd<SV>), dim3((unsigned)grid), dim3(256), 0, st, es, w1, w2,     \
                            w3, w4, gout, (float*)ws, E, ntiles);                                                 \
-        int rc = gml_launch_status();                                                                            \
-        if (rc != GML_OK) return rc;                                                                             \
-        if (!dw1) return GML_OK;   /* partials stay in ws: gml_fold_many */                                      \
-        const int n123 = 2 * SV * SV, n4 = SV * 4 * SV;                                                          \
-        hipLaunchKernelGGL(gml_k_reduce_partials, dim3((unsigned)gml_cdiv(NW, 16)), dim3(256), 0, st,            \
-                           (const float*)ws, grid, NW, dw1, n123, dw2, n123, dw3, n123, dw4, n4);                \
-        return gml_launch_status();                                                                              \
+        return gml_edge_fold_tail(ws, grid, SV, dw1, dw2, dw3, dw4, st);                                         \
     }

@@ -59,7 +59,7 @@ __device__ __forceinline__ void gml_chain16x6_load_weights(GmlChain16W6<S>& W, c
 // out [E, S]; out_t (optional): the same rows at tpos[e].  SYM (gml_edge_chain_sym_impl.h): tile entry u evaluates edge uid[u] and
 // stores the row to out[uid[u]] and out[mir[u]] (mir < 0: none); E is then the number of entries (tpos / out_t unused)
 // DEV (with SYM): the number of entries is *ucount, clamped to [0, E] (E = the capacity the grid was sized for)
-template <int S, bool TA, bool SYM = false, bool DEV = false>
+template <int S, bool SYM = false, bool DEV = false>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16x6_fwd(const float* __restrict__ ea, const float* __restrict__ w1,
                                                                   const float* __restrict__ w2, const float* __restrict__ w3,
                                                                   const float* __restrict__ w4, float* __restrict__ out,
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain16x6_fwd(const float* 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float t2, t3;
-                gml_tanh_pair_scaled<TA>(z[1][r], z[2][r], t2, t3);
+                gml_tanh_pair_scaled(z[1][r], z[2][r], t2, t3);
                 h1[rt][r] = gml_relu1(z[0][r]);
                 h23[rt][r] = t2 * t3;
             }
@@ -187,19 +187,11 @@ int gml_launch_edge_chain16x6_fwd_sym(const float* ea, const int32_t* uid, const
     const int64_t ntiles = gml_cdiv(U, 16);
     int64_t grid = gml_cdiv(ntiles, 8);
     if (grid > 2 * GML_NUM_CU) grid = 2 * GML_NUM_CU;
-    if (ucount) {                                               // U = capacity: the grid covers it, the kernel reads the count
-        if (gml_chain6_accurate_tanh())
-            hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out,
-                               nullptr, nullptr, U, ntiles, uid, mir, ucount);
-        else
-            hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, false, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out,
-                               nullptr, nullptr, U, ntiles, uid, mir, ucount);
-        return gml_launch_status();
-    }
-    if (gml_chain6_accurate_tanh())
-        hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, nullptr, nullptr, U, ntiles, uid, mir);
+    if (ucount)                                                 // U = capacity: the grid covers it, the kernel reads the count
+        hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out,
+                           nullptr, nullptr, U, ntiles, uid, mir, ucount);
     else
-        hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, false, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, nullptr, nullptr, U, ntiles, uid, mir);
+        hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, nullptr, nullptr, U, ntiles, uid, mir);
     return gml_launch_status();
 }
 
@@ -209,9 +201,6 @@ int gml_launch_edge_chain16x6_fwd(const float* ea, const float* w1, const float*
     const int64_t ntiles = gml_cdiv(E, 16);
     int64_t grid = gml_cdiv(ntiles, 8);
     if (grid > 2 * GML_NUM_CU) grid = 2 * GML_NUM_CU;
-    if (gml_chain6_accurate_tanh())
-        hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, tpos, out_t, E, ntiles);
-    else
-        hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S, false>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, tpos, out_t, E, ntiles);
+    hipLaunchKernelGGL((gml_k_edge_chain16x6_fwd<S>), dim3((unsigned)grid), dim3(256), 0, st, ea, w1, w2, w3, w4, out, tpos, out_t, E, ntiles);
     return gml_launch_status();
 }

@@ -21,6 +21,12 @@
 #pragma once
 #include "gml_edge_chain_impl.h"
 
+// S = Sout of the single-layer forward (gml_edge_chain6_a.hip; 8 < S <= 16: GML_ECHAIN16_S) and (S, layers) of the stacked one
+// (gml_edge_chain6_b.hip; the unique-row form, gml_edge_chain_sym.hip, adds GML_ESYM_SINGLES)
+#define GML_ECHAIN6_S(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#define GML_ECHAIN6_STACKS(X) X(8, 1) X(8, 2) X(8, 3) X(8, 4) X(4, 1) X(4, 2) X(4, 3) X(4, 4)
+#define GML_ESYM_SINGLES(X) X(2, 1) X(3, 1) X(5, 1) X(6, 1) X(7, 1)
+
 struct GmlOp3 { bf16x8 h, m, l; };
 
 // max(x, 0) as ONE instruction: non-negative floats order like their bit patterns and every negative one has the sign bit, so the signed
@@ -45,25 +51,23 @@ __device__ __forceinline__ GmlOp3 gml_wop3(const float (&v)[8]) {
     return o;
 }
 
-// tanh of two arguments that arrive pre-scaled by 2 log2(e) (z = x / k, k = ln(2) / 2).  TA: relative-accurate -- below |x| = 1/4 the odd
+// tanh of two arguments that arrive pre-scaled by 2 log2(e) (z = x / k, k = ln(2) / 2), relative-accurate: below |x| = 1/4 the odd
 // series of gml_tanh_small in the scaled argument, x + x^3 P(x^2) = z (k + w (b0 + w (b1 + w (b2 + w b3)))), w = z^2,
 // b_i = k^(2 i + 3) a_i, both values at once on the packed fp32 pipe (6 packed operations per pair; series error 8e-9 relative);
-// otherwise (and above 1/4) the short form 1 - 2 / (e^2x + 1), ~2e-7 ABSOLUTE
-template <bool TA>
+// above 1/4 the short form 1 - 2 / (e^2x + 1), ~2e-7 ABSOLUTE -- which alone (the two-piece chain's tanh) is what would be left of
+// the branch's error once the products are exact
 __device__ __forceinline__ void gml_tanh_pair_scaled(float z2, float z3, float& t2, float& t3) {
     t2 = fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(z2) + 1.f), 1.f);
     t3 = fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(z3) + 1.f), 1.f);
-    if constexpr (TA) {
-        const f32x2 zz = f32x2{z2, z3};
-        const f32x2 w = zz * zz;
-        f32x2 q = w * 1.5776033314321529e-06f - 3.241205933362716e-05f;     // b3 = k^9 62/2835, b2 = -k^7 17/315
-        q = q * w + 6.666779073214221e-04f;                               // b1 = k^5 2/15
-        q = q * w - 1.3876027166205392e-02f;                              // b0 = -k^3 / 3
-        q = q * w + 0.34657359027997264f;                                 // k
-        q = q * zz;
-        t2 = fabsf(z2) < 0.7213475f ? q.x : t2;
-        t3 = fabsf(z3) < 0.7213475f ? q.y : t3;
-    }
+    const f32x2 zz = f32x2{z2, z3};
+    const f32x2 w = zz * zz;
+    f32x2 q = w * 1.5776033314321529e-06f - 3.241205933362716e-05f;     // b3 = k^9 62/2835, b2 = -k^7 17/315
+    q = q * w + 6.666779073214221e-04f;                               // b1 = k^5 2/15
+    q = q * w - 1.3876027166205392e-02f;                              // b0 = -k^3 / 3
+    q = q * w + 0.34657359027997264f;                                 // k
+    q = q * zz;
+    t2 = fabsf(z2) < 0.7213475f ? q.x : t2;
+    t3 = fabsf(z3) < 0.7213475f ? q.y : t3;
 }
 
 template <int S>
@@ -130,9 +134,8 @@ __device__ __forceinline__ void gml_chain6_b1(const float (&e)[8], int g, bf16x8
     BB = gml_op(b[0], b[1], b[2], b[3]);
 }
 
-// out (pre-activation, rows q = 4 (g & 1) + r) of one tile.  TA: relative-accurate tanh (series below 1/4, as gml_tanh) instead of the
-// short form 1 - 2 / (e^2x + 1), whose ~2e-7 ABSOLUTE error is what is left of the branch's error once the products are exact
-template <int S, bool TA, bool RES>
+// out (pre-activation, rows q = 4 (g & 1) + r) of one tile
+template <int S>
 __device__ __forceinline__ f32x4 gml_chain6_forward(const GmlChain6W<S>& W, const GmlNegI& negI, const bf16x8 BA, const bf16x8 BB) {
     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 z[3];
@@ -142,21 +145,13 @@ __device__ __forceinline__ f32x4 gml_chain6_forward(const GmlChain6W<S>& W, cons
 #pragma unroll
     for (int r = 0; r < 4; ++r) {                            // z[1], z[2] arrive pre-scaled by 2 log2(e): z = x / k, k = ln(2) / 2
         float t2, t3;
-        gml_tanh_pair_scaled<TA>(z[1][r], z[2][r], t2, t3);
+        gml_tanh_pair_scaled(z[1][r], z[2][r], t2, t3);
         h[r] = gml_relu1(z[0][r]);
         h[4 + r] = t2 * t3;
     }
-    bf16x8 Bh, Bm, Bl;                                       // (h1 pair, h1 pair, h23 pair, h23 pair) of each piece
-    if constexpr (RES) {
-        u32x4 ph, pm, pl;
-        gml_split3_tiles(negI, f32x4{h[0], h[1], h[2], h[3]}, f32x4{h[4], h[5], h[6], h[7]}, ph, pm, pl);
-        Bh = __builtin_bit_cast(bf16x8, ph); Bm = __builtin_bit_cast(bf16x8, pm); Bl = __builtin_bit_cast(bf16x8, pl);
-    } else {
-        uint32_t hh[4], hm[4], hl[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gml_split3_pair(h[2 * j], h[2 * j + 1], hh[j], hm[j], hl[j]);
-        Bh = gml_op(hh[0], hh[1], hh[2], hh[3]); Bm = gml_op(hm[0], hm[1], hm[2], hm[3]); Bl = gml_op(hl[0], hl[1], hl[2], hl[3]);
-    }
+    u32x4 ph, pm, pl;                                        // (h1 pair, h1 pair, h23 pair, h23 pair) of each piece
+    gml_split3_tiles(negI, f32x4{h[0], h[1], h[2], h[3]}, f32x4{h[4], h[5], h[6], h[7]}, ph, pm, pl);
+    const bf16x8 Bh = __builtin_bit_cast(bf16x8, ph), Bm = __builtin_bit_cast(bf16x8, pm), Bl = __builtin_bit_cast(bf16x8, pl);
     f32x4 o = GML_MFMA(W.a2[2], Bh, zero);
     o = GML_MFMA(W.a2[1], Bm, o);
     o = GML_MFMA(W.a2[0], Bl, o);
@@ -164,10 +159,6 @@ __device__ __forceinline__ f32x4 gml_chain6_forward(const GmlChain6W<S>& W, cons
     o = GML_MFMA(W.a2[0], Bm, o);
     return GML_MFMA(W.a2[0], Bh, o);
 }
-
-#ifndef GML_CHAIN6_RES
-#define GML_CHAIN6_RES true
-#endif
 
 template <int L>
 struct GmlChain6Stack {
@@ -177,7 +168,7 @@ struct GmlChain6Stack {
 
 // L layers' edge branches over the SAME raw supports in one pass (L = 1: the single-layer forward, optionally with the second,
 // scattered copy out_t[tpos[e]] = out[e] of the dual-order scheme)
-template <int S, int L, bool DUAL, bool TA>
+template <int S, int L, bool DUAL>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd(const float* __restrict__ ea, const GmlChain6Stack<L> a,
                                                                const int32_t* __restrict__ tpos, float* __restrict__ out_t,
                                                                int64_t E, int64_t ntiles) {
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd(const float* __r
         for (int l = 0; l < L; ++l) {
             f32x4 o[2];
 #pragma unroll
-            for (int u = 0; u < 2; ++u) o[u] = gml_chain6_forward<S, TA, GML_CHAIN6_RES>(W[l], negI, BA[u], BB[u]);
+            for (int u = 0; u < 2; ++u) o[u] = gml_chain6_forward<S>(W[l], negI, BA[u], BB[u]);
             // lane groups 0,1 hold q = 0..3 / 4..7 and write `out`; groups 2,3 hold the same rows again and (DUAL) write the second,
             // source-sorted copy at tpos[e]; the range check of the descriptor drops edges past E
             const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.out[l]) + (((uint64_t)thi << 32) | tlo), 0, nrec, 0x00020000);
@@ -281,27 +272,18 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd(const float* __r
     }
 }
 
-// GML_CHAIN6_TANH=0 in the environment: the short tanh (A/B)
-static inline bool gml_chain6_accurate_tanh() {
-    static const bool v = [] { const char* e = getenv("GML_CHAIN6_TANH"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 template <int S, int L>
 int gml_launch_edge_chain6_fwd(const float* ea, const GmlChain6Stack<L>& a, const int32_t* tpos, float* out_t, int64_t E, hipStream_t st) {
     const int64_t ntiles = gml_cdiv(E, 16);
     int64_t grid = gml_cdiv(ntiles, 8);
     if (grid > 4 * GML_NUM_CU) grid = 4 * GML_NUM_CU;
     const dim3 gd((unsigned)grid), bd(256);
-    const bool ta = gml_chain6_accurate_tanh();
     if constexpr (L == 1) {
         if (out_t != nullptr) {
-            if (ta) hipLaunchKernelGGL((gml_k_edge_chain6_fwd<S, 1, true, true>), gd, bd, 0, st, ea, a, tpos, out_t, E, ntiles);
-            else hipLaunchKernelGGL((gml_k_edge_chain6_fwd<S, 1, true, false>), gd, bd, 0, st, ea, a, tpos, out_t, E, ntiles);
+            hipLaunchKernelGGL((gml_k_edge_chain6_fwd<S, 1, true>), gd, bd, 0, st, ea, a, tpos, out_t, E, ntiles);
             return gml_launch_status();
         }
     }
-    if (ta) hipLaunchKernelGGL((gml_k_edge_chain6_fwd<S, L, false, true>), gd, bd, 0, st, ea, a, tpos, out_t, E, ntiles);
-    else hipLaunchKernelGGL((gml_k_edge_chain6_fwd<S, L, false, false>), gd, bd, 0, st, ea, a, tpos, out_t, E, ntiles);
+    hipLaunchKernelGGL((gml_k_edge_chain6_fwd<S, L, false>), gd, bd, 0, st, ea, a, tpos, out_t, E, ntiles);
     return gml_launch_status();
 }

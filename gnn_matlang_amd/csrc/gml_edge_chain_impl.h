@@ -19,8 +19,14 @@
 // K = 32 operands of  dW += [h1; h23; gz1; gz2; gz3]^T-tiles x [go | e]^T-tile,  accumulated in registers over
 // the wave's whole edge range; one partial per workgroup, folded by gml_k_reduce_partials in fixed order.
 #pragma once
-#include "gml_common.h"
+#include "gml_edge_plan.h"
 
+// the S = Sout each fam file instantiates (gml_edge_chain_a.hip, _b.hip); declarations and launch ladders derive from the same lists
+#define GML_ECHAIN_S_A(X) X(1) X(2) X(3) X(4)
+#define GML_ECHAIN_S_B(X) X(5) X(6) X(7) X(8)
+#define GML_ECHAIN_S(X) GML_ECHAIN_S_A(X) GML_ECHAIN_S_B(X)
+// (S, layers) of the stacked forward (gml_edge_chain_e.hip)
+#define GML_ECHAIN_STACKS(X) X(8, 2) X(8, 3) X(8, 4) X(4, 2) X(4, 3) X(4, 4)
 
 __device__ __forceinline__ uint32_t gml_pack2(float a, float b) {           // v_cvt_pk_bf16_f32 (RNE)
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
@@ -190,24 +196,8 @@ __device__ __forceinline__ void gml_chain_forward(const GmlChainW<S>& W, GmlChai
     f32x4 h1, h23;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {                            // z2, z3 arrive pre-scaled by 2 log2(e)
-#if defined(GML_EABL) && (GML_EABL & 4)
-        T.t2[r] = z2[r]; T.t3[r] = z3[r];
-#else
-#if defined(GML_CHAIN_TANH) && GML_CHAIN_TANH == 1
-        // experiment (round 5): relative-accurate tanh in the chain (series below 1/4, (e - 1) / (e + 1) above): the learned supports'
-        // error 4.6e-7 -> 4.0e-7 rms (the bf16 splits dominate it), edge forward 0.89 -> 1.45, backward 2.02 -> 2.52 ms/step: not taken
-        {
-            const float x2_ = z2[r] * 0.34657359027997264f, x3_ = z3[r] * 0.34657359027997264f;   // back from the 2 log2(e) scale
-            const float e2_ = __builtin_amdgcn_exp2f(z2[r]), e3_ = __builtin_amdgcn_exp2f(z3[r]);
-            const float b2_ = (e2_ - 1.f) * __builtin_amdgcn_rcpf(e2_ + 1.f), b3_ = (e3_ - 1.f) * __builtin_amdgcn_rcpf(e3_ + 1.f);
-            T.t2[r] = fabsf(x2_) < 0.25f ? gml_tanh_small(x2_) : (e2_ > 3.0e38f ? 1.f : b2_);
-            T.t3[r] = fabsf(x3_) < 0.25f ? gml_tanh_small(x3_) : (e3_ > 3.0e38f ? 1.f : b3_);
-        }
-#else
         T.t2[r] = fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(z2[r]) + 1.f), 1.f);
         T.t3[r] = fmaf(-2.f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(z3[r]) + 1.f), 1.f);
-#endif
-#endif
         h1[r] = fmaxf(T.z1[r], 0.f);
         h23[r] = T.t2[r] * T.t3[r];
     }
@@ -310,17 +300,8 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain_fwd(const float* __re
                 const f32x4 v = f32x4{fmaxf(T[u].out[0], 0.f), fmaxf(T[u].out[1], 0.f), fmaxf(T[u].out[2], 0.f),
                                       fmaxf(T[u].out[3], 0.f)};
                 const bool q_ok = q0 < S;
-#ifndef GML_FABL
-#define GML_FABL 0
-#endif
-#if !(GML_FABL & 2)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_o, q_ok ? off_o : (int)0xffffff00, 0, /*nt: written once, read by the next kernel from HBM anyway*/ 2);
-#else
-                asm volatile("" :: "v"(v));
-#endif
-#if !(GML_FABL & 1)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_t, q_ok ? off_t : (int)0xffffff00, 0, 0);
-#endif
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -352,6 +333,15 @@ struct GmlChainStack {
     const float* w1[L]; const float* w2[L]; const float* w3[L]; const float* w4[L];
     float* out[L];
 };
+
+// the kernel argument of a stacked forward (GmlChainStack, GmlChain6Stack) from the entry points' host pointer arrays
+template <class Stack>
+static inline Stack gml_chain_stack_args(int L, const float* const* w1, const float* const* w2, const float* const* w3,
+                                         const float* const* w4, float* const* out) {
+    Stack a;
+    for (int l = 0; l < L; ++l) { a.w1[l] = w1[l]; a.w2[l] = w2[l]; a.w3[l] = w3[l]; a.w4[l] = w4[l]; a.out[l] = out[l]; }
+    return a;
+}
 
 template <int S, int L>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain_fwd_stack(const uint32_t* __restrict__ es, const GmlChainStack<L> a,
@@ -432,7 +422,7 @@ template <int S, bool GIN>
 struct GmlChainWB {
     bf16x8 a3[2];             // W4^T blocks (h1 part, h23 part): k = q, groups 0,1 hi / 2,3 lo, slots [q | q]
     bf16x8 a5[GIN ? 4 : 1];   // [W1|W2|W3]^T operands for d e: [H1|H2], [L1|L2], [H3|0], [L3|0]
-    bf16x8 bIh, bIl;          // [I ; 0] and [0 ; I]: transposes of the hi / the lo image of a split tile
+    bf16x8 bIh, bIl;          // [I ; 0] and [0 ; I] (a transposition on the matrix cores: unused since the LDS one; without them S = 8 is scheduled differently)
     bf16x8 aE;                // rows 8..15 <- hi + lo of the pre-split supports (e rows of the [go | e] tile, exact)
 };
 
@@ -537,18 +527,6 @@ __global__ __launch_bounds__(256, 3) void gml_k_edge_chain_bwd(
     f32x4 acc[5];
 #pragma unroll
     for (int b = 0; b < 5; ++b) acc[b] = zero;
-
-    // transposed split tiles: lane (channel = c16, g) gets [hi | lo] of edges 4g..4g+3 -- exact, the transposed values
-    // are bf16 numbers, so the repack is a plain conversion.  The operands are the pair tuples as they are:
-    // [I ; 0] selects the first tile of a tuple, [0 ; I] the second.
-    auto repack = [&](const f32x4 th, const f32x4 tl) -> bf16x8 {
-        return gml_op(gml_pack2(th[0], th[1]), gml_pack2(th[2], th[3]), gml_pack2(tl[0], tl[1]), gml_pack2(tl[2], tl[3]));
-    };
-    auto transpose_pair = [&](const u32x4 hi, const u32x4 lo, bf16x8& xa, bf16x8& xb) {
-        const bf16x8 H = __builtin_bit_cast(bf16x8, hi), L = __builtin_bit_cast(bf16x8, lo);
-        xa = repack(GML_MFMA(H, WB.bIh, zero), GML_MFMA(L, WB.bIh, zero));
-        xb = repack(GML_MFMA(H, WB.bIl, zero), GML_MFMA(L, WB.bIl, zero));
-    };
 
     const int64_t stride = (int64_t)gridDim.x * 4;
     int64_t t = (int64_t)blockIdx.x * 4 + wave;
@@ -673,24 +651,10 @@ __global__ __launch_bounds__(256, 3) void gml_k_edge_chain_bwd(
         }
         // weight gradients of the 16 edges: k-slots (g, j < 4) = hi, (g, j >= 4) = lo of edge 4g + (j & 3);
         //   X.[Yh | Yh] = Xh Yh + Xl Yh ,  X.[Yl | 0] = Xh Yl
-#ifndef GML_EABL
-#define GML_EABL 0
-#endif
-#if GML_EABL & 2
-        asm volatile("" :: "v"(T.hh), "v"(T.hl), "v"(g12h), "v"(g12l), "v"(g3yh), "v"(g3yl));
-        if (false) {
-#else
-        {
-#endif
         bf16x8 XT[5], YTb;
-#ifdef GML_EDGE_MFMA_TRANSPOSE
-        transpose_pair(T.hh, T.hl, XT[0], XT[1]);            // h1, h23
-        transpose_pair(g12h, g12l, XT[2], XT[3]);            // gz1, gz2
-        transpose_pair(g3yh, g3yl, XT[4], YTb);              // gz3, [go | e]
-#else
         // The split tiles are bf16 pairs already (lane (edge, g): channels 4g..4g+3 = 8 bytes per image): written as
         // [edge][channel] images (swizzled, see tr_wo) to the wave's LDS scratch and read back with ds_read_b64_tr_b16, lane (channel, g) receives
-        // edges 4g..4g+3 -- the same operands as the matrix-core transposes, without their 12 MFMAs and 24 conversions
+        // edges 4g..4g+3 -- the operands a transposition on the matrix cores would give, without its 12 MFMAs and 24 conversions
         // (an MFMA holds the VALU issue port for 8 cycles, tools/probes/probe_overlap.hip: this kernel is issue-bound).
         // One wave, in-order LDS queue: no barrier.
         {
@@ -708,20 +672,13 @@ __global__ __launch_bounds__(256, 3) void gml_k_edge_chain_bwd(
             YTb = gml_tr_frag(trw + 10 * 512 + tr_ro, trw + 11 * 512 + tr_ro);
             __builtin_amdgcn_wave_barrier();
         }
-#endif
         const u32x4 YT = __builtin_bit_cast(u32x4, YTb);
         const bf16x8 Bhh = gml_op(YT.x, YT.y, YT.x, YT.y);
         const bf16x8 Bl0 = gml_op(YT.z, YT.w, 0u, 0u);
-#if GML_EABL & 1
-#pragma unroll
-        for (int b = 0; b < 5; ++b) asm volatile("" :: "v"(XT[b]), "v"(Bl0), "v"(Bhh));
-#else
 #pragma unroll
         for (int b = 0; b < 5; ++b) {
             acc[b] = GML_MFMA(XT[b], Bl0, acc[b]);
             acc[b] = GML_MFMA(XT[b], Bhh, acc[b]);
-        }
-#endif
         }
         if constexpr (PRE) {
             __builtin_amdgcn_sched_barrier(0);
@@ -758,22 +715,6 @@ int gml_launch_edge_chain_bwd(const float* ea, const uint32_t* es, const float* 
                               const float* gout, float* gin, float* dw1, float* dw2, float* dw3, float* dw4,
                               int64_t E, void* ws, size_t ws_bytes, hipStream_t st);
 
-__global__ void gml_k_reduce_partials(const float* __restrict__ partial, int64_t nwaves, int nw,
-                                      float* __restrict__ d0, int n0, float* __restrict__ d1, int n1,
-                                      float* __restrict__ d2, int n2, float* __restrict__ d3, int n3);
-
-// persistent workgroups per CU (GML_EDGE_BWD_WGS, 1..6: 24.5 KB of LDS each); the workspace is sized for the maximum
-static inline int gml_edge_chain_bwd_wgs() {
-    static const int v = [] { const char* e = getenv("GML_EDGE_BWD_WGS"); const int n = e ? atoi(e) : 6; return n < 1 ? 1 : (n > 6 ? 6 : n); }();
-    return v;
-}
-static inline int64_t gml_edge_chain_bwd_groups(int64_t E, int wgs_per_cu = 8) {
-    const int64_t ntiles = gml_cdiv(E, 16);
-    int64_t grid = gml_cdiv(ntiles, 4);
-    if (grid > wgs_per_cu * GML_NUM_CU) grid = wgs_per_cu * GML_NUM_CU;
-    return grid < 1 ? 1 : grid;
-}
-
 #define GML_DEFINE_EDGE_CHAIN(SV)                                                                               \
     template <>                                                                                                 \
     int gml_launch_edge_chain_fwd<SV>(const float* ea, const uint32_t* es, const float* w1, const float* w2,    \
@@ -781,8 +722,7 @@ static inline int64_t gml_edge_chain_bwd_groups(int64_t E, int wgs_per_cu = 8) {
                                       float* out_t, int64_t E, hipStream_t st) {                                \
         const int64_t ntiles = gml_cdiv(E, 16);                                                                 \
         int64_t grid = gml_cdiv(ntiles, 8);                                                                     \
-        static const int fw = [] { const char* e = getenv("GML_EDGE_FWD_WGS"); const int n = e ? atoi(e) : 6; return n < 1 ? 1 : n; }();  \
-        if (grid > fw * GML_NUM_CU) grid = fw * GML_NUM_CU;   /* all resident at 70 VGPRs; 4..8 measured within 2 % */   \
+        if (grid > 6 * GML_NUM_CU) grid = 6 * GML_NUM_CU;     /* all resident at 70 VGPRs; 4..8 measured within 2 % */   \
         if (es != nullptr)                                                                                      \
             hipLaunchKernelGGL((gml_k_edge_chain_fwd<SV, true>), dim3((unsigned)grid), dim3(256), 0, st, ea,    \
                                es, w1, w2, w3, w4, out, tpos, out_t, E, ntiles);                                \
@@ -797,7 +737,7 @@ static inline int64_t gml_edge_chain_bwd_groups(int64_t E, int wgs_per_cu = 8) {
                                       float* dw1, float* dw2, float* dw3, float* dw4, int64_t E, void* ws,      \
                                       size_t ws_bytes, hipStream_t st) {                                        \
         const int64_t ntiles = gml_cdiv(E, 16);                                                                 \
-        const int64_t grid = gml_edge_chain_bwd_groups(E, gml_edge_chain_bwd_wgs());                                                  \
+        const int64_t grid = gml_edge_chain_bwd_groups(E);                                                      \
         constexpr int NW = GML_CHAIN_NW(SV);                                                                    \
         if (ws_bytes < (size_t)grid * NW * sizeof(float)) return GML_E_WORKSPACE;                               \
         const dim3 gd((unsigned)grid), bd(256);                                                                 \
@@ -814,11 +754,5 @@ static inline int64_t gml_edge_chain_bwd_groups(int64_t E, int wgs_per_cu = 8) {
         else                                                                                                    \
             hipLaunchKernelGGL((gml_k_edge_chain_bwd<SV, false, false>), gd, bd, 0, st, ea, es, w1, w2, w3, w4, \
                                gout, gin, wsf, E, ntiles);                                                      \
-        int rc = gml_launch_status();                                                                           \
-        if (rc != GML_OK) return rc;                                                                            \
-        if (!dw1) return GML_OK;   /* partials stay in ws: gml_fold_many */                                     \
-        const int n123 = 2 * SV * SV, n4 = SV * 4 * SV;                                                         \
-        hipLaunchKernelGGL(gml_k_reduce_partials, dim3((unsigned)gml_cdiv(NW, 16)), dim3(256), 0, st,           \
-                           (const float*)ws, grid, NW, dw1, n123, dw2, n123, dw3, n123, dw4, n4);               \
-        return gml_launch_status();                                                                             \
+        return gml_edge_fold_tail(ws, grid, SV, dw1, dw2, dw3, dw4, st);                                        \
     }

@@ -16,16 +16,10 @@
 #pragma once
 #include "gml_edge_chain6_impl.h"
 
-// cache policy of the forward's output stores: 0 = default (write-back).  The plain forward streams its rows out with nt (2); here the
+// The forward's output stores use the default cache policy (write-back).  The plain forward streams its rows out with nt; here the
 // mirror's row is a second, scattered 32-byte store into a line a later entry completes -- keeping the lines in the L2 until they are
-// full measured 1.15 vs 1.28 ms per step for the four-layer forward (profiles/r06_d_edge_sym_ab.log)
-#ifndef GML_SYM_ST_AUX
-#define GML_SYM_ST_AUX 0
-#endif
-// workgroups per CU of the backward (launch bound): 3 = 150 VGPRs, no spills; 4 = 128 VGPRs + 8 spilled: 1.83 vs 1.45 ms per step
-#ifndef GML_SYM_BWD_WGS
-#define GML_SYM_BWD_WGS 3
-#endif
+// full measured 1.15 vs 1.28 ms per step for the four-layer forward (profiles/r06_d_edge_sym_ab.log).
+// The backward is bound to 3 workgroups per CU: 150 VGPRs, no spills (4 = 128 VGPRs + 8 spilled: 1.83 vs 1.45 ms per step).
 
 // flag / mirror of every edge of the SOURCE-keyed view (row r = source, col_t = targets ascending inside a row).  2^LPS lanes share a
 // source row and deal its edges (the row is known without a search; ZINC-like rows hold ~6 edges: 4 lanes per row), the mirror is
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(256) void gml_k_edge_sym_flags(const int32_t* __res
 // entry u: uid[u] = the edge to evaluate, mir[u] = its mirror (-1: none).  out[l][uid] and out[l][mir] receive the row.
 // DEV: the number of entries is *ucount (read here, clamped to [0, U]; U = the capacity the grid was sized for) -- the list of a batch
 // assembled on the device (gml_batch_assemble_any), whose length the host never reads
-template <int S, int L, bool TA, bool DEV = false>
+template <int S, int L, bool DEV = false>
 __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd_sym(const float* __restrict__ ea, const int32_t* __restrict__ uid,
                                                                    const int32_t* __restrict__ mir, const GmlChain6Stack<L> a,
                                                                    int64_t E, int64_t U, int64_t ntiles,
@@ -158,22 +152,22 @@ __global__ __launch_bounds__(256, 2) void gml_k_edge_chain6_fwd_sym(const float*
         for (int l = 0; l < L; ++l) {
             f32x4 o[2];
 #pragma unroll
-            for (int v = 0; v < 2; ++v) o[v] = gml_chain6_forward<S, TA, GML_CHAIN6_RES>(W[l], negI, BA[v], BB[v]);
+            for (int v = 0; v < 2; ++v) o[v] = gml_chain6_forward<S>(W[l], negI, BA[v], BB[v]);
             const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(a.out[l], 0, (int)(uint32_t)(E * S * 4), 0x00020000);
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
                 const f32x4 x = f32x4{gml_relu1(o[v][0]), gml_relu1(o[v][1]), gml_relu1(o[v][2]), gml_relu1(o[v][3])};
                 const int off = (st_c[v] >= 0 && q0 < S) ? (st_c[v] * S + q0) * 4 : OOB;
                 if constexpr (S % 4 == 0) {
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs_o, off, 0, GML_SYM_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs_o, off, 0, 0);
                 } else if constexpr (S == 6) {                   // rows of 24 bytes: columns 0..3 as one 16-byte store (dword-aligned: enough for a
                     typedef uint32_t u32x2_ __attribute__((ext_vector_type(2)));                      // buffer store), columns 4, 5 as one 8-byte store
-                    if (q0 == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs_o, off, 0, GML_SYM_ST_AUX);
-                    else __builtin_amdgcn_raw_buffer_store_b64(u32x2_{__float_as_uint(x[0]), __float_as_uint(x[1])}, rs_o, off, 0, GML_SYM_ST_AUX);
+                    if (q0 == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs_o, off, 0, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b64(u32x2_{__float_as_uint(x[0]), __float_as_uint(x[1])}, rs_o, off, 0, 0);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x[r]), rs_o, (q0 + r < S && off != OOB) ? off + 4 * r : OOB, 0, GML_SYM_ST_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x[r]), rs_o, (q0 + r < S && off != OOB) ? off + 4 * r : OOB, 0, 0);
                 }
             }
         }
@@ -195,19 +189,11 @@ int gml_launch_edge_chain6_fwd_sym(const float* ea, const int32_t* uid, const in
     const int64_t ntiles = gml_cdiv(U, 16);
     int64_t grid = gml_cdiv(ntiles, 8);
     if (grid > 4 * GML_NUM_CU) grid = 4 * GML_NUM_CU;
-    if (ucount) {                                            // U = capacity: the grid covers it, the kernel reads the count
-        if (gml_chain6_accurate_tanh())
-            hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, true, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U,
-                               ntiles, ucount);
-        else
-            hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, false, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U,
-                               ntiles, ucount);
-        return gml_launch_status();
-    }
-    if (gml_chain6_accurate_tanh())
-        hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U, ntiles);
+    if (ucount)                                              // U = capacity: the grid covers it, the kernel reads the count
+        hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, true>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U,
+                           ntiles, ucount);
     else
-        hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L, false>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U, ntiles);
+        hipLaunchKernelGGL((gml_k_edge_chain6_fwd_sym<S, L>), dim3((unsigned)grid), dim3(256), 0, st, ea, uid, mir, a, E, U, ntiles);
     return gml_launch_status();
 }
 
@@ -217,7 +203,7 @@ int gml_launch_edge_chain6_fwd_sym(const float* ea, const int32_t* uid, const in
 // partial-sum layout [dw1 | dw2 | dw3 | dw4] per workgroup.
 // DEV: the entry count is *ucount (clamped to [0, U]), as in gml_k_edge_chain6_fwd_sym; every workgroup still writes its partial row
 template <int S, bool DEV = false>
-__global__ __launch_bounds__(256, GML_SYM_BWD_WGS) void gml_k_edge_chain_bwd_sym(
+__global__ __launch_bounds__(256, 3) void gml_k_edge_chain_bwd_sym(
     const uint32_t* __restrict__ es, const int32_t* __restrict__ uid, const int32_t* __restrict__ mir, const float* __restrict__ w1,
     const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ w4, const float* __restrict__ gout,
     float* __restrict__ partial, int64_t U, int64_t ntiles, const int32_t* __restrict__ ucount = nullptr) {

@@ -2,16 +2,9 @@
 #include "gml_edge_mlp_impl.h"
 #include "gml_edge_chain_impl.h"
 #include "gml_edge_chain16_impl.h"
-#include <stdlib.h>
 
-// 2 <= S <= 8 runs on the bf16 matrix cores (gml_edge_chain_impl.h); GML_EDGE_VALU=1 in the environment keeps the
-// one-edge-per-lane fp32 VALU kernels for every S (ablation / exact-fp32 arithmetic).  S = 1 stays on the VALU
-// kernels: its contractions are single products, so the split's 2^-17 rounding is not averaged over a sum (measured
-// 5e-5 .. 1e-4 of the output scale against 1e-5 for S >= 2), and there is no arithmetic to save.
-static bool emlp_use_chain(int S) {
-    static const bool valu = [] { const char* e = getenv("GML_EDGE_VALU"); return e && e[0] == '1'; }();
-    return S >= 2 && S <= 8 && !valu;
-}
+// Which family a call takes: gml_edge_plan.h.  The launchers are instantiated in the fam files (gml_edge_chain_a/b, gml_edge_chain16_a..d,
+// gml_edge_mlp_a..f) from the same S lists as the ladders below.
 #define GML_DECL_ECHAIN(SV)                                                                                  \
     template <> int gml_launch_edge_chain_fwd<SV>(const float*, const uint32_t*, const float*, const float*, \
                                                   const float*, const float*, float*, const int32_t*, float*, \
@@ -19,34 +12,31 @@ static bool emlp_use_chain(int S) {
     template <> int gml_launch_edge_chain_bwd<SV>(const float*, const uint32_t*, const float*, const float*, \
                                                   const float*, const float*, const float*, float*, float*,  \
                                                   float*, float*, float*, int64_t, void*, size_t, hipStream_t);
-GML_DECL_ECHAIN(1) GML_DECL_ECHAIN(2) GML_DECL_ECHAIN(3) GML_DECL_ECHAIN(4)
-GML_DECL_ECHAIN(5) GML_DECL_ECHAIN(6) GML_DECL_ECHAIN(7) GML_DECL_ECHAIN(8)
-// 8 < S <= 16 (counting.py: S = 12): the K = 16-slot chain of gml_edge_chain16_impl.h; needs the 64-byte pre-split rows and
-// produces no gradient for the raw supports (those cases stay on the VALU kernels)
-static bool emlp_use_chain16(int S, const void* ea_split, const void* gin) {
-    static const bool valu = [] { const char* e = getenv("GML_EDGE_VALU"); return e && e[0] == '1'; }();
-    return S > 8 && S <= 16 && !valu && ea_split != nullptr && gin == nullptr;
-}
+GML_ECHAIN_S(GML_DECL_ECHAIN)
 #define GML_DECL_ECHAIN16(SV)                                                                                \
     template <> int gml_launch_edge_chain16_fwd<SV>(const uint32_t*, const float*, const float*, const float*, \
                                                     const float*, float*, const int32_t*, float*, int64_t, hipStream_t); \
     template <> int gml_launch_edge_chain16_bwd<SV>(const uint32_t*, const float*, const float*, const float*, \
                                                     const float*, const float*, float*, float*, float*, float*, \
                                                     int64_t, void*, size_t, hipStream_t);
-GML_DECL_ECHAIN16(9) GML_DECL_ECHAIN16(10) GML_DECL_ECHAIN16(11) GML_DECL_ECHAIN16(12)
-GML_DECL_ECHAIN16(13) GML_DECL_ECHAIN16(14) GML_DECL_ECHAIN16(15) GML_DECL_ECHAIN16(16)
-#define GML_ECHAIN16_SWITCH(CALL)                                                               \
-    switch (S) {                                                                                \
-        case 9: return CALL(9); case 10: return CALL(10); case 11: return CALL(11);             \
-        case 12: return CALL(12); case 13: return CALL(13); case 14: return CALL(14);           \
-        case 15: return CALL(15); case 16: return CALL(16);                                     \
-    }
-#define GML_ECHAIN_SWITCH(CALL)                                                                 \
-    switch (S) {                                                                                \
-        case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3);                 \
-        case 4: return CALL(4); case 5: return CALL(5); case 6: return CALL(6);                 \
-        case 7: return CALL(7); case 8: return CALL(8);                                         \
-    }
+GML_ECHAIN16_S(GML_DECL_ECHAIN16)
+#define GML_DECL_EMLP(SV)                                                                                    \
+    template <> int gml_launch_edge_mlp_fwd<SV, SV>(const float*, const float*, const float*, const float*,  \
+                                                    const float*, float*, const int32_t*, float*, int64_t,   \
+                                                    hipStream_t);                                            \
+    template <> int gml_launch_edge_mlp_bwd<SV, SV>(const float*, const float*, const float*, const float*,  \
+                                                    const float*, const float*, float*, float*, float*,      \
+                                                    float*, float*, int64_t, void*, size_t, hipStream_t);
+GML_EMLP_S(GML_DECL_EMLP)
+
+extern "C" int32_t gml_edge_mlp_plan(int32_t direction, int32_t S, int32_t Sout, int32_t nlayers, uint32_t flags) {
+    const int arith = (int)(flags & GML_EDGE_ARITH_MASK);
+    const bool split = flags & GML_EDGE_HAS_SPLIT, gin = flags & GML_EDGE_WANT_GIN, dual = flags & GML_EDGE_DUAL, sym = flags & GML_EDGE_UNIQUE;
+    if (arith > EDGE_EXACT || (flags & ~63u)) return GML_EDGE_FAM_NONE;
+    if (direction == GML_EDGE_FWD) return gin ? GML_EDGE_FAM_NONE : edge_plan_fwd(S, Sout, nlayers, arith, split, dual, sym);
+    if (direction == GML_EDGE_BWD) return dual ? GML_EDGE_FAM_NONE : edge_plan_bwd(S, Sout, split, gin, sym, arith == EDGE_EXACT);
+    return GML_EDGE_FAM_NONE;
+}
 
 // dst[j] = sum_w partial[w][j] in a fixed order: 16 lanes split the partial index, LDS tree in fixed order
 __global__ __launch_bounds__(256) void gml_k_reduce_partials(const float* __restrict__ partial, int64_t nwaves, int nw,
@@ -70,27 +60,12 @@ __global__ __launch_bounds__(256) void gml_k_reduce_partials(const float* __rest
     }
 }
 
-#define GML_DECL_EMLP(SV)                                                                                    \
-    template <> int gml_launch_edge_mlp_fwd<SV, SV>(const float*, const float*, const float*, const float*,  \
-                                                    const float*, float*, const int32_t*, float*, int64_t,   \
-                                                    hipStream_t);                                            \
-    template <> int gml_launch_edge_mlp_bwd<SV, SV>(const float*, const float*, const float*, const float*,  \
-                                                    const float*, const float*, float*, float*, float*,      \
-                                                    float*, float*, int64_t, void*, size_t, hipStream_t);
-GML_DECL_EMLP(1) GML_DECL_EMLP(2) GML_DECL_EMLP(3) GML_DECL_EMLP(4) GML_DECL_EMLP(5) GML_DECL_EMLP(6)
-GML_DECL_EMLP(7) GML_DECL_EMLP(8) GML_DECL_EMLP(9) GML_DECL_EMLP(10) GML_DECL_EMLP(11) GML_DECL_EMLP(12)
-GML_DECL_EMLP(13) GML_DECL_EMLP(14) GML_DECL_EMLP(15) GML_DECL_EMLP(16)
-
-#define GML_EMLP_SWITCH(CALL)                                                                   \
-    switch (S) {                                                                                \
-        case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3);                 \
-        case 4: return CALL(4); case 5: return CALL(5); case 6: return CALL(6);                 \
-        case 7: return CALL(7); case 8: return CALL(8); case 9: return CALL(9);                 \
-        case 10: return CALL(10); case 11: return CALL(11); case 12: return CALL(12);           \
-        case 13: return CALL(13); case 14: return CALL(14); case 15: return CALL(15);           \
-        case 16: return CALL(16);                                                               \
-    }                                                                                           \
-    return GML_E_UNSUPPORTED;
+// (x0, x1) -> packed bf16 pairs: hi = the values truncated to bf16, lo = their rounded residuals (the split of gml_chain_b1)
+__device__ __forceinline__ uint2 gml_presplit_pair(float x0, float x1) {
+    const float t0 = __uint_as_float(__float_as_uint(x0) & 0xffff0000u);
+    const float t1 = __uint_as_float(__float_as_uint(x1) & 0xffff0000u);
+    return uint2{gml_pack2(t0, t1), gml_pack2(x0 - t0, x1 - t1)};
+}
 
 // hi[8] | lo[8] bf16 per edge (32 bytes): the layer-1 operand of the matrix-core kernels, made once per batch
 // 8 < S <= 16: hi[16] | lo[16] per edge (64 bytes), the operand rows of gml_edge_chain16_impl.h
@@ -102,10 +77,9 @@ __global__ __launch_bounds__(256) void gml_k_edge_presplit16(const float* __rest
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float x0 = (2 * j < S) ? ea[e * S + 2 * j] : 0.f, x1 = (2 * j + 1 < S) ? ea[e * S + 2 * j + 1] : 0.f;
-        const float t0 = __uint_as_float(__float_as_uint(x0) & 0xffff0000u);
-        const float t1 = __uint_as_float(__float_as_uint(x1) & 0xffff0000u);
-        hi[j] = gml_pack2(t0, t1);
-        lo[j] = gml_pack2(x0 - t0, x1 - t1);
+        const uint2 p = gml_presplit_pair(x0, x1);
+        hi[j] = p.x;
+        lo[j] = p.y;
     }
     u32x4* o = reinterpret_cast<u32x4*>(es + e * 16);
     o[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
@@ -122,10 +96,9 @@ __global__ __launch_bounds__(256) void gml_k_edge_presplit(const float* __restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float x0 = (2 * j < S) ? ea[e * S + 2 * j] : 0.f, x1 = (2 * j + 1 < S) ? ea[e * S + 2 * j + 1] : 0.f;
-        const float t0 = __uint_as_float(__float_as_uint(x0) & 0xffff0000u);
-        const float t1 = __uint_as_float(__float_as_uint(x1) & 0xffff0000u);
-        hi[j] = gml_pack2(t0, t1);
-        lo[j] = gml_pack2(x0 - t0, x1 - t1);
+        const uint2 p = gml_presplit_pair(x0, x1);
+        hi[j] = p.x;
+        lo[j] = p.y;
     }
     u32x4* o = reinterpret_cast<u32x4*>(es + e * 8);
     o[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
@@ -156,10 +129,9 @@ __global__ __launch_bounds__(256) void gml_k_gather_presplit(const float* __rest
     uint32_t hi[4], lo[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float t0 = __uint_as_float(__float_as_uint(x[2 * j]) & 0xffff0000u);
-        const float t1 = __uint_as_float(__float_as_uint(x[2 * j + 1]) & 0xffff0000u);
-        hi[j] = gml_pack2(t0, t1);
-        lo[j] = gml_pack2(x[2 * j] - t0, x[2 * j + 1] - t1);
+        const uint2 p = gml_presplit_pair(x[2 * j], x[2 * j + 1]);
+        hi[j] = p.x;
+        lo[j] = p.y;
     }
     u32x4* o = reinterpret_cast<u32x4*>(es + e * 8);
     o[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
@@ -201,25 +173,22 @@ extern "C" int gml_edge_mlp_fwd(const float* ea, const void* ea_split, const flo
     if (!ea || !w1 || !w2 || !w3 || !w4 || !out) return GML_E_BADARG;
     if (S != Sout) return GML_E_UNSUPPORTED;   // every reference script uses nedgeoutput == nedgeinput
     if ((((uintptr_t)ea | (uintptr_t)out | (uintptr_t)out_t | (uintptr_t)ea_split) & 15) != 0) return GML_E_BADARG;
-#ifdef GML_NO_PRESPLIT
-    ea_split = nullptr;
-#endif
     if (out_t && !tpos) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    if (emlp_use_chain(S)) {
-        // the second (source-order) copy is scattered through one buffer descriptor: 32-bit byte offsets
-        if (out_t && (uint64_t)num_edges * (uint64_t)S * 4u >= 0xffffff00ull) return GML_E_UNSUPPORTED;
-#define GML_CALL_CF(SV) \
-    gml_launch_edge_chain_fwd<SV>(ea, (const uint32_t*)ea_split, w1, w2, w3, w4, out, tpos, out_t, num_edges, st)
-        GML_ECHAIN_SWITCH(GML_CALL_CF)
+    const uint32_t* es = (const uint32_t*)ea_split;
+#define GML_CASE_CF(SV) case SV: return gml_launch_edge_chain_fwd<SV>(ea, es, w1, w2, w3, w4, out, tpos, out_t, num_edges, st);
+#define GML_CASE_CF16(SV) case SV: return gml_launch_edge_chain16_fwd<SV>(es, w1, w2, w3, w4, out, tpos, out_t, num_edges, st);
+#define GML_CASE_F(SV) case SV: return gml_launch_edge_mlp_fwd<SV, SV>(ea, w1, w2, w3, w4, out, tpos, out_t, num_edges, st);
+    switch (edge_plan_fwd(S, Sout, 0, EDGE_TWO_PIECE, es != nullptr, out_t != nullptr, false)) {
+        case GML_EDGE_FAM_CHAIN:
+            // the second (source-order) copy is scattered through one buffer descriptor: 32-bit byte offsets
+            if (out_t && !edge_plan_offsets_fit(num_edges, S, 0xffffff00ull)) return GML_E_UNSUPPORTED;
+            switch (S) { GML_ECHAIN_S(GML_CASE_CF) }
+            break;
+        case GML_EDGE_FAM_CHAIN16: switch (S) { GML_ECHAIN16_S(GML_CASE_CF16) } break;
+        case GML_EDGE_FAM_VALU: switch (S) { GML_EMLP_S(GML_CASE_F) } break;
     }
-    if (emlp_use_chain16(S, ea_split, nullptr)) {
-#define GML_CALL_CF16(SV) \
-    gml_launch_edge_chain16_fwd<SV>((const uint32_t*)ea_split, w1, w2, w3, w4, out, tpos, out_t, num_edges, st)
-        GML_ECHAIN16_SWITCH(GML_CALL_CF16)
-    }
-#define GML_CALL_F(SV) gml_launch_edge_mlp_fwd<SV, SV>(ea, w1, w2, w3, w4, out, tpos, out_t, num_edges, st)
-    GML_EMLP_SWITCH(GML_CALL_F)
+    return GML_E_UNSUPPORTED;
 }
 
 // the same on the exact-arithmetic family whatever the shape (one edge per lane, fp32 FMAs, f32-input MFMA for the weight gradients, the
@@ -234,34 +203,25 @@ extern "C" int gml_edge_mlp_fwd_exact(const float* ea, const float* w1, const fl
     if ((((uintptr_t)ea | (uintptr_t)out | (uintptr_t)out_t) & 15) != 0) return GML_E_BADARG;
     if (out_t && !tpos) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    GML_EMLP_SWITCH(GML_CALL_F)
+    if (edge_plan_fwd(S, Sout, 0, EDGE_EXACT, false, out_t != nullptr, false) == GML_EDGE_FAM_VALU) switch (S) { GML_EMLP_S(GML_CASE_F) }
+    return GML_E_UNSUPPORTED;
 }
 
-static int64_t emlp_bwd_waves(int64_t E, int S) {
-    const int chb = 7 * S, cha = 5 * S;
-    const int str = (chb > cha ? chb : cha) | 1;
-    const int waves = (str * 64 * 4 * 4 <= 64 * 1024) ? 4 : 2;
-    return gml_edge_mlp_bwd_waves(E, waves);
-}
-
+// every family the shape can take is covered, so the size does not depend on the call's pointers or on the environment (the S <= 8
+// chain is counted at 8 workgroups per CU, above the 6 it launches: the size callers have always been given)
 extern "C" size_t gml_edge_mlp_bwd_workspace_bytes(int64_t num_edges, int32_t S, int32_t Sout) {
     if (num_edges <= 0 || S <= 0 || Sout != S) return 0;
-    // both kernel families are covered, so the size does not depend on the environment switch
-    int64_t parts = emlp_bwd_waves(num_edges, S);
-    if (S <= 8 && gml_edge_chain_bwd_groups(num_edges) > parts) parts = gml_edge_chain_bwd_groups(num_edges);
+    int64_t parts = edge_plan_bwd_parts(GML_EDGE_FAM_VALU, num_edges, S);
+    if (S <= 8 && gml_edge_chain_bwd_groups(num_edges, 8) > parts) parts = gml_edge_chain_bwd_groups(num_edges, 8);
     if (S > 8 && S <= 16 && gml_edge_chain16_bwd_groups(num_edges) > parts) parts = gml_edge_chain16_bwd_groups(num_edges);
     return (size_t)parts * (size_t)(6 * S * S + Sout * 4 * S) * sizeof(float);
 }
 
-// partial rows gml_edge_mlp_bwd leaves in ws for this call shape (the dispatch below, mirrored)
+// partial rows gml_edge_mlp_bwd leaves in ws for this call shape (a shape it refuses: the VALU family's count)
 extern "C" int64_t gml_edge_mlp_bwd_parts(int64_t num_edges, int32_t S, int32_t Sout, int32_t has_split, int32_t want_gin) {
     if (num_edges <= 0 || S <= 0 || Sout != S) return 0;
-#ifdef GML_NO_PRESPLIT
-    has_split = 0;
-#endif
-    if (emlp_use_chain(S)) return gml_edge_chain_bwd_groups(num_edges, gml_edge_chain_bwd_wgs());
-    if (emlp_use_chain16(S, has_split ? (const void*)1 : nullptr, want_gin ? (const void*)1 : nullptr)) return gml_edge_chain16_bwd_groups(num_edges);
-    return emlp_bwd_waves(num_edges, S);
+    const int fam = edge_plan_bwd(S, Sout, has_split != 0, want_gin != 0, false, false);
+    return edge_plan_bwd_parts(fam == GML_EDGE_FAM_NONE ? GML_EDGE_FAM_VALU : fam, num_edges, S);
 }
 
 extern "C" int gml_edge_mlp_bwd(const float* ea, const void* ea_split, const float* w1, const float* w2, const float* w3,
@@ -275,32 +235,23 @@ extern "C" int gml_edge_mlp_bwd(const float* ea, const void* ea_split, const flo
     hipStream_t st = (hipStream_t)stream;
     if (num_edges == 0) {
         if (nofold) return GML_OK;                           /* (gml_edge_mlp_bwd_parts is 0: the fold writes zeros) */
-        gml_zero_async(dw1, sizeof(float) * 2 * S * S, st);
-        gml_zero_async(dw2, sizeof(float) * 2 * S * S, st);
-        gml_zero_async(dw3, sizeof(float) * 2 * S * S, st);
-        gml_zero_async(dw4, sizeof(float) * 4 * S * Sout, st);
-        return gml_launch_status();
+        return gml_edge_zero_dw(dw1, dw2, dw3, dw4, S, Sout, st);
     }
     if (!ea || !gout || !ws) return GML_E_BADARG;
     if ((((uintptr_t)ea | (uintptr_t)gout | (uintptr_t)gin | (uintptr_t)ea_split) & 15) != 0) return GML_E_BADARG;
-#ifdef GML_NO_PRESPLIT
-    ea_split = nullptr;
-#endif
-    if (emlp_use_chain(S)) {
-#define GML_CALL_CB(SV) \
-    gml_launch_edge_chain_bwd<SV>(ea, (const uint32_t*)ea_split, w1, w2, w3, w4, gout, gin, dw1, dw2, dw3, dw4, \
-                                  num_edges, ws, ws_bytes, st)
-        GML_ECHAIN_SWITCH(GML_CALL_CB)
+    const uint32_t* es = (const uint32_t*)ea_split;
+#define GML_CASE_CB(SV) \
+    case SV: return gml_launch_edge_chain_bwd<SV>(ea, es, w1, w2, w3, w4, gout, gin, dw1, dw2, dw3, dw4, num_edges, ws, ws_bytes, st);
+#define GML_CASE_CB16(SV) \
+    case SV: return gml_launch_edge_chain16_bwd<SV>(es, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, num_edges, ws, ws_bytes, st);
+#define GML_CASE_B(SV) \
+    case SV: return gml_launch_edge_mlp_bwd<SV, SV>(ea, w1, w2, w3, w4, gout, gin, dw1, dw2, dw3, dw4, num_edges, ws, ws_bytes, st);
+    switch (edge_plan_bwd(S, Sout, es != nullptr, gin != nullptr, false, false)) {
+        case GML_EDGE_FAM_CHAIN: switch (S) { GML_ECHAIN_S(GML_CASE_CB) } break;
+        case GML_EDGE_FAM_CHAIN16: switch (S) { GML_ECHAIN16_S(GML_CASE_CB16) } break;
+        case GML_EDGE_FAM_VALU: switch (S) { GML_EMLP_S(GML_CASE_B) } break;
     }
-    if (emlp_use_chain16(S, ea_split, gin)) {
-#define GML_CALL_CB16(SV) \
-    gml_launch_edge_chain16_bwd<SV>((const uint32_t*)ea_split, w1, w2, w3, w4, gout, dw1, dw2, dw3, dw4, num_edges, ws, \
-                                    ws_bytes, st)
-        GML_ECHAIN16_SWITCH(GML_CALL_CB16)
-    }
-#define GML_CALL_B(SV) \
-    gml_launch_edge_mlp_bwd<SV, SV>(ea, w1, w2, w3, w4, gout, gin, dw1, dw2, dw3, dw4, num_edges, ws, ws_bytes, st)
-    GML_EMLP_SWITCH(GML_CALL_B)
+    return GML_E_UNSUPPORTED;
 }
 
 // gml_edge_mlp_bwd on the exact-arithmetic family (see gml_edge_mlp_fwd_exact); dw1 .. dw4 are required (no deferred fold);
@@ -313,13 +264,10 @@ extern "C" int gml_edge_mlp_bwd_exact(const float* ea, const float* w1, const fl
     if (S != Sout) return GML_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (num_edges == 0) {
-        gml_zero_async(dw1, sizeof(float) * 2 * S * S, st);
-        gml_zero_async(dw2, sizeof(float) * 2 * S * S, st);
-        gml_zero_async(dw3, sizeof(float) * 2 * S * S, st);
-        gml_zero_async(dw4, sizeof(float) * 4 * S * Sout, st);
-        return gml_launch_status();
+        return gml_edge_zero_dw(dw1, dw2, dw3, dw4, S, Sout, st);
     }
     if (!ea || !gout || !ws) return GML_E_BADARG;
     if ((((uintptr_t)ea | (uintptr_t)gout | (uintptr_t)gin) & 15) != 0) return GML_E_BADARG;
-    GML_EMLP_SWITCH(GML_CALL_B)
+    if (edge_plan_bwd(S, Sout, false, gin != nullptr, false, true) == GML_EDGE_FAM_VALU) switch (S) { GML_EMLP_S(GML_CASE_B) }
+    return GML_E_UNSUPPORTED;
 }

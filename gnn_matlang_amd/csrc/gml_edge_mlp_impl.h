@@ -10,7 +10,16 @@
 // edge axis with v_mfma_f32_16x16x4_f32, accumulating across all its batches in registers; one
 // deterministic partial per wave goes to the workspace and a second kernel folds them.
 #pragma once
-#include "gml_common.h"
+#include "gml_edge_plan.h"
+
+// the S = Sout each fam file instantiates (gml_edge_mlp_a.hip .. _f.hip): one compile job each
+#define GML_EMLP_S_A(X) X(1) X(2) X(3) X(4) X(5)
+#define GML_EMLP_S_B(X) X(6) X(7) X(8)
+#define GML_EMLP_S_C(X) X(9) X(10) X(11)
+#define GML_EMLP_S_D(X) X(12) X(13)
+#define GML_EMLP_S_E(X) X(14) X(15)
+#define GML_EMLP_S_F(X) X(16)
+#define GML_EMLP_S(X) GML_EMLP_S_A(X) GML_EMLP_S_B(X) GML_EMLP_S_C(X) GML_EMLP_S_D(X) GML_EMLP_S_E(X) GML_EMLP_S_F(X)
 
 // The weights are loop-invariant, so LICM would hoist all 10*S*S scalar loads out of the edge loop
 // and spill hundreds of SGPRs; re-deriving the (uniform) pointers per iteration keeps every s_load
@@ -252,11 +261,6 @@ void gml_k_edge_mlp_bwd(const float* __restrict__ ea, const float* __restrict__ 
         }
 }
 
-// dw[j] = sum_w partial[w][j]  (fixed order: deterministic)
-__global__ void gml_k_reduce_partials(const float* __restrict__ partial, int64_t nwaves, int nw,
-                                      float* __restrict__ d0, int n0, float* __restrict__ d1, int n1,
-                                      float* __restrict__ d2, int n2, float* __restrict__ d3, int n3);
-
 template <int S, int SO>
 int gml_launch_edge_mlp_fwd(const float* ea, const float* w1, const float* w2, const float* w3, const float* w4,
                             float* out, const int32_t* tpos, float* out_t, int64_t E, hipStream_t st);
@@ -264,14 +268,6 @@ template <int S, int SO>
 int gml_launch_edge_mlp_bwd(const float* ea, const float* w1, const float* w2, const float* w3, const float* w4,
                             const float* gout, float* gin, float* dw1, float* dw2, float* dw3, float* dw4,
                             int64_t E, void* ws, size_t ws_bytes, hipStream_t st);
-
-static inline int64_t gml_edge_mlp_bwd_waves(int64_t E, int waves_per_wg) {
-    const int64_t nbatch = gml_cdiv(E, 64);
-    int64_t nw = (int64_t)GML_NUM_CU * 8;            // persistent: <= 8 waves per CU hold accumulators
-    if (nw > nbatch) nw = nbatch;
-    nw = gml_cdiv(nw, waves_per_wg) * waves_per_wg;
-    return nw < waves_per_wg ? waves_per_wg : nw;
-}
 
 #define GML_DEFINE_EDGE_MLP(SV)                                                                              \
     template <>                                                                                              \
@@ -291,6 +287,7 @@ static inline int64_t gml_edge_mlp_bwd_waves(int64_t E, int waves_per_wg) {
                                         size_t ws_bytes, hipStream_t st) {                                   \
         using C = GmlEdgeMlpBwdCfg<SV, SV>;                                                                  \
         const int64_t nbatch = gml_cdiv(E, 64);                                                              \
+        static_assert(C::WAVES == edge_plan_valu_bwd_wg_waves(SV) && C::NW == 10 * SV * SV, "gml_edge_plan.h"); \
         const int64_t nwaves = gml_edge_mlp_bwd_waves(E, C::WAVES);                                          \
         if (ws_bytes < (size_t)nwaves * C::NW * sizeof(float)) return GML_E_WORKSPACE;                       \
         const int64_t bpw = gml_cdiv(nbatch, nwaves);                                                        \
@@ -298,11 +295,5 @@ static inline int64_t gml_edge_mlp_bwd_waves(int64_t E, int waves_per_wg) {
         hipLaunchKernelGGL((gml_k_edge_mlp_bwd<SV, SV>), dim3((unsigned)(nwaves / C::WAVES)),                \
                            dim3(C::WAVES * 64), lds, st, ea, w1, w2, w3, w4, gout, gin, (float*)ws, E,       \
                            nbatch, bpw);                                                                     \
-        int rc = gml_launch_status();                                                                        \
-        if (rc != GML_OK) return rc;                                                                         \
-        if (!dw1) return GML_OK;   /* partials stay in ws: gml_fold_many */                                  \
-        const int n123 = 2 * SV * SV, n4 = SV * 4 * SV;                                                      \
-        hipLaunchKernelGGL(gml_k_reduce_partials, dim3((unsigned)gml_cdiv(C::NW, 16)), dim3(256), 0, st,      \
-                           (const float*)ws, nwaves, C::NW, dw1, n123, dw2, n123, dw3, n123, dw4, n4);       \
-        return gml_launch_status();                                                                          \
+        return gml_edge_fold_tail(ws, nwaves, SV, dw1, dw2, dw3, dw4, st);                                   \
     }

@@ -145,7 +145,7 @@ def flush_folds(jobs):
                 _lib.call('gml_fold_many', ctypes.addressof(arr), len(chunk), _stream(dev))
 
 
-EDGE_VALU = _os.environ.get('GML_EDGE_VALU', '0') == '1'
+EDGE_VALU = None               # GML_EDGE_VALU=1 as the LIBRARY read it (it decides: csrc/gml_edge_plan.h); filled by _edge_arith
 
 
 # GML_VERBOSE=1: count which kernel family every layer call takes (shapes off the compiled set degrade in SPEED, never in
@@ -492,6 +492,29 @@ class EdgeBranchWide(torch.autograd.Function):
         return tuple(next(gs) if n else None for n in need)
 
 
+def _edge_arith():
+    """the arithmetic flag of gml_edge_mlp_plan for a forward call under the current switches"""
+    global EDGE_VALU
+    if EDGE_VALU is None:
+        EDGE_VALU = int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, 2, 2, 0, _lib.GML_EDGE_TWO_PIECE)) == _lib.GML_EDGE_FAM_VALU
+    if exact_mode('edge'):
+        return _lib.GML_EDGE_EXACT
+    return _lib.GML_EDGE_THREE_PIECE if (EDGE_FWD6 and not EDGE_VALU) else _lib.GML_EDGE_TWO_PIECE
+
+
+# GML_VERBOSE labels of the families gml_edge_mlp_plan answers (tools/bench_configs.py lists 'VALU kernels' as a slow path)
+_EDGE_LABEL = {_lib.GML_EDGE_FAM_VALU: 'VALU kernels (one edge per lane, fp32)', _lib.GML_EDGE_FAM_CHAIN: 'matrix-core chain, two-piece',
+               _lib.GML_EDGE_FAM_CHAIN16: 'matrix-core chain16, two-piece', _lib.GML_EDGE_FAM_CHAIN6: 'matrix-core chain, three-piece',
+               _lib.GML_EDGE_FAM_CHAIN16X6: 'matrix-core chain16, three-piece', _lib.GML_EDGE_FAM_SYM6: 'matrix-core chain, three-piece, unique rows',
+               _lib.GML_EDGE_FAM_SYM16X6: 'matrix-core chain16, three-piece, unique rows'}
+
+
+def _edge_path(fam, arith, S, L=0):
+    if VERBOSE:
+        what = 'exact family (one edge per lane, fp32)' if arith == _lib.GML_EDGE_EXACT else _EDGE_LABEL[fam]
+        _path('edge', ('stack of %d layers in one pass, ' % L if L > 1 else '') + what, S, '-', S)
+
+
 def edge_mlp_fwd(ea, w1, w2, w3, w4, tpos=None, ea_split=None):
     """returns out (same edge order as ea) and, when tpos is given, the same rows at out_t[tpos[e]]."""
     E, S = ea.shape
@@ -502,18 +525,22 @@ def edge_mlp_fwd(ea, w1, w2, w3, w4, tpos=None, ea_split=None):
         return out[:, :So].contiguous(), (out_t[:, :So].contiguous() if out_t is not None else None)
     out = torch.empty(E, So, dtype=torch.float32, device=ea.device)
     out_t = torch.empty(E, So, dtype=torch.float32, device=ea.device) if tpos is not None else None
-    if exact_mode('edge'):                                # exact arithmetic covers the edge branch too (round 5: it did not)
-        _lib.call('gml_edge_mlp_fwd_exact', _ptr(ea), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(out), _ptr(tpos), _ptr(out_t),
-                  int(E), int(S), int(So), _stream(ea.device))
-        return out, out_t
-    if EDGE_FWD6 and 2 <= S <= 16 and not EDGE_VALU:      # three-piece products (fp32-class), reads the fp32 rows itself
-        rc = _lib.lib().gml_edge_mlp_fwd6(_ptr(ea), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(out), _ptr(tpos), _ptr(out_t),
-                                          int(E), int(S), int(So), _stream(ea.device))
-        if rc != _lib.GML_E_UNSUPPORTED:
-            _lib.check(rc)
-            return out, out_t
-    _lib.call('gml_edge_mlp_fwd', _ptr(ea), _ptr(ea_split), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(out), _ptr(tpos),
-              _ptr(out_t), int(E), int(S), int(So), _stream(ea.device))
+    arith = _edge_arith()
+    flags = (_lib.GML_EDGE_HAS_SPLIT if ea_split is not None else 0) | (_lib.GML_EDGE_DUAL if tpos is not None else 0)
+    fam = int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(So), 0, arith | flags))
+    if fam == _lib.GML_EDGE_FAM_NONE and arith == _lib.GML_EDGE_THREE_PIECE:      # S = 1 has no three-piece form: the default entry
+        arith = _lib.GML_EDGE_TWO_PIECE
+        fam = int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(So), 0, arith | flags))
+    if fam == _lib.GML_EDGE_FAM_NONE:
+        _lib.check(_lib.GML_E_UNSUPPORTED)
+    _edge_path(fam, arith, S)
+    tail = (_ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(out), _ptr(tpos), _ptr(out_t), int(E), int(S), int(So), _stream(ea.device))
+    if arith == _lib.GML_EDGE_EXACT:                      # exact arithmetic covers the edge branch too (round 5: it did not)
+        _lib.call('gml_edge_mlp_fwd_exact', _ptr(ea), *tail)
+    elif arith == _lib.GML_EDGE_THREE_PIECE:              # three-piece products (fp32-class), reads the fp32 rows itself
+        _lib.call('gml_edge_mlp_fwd6', _ptr(ea), *tail)
+    else:
+        _lib.call('gml_edge_mlp_fwd', _ptr(ea), _ptr(ea_split), *tail)
     return out, out_t
 
 
@@ -533,40 +560,41 @@ def edge_mlp_fwd_stack(ea, ea_split, weights, sym=None):
     import ctypes
     E, S = ea.shape
     L = len(weights)
-    if exact_mode('edge') or not ((1 if sym is not None else 2) <= L <= 4) or any(w[3].size(0) != S or w[0].size(1) != S for w in weights):
-        return None                                       # (the stacked kernel is a matrix-core chain: not the exact arithmetic)
-    arr = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
-    if EDGE_FWD6 and not EDGE_VALU and (S in (4, 8) or (L == 1 and 2 <= S <= 16)) and sym is not None and EDGE_SYM:
-        # the unique support rows only (gml_edge_chain_sym_impl.h): every output row is written, by its own entry or by its mirror's
-        outs = [torch.empty(E, S, dtype=torch.float32, device=ea.device) for _ in range(L)]
-        ws4 = (arr([w[0] for w in weights]), arr([w[1] for w in weights]), arr([w[2] for w in weights]), arr([w[3] for w in weights]))
-        if len(sym) == 3:                                 # (uid, mir, count): the entry count lives on the device (an assembled batch)
-            rc = _lib.lib().gml_edge_mlp_fwd_stack6_sym_dev(_ptr(ea), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), int(sym[0].numel()), L, *ws4,
-                                                            arr(outs), int(E), int(S), int(S), _stream(ea.device))
-        else:
-            rc = _lib.lib().gml_edge_mlp_fwd_stack6_sym(_ptr(ea), _ptr(sym[0]), _ptr(sym[1]), int(sym[0].numel()), L, *ws4,
-                                                        arr(outs), int(E), int(S), int(S), _stream(ea.device))
-        if rc != _lib.GML_E_UNSUPPORTED:
-            _lib.check(rc)
-            return outs
-    if EDGE_FWD6 and not EDGE_VALU and S in (4, 8):
-        outs = [torch.empty(E, S, dtype=torch.float32, device=ea.device) for _ in range(L)]
-        rc = _lib.lib().gml_edge_mlp_fwd_stack6(_ptr(ea), L, arr([w[0] for w in weights]), arr([w[1] for w in weights]),
-                                                arr([w[2] for w in weights]), arr([w[3] for w in weights]), arr(outs), int(E), int(S),
-                                                int(S), _stream(ea.device))
-        if rc != _lib.GML_E_UNSUPPORTED:
-            _lib.check(rc)
-            return outs
-    if ea_split is None:
+    if not ((1 if sym is not None else 2) <= L <= 4) or any(w[3].size(0) != S or w[0].size(1) != S for w in weights):
         return None
+    arith = _edge_arith()                                 # (exact: no stacked kernel, the plan answers none)
+    plan = lambda flags: int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(S), L, arith | flags))
+    # the unique support rows only (gml_edge_chain_sym_impl.h): every output row is written, by its own entry or by its mirror's
+    fam = plan(_lib.GML_EDGE_UNIQUE) if (sym is not None and EDGE_SYM) else _lib.GML_EDGE_FAM_NONE
+    if fam == _lib.GML_EDGE_FAM_NONE:
+        fam = plan(_lib.GML_EDGE_HAS_SPLIT if ea_split is not None else 0)
+    if fam == _lib.GML_EDGE_FAM_NONE:
+        return None
+    _edge_path(fam, arith, S, L)
     outs = [torch.empty(E, S, dtype=torch.float32, device=ea.device) for _ in range(L)]
-    rc = _lib.lib().gml_edge_mlp_fwd_stack(_ptr(ea_split), L, arr([w[0] for w in weights]), arr([w[1] for w in weights]),
-                                           arr([w[2] for w in weights]), arr([w[3] for w in weights]), arr(outs), int(E), int(S),
-                                           int(S), _stream(ea.device))
-    if rc == _lib.GML_E_UNSUPPORTED:
-        return None
-    _lib.check(rc)
+    arr = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
+    tail = [arr([w[i] for w in weights]) for i in range(4)] + [arr(outs), int(E), int(S), int(S), _stream(ea.device)]
+    if fam in (_lib.GML_EDGE_FAM_SYM6, _lib.GML_EDGE_FAM_SYM16X6):
+        if len(sym) == 3:                                 # (uid, mir, count): the entry count lives on the device (an assembled batch)
+            _lib.call('gml_edge_mlp_fwd_stack6_sym_dev', _ptr(ea), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), int(sym[0].numel()), L, *tail)
+        else:
+            _lib.call('gml_edge_mlp_fwd_stack6_sym', _ptr(ea), _ptr(sym[0]), _ptr(sym[1]), int(sym[0].numel()), L, *tail)
+    elif fam == _lib.GML_EDGE_FAM_CHAIN6:
+        _lib.call('gml_edge_mlp_fwd_stack6', _ptr(ea), L, *tail)
+    else:
+        _lib.call('gml_edge_mlp_fwd_stack', _ptr(ea_split), L, *tail)
     return outs
+
+
+def _edge_dw_flat(fq, ws, nparts, S, So, w1, w2, w3, w4):
+    """Queue the deferred fold of the partial rows in ws and return dw1 .. dw4 as views of its ONE flat destination: autograd takes
+    a view over as .grad without a copy, and the flat tensor (held by the queue until the fold has run) cannot be freed under the
+    fold's feet -- separate tensors referenced by the queue would be CLONED by AccumulateGrad (a second owner), before the fold
+    has filled them."""
+    n1, n4 = 2 * S * S, 4 * S * So
+    flat = torch.empty(3 * n1 + n4, dtype=torch.float32, device=ws.device)
+    fq.append((ws, nparts, 3 * n1 + n4, [(flat, 3 * n1 + n4)]))
+    return flat[:n1].view_as(w1), flat[n1:2 * n1].view_as(w2), flat[2 * n1:3 * n1].view_as(w3), flat[3 * n1:].view_as(w4)
 
 
 def edge_mlp_bwd(ea, w1, w2, w3, w4, gout, need_gin, ea_split=None, sym=None):
@@ -584,44 +612,32 @@ def edge_mlp_bwd(ea, w1, w2, w3, w4, gout, need_gin, ea_split=None, sym=None):
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
     gin = torch.empty_like(ea) if need_gin else None
     dw1, dw2, dw3, dw4 = torch.empty_like(w1), torch.empty_like(w2), torch.empty_like(w3), torch.empty_like(w4)
+    wsa = (int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
     if exact_mode('edge'):
         _lib.call('gml_edge_mlp_bwd_exact', _ptr(ea), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout), _ptr(gin),
-                  _ptr(dw1), _ptr(dw2), _ptr(dw3), _ptr(dw4), int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
+                  _ptr(dw1), _ptr(dw2), _ptr(dw3), _ptr(dw4), *wsa)
         return gin, dw1, dw2, dw3, dw4
-    fq = _fold_queue()
-    if sym is not None and EDGE_SYM and not need_gin and ea_split is not None and 2 <= S <= 16 and not EDGE_VALU and E > 0:
+    _edge_arith()                                         # (fills EDGE_VALU)
+    fq = _fold_queue() if E > 0 else None                 # deferred fold: no destinations, the partial rows stay in ws
+    d = [_ptr(None)] * 4 if fq is not None else [_ptr(dw1), _ptr(dw2), _ptr(dw3), _ptr(dw4)]
+    flags = (_lib.GML_EDGE_HAS_SPLIT if ea_split is not None else 0) | (_lib.GML_EDGE_WANT_GIN if need_gin else 0)
+    unique = sym is not None and EDGE_SYM and not EDGE_VALU and E > 0
+    if unique and int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_BWD, int(S), int(So), 0, flags | _lib.GML_EDGE_UNIQUE)) != _lib.GML_EDGE_FAM_NONE:
         # unique support rows only: entry u runs the chain once on gout[uid[u]] + gout[mir[u]]
         U = int(sym[0].numel())
-        nofold = fq is not None
-        d = [_ptr(None)] * 4 if nofold else [_ptr(dw1), _ptr(dw2), _ptr(dw3), _ptr(dw4)]
         if len(sym) == 3:                                 # (uid, mir, count): U is the capacity, the count lives on the device
-            rc = _lib.lib().gml_edge_mlp_bwd_sym_dev(_ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), U, _ptr(w1), _ptr(w2), _ptr(w3),
-                                                     _ptr(w4), _ptr(gout), d[0], d[1], d[2], d[3], int(E), int(S), int(So), _ptr(ws), ws.numel(),
-                                                     _stream(dev))
+            _lib.call('gml_edge_mlp_bwd_sym_dev', _ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), U, _ptr(w1), _ptr(w2), _ptr(w3),
+                      _ptr(w4), _ptr(gout), *d, *wsa)
         else:
-            rc = _lib.lib().gml_edge_mlp_bwd_sym(_ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), U, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout),
-                                                 d[0], d[1], d[2], d[3], int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
-        if rc != _lib.GML_E_UNSUPPORTED:
-            _lib.check(rc)
-            if not nofold:
-                return None, dw1, dw2, dw3, dw4
-            n1, n4 = 2 * S * S, 4 * S * So
-            flat = torch.empty(3 * n1 + n4, dtype=torch.float32, device=dev)
-            fq.append((ws, int(_lib.lib().gml_edge_mlp_bwd_sym_parts(U, int(S))), 3 * n1 + n4, [(flat, 3 * n1 + n4)]))
-            return (None, flat[:n1].view_as(w1), flat[n1:2 * n1].view_as(w2), flat[2 * n1:3 * n1].view_as(w3), flat[3 * n1:].view_as(w4))
-    if fq is not None and E > 0:
-        nparts = int(_lib.lib().gml_edge_mlp_bwd_parts(int(E), int(S), int(So), 1 if ea_split is not None else 0, 1 if need_gin else 0))
-        _lib.call('gml_edge_mlp_bwd', _ptr(ea), _ptr(ea_split), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout), _ptr(gin),
-                  _ptr(None), _ptr(None), _ptr(None), _ptr(None), int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
-        # ONE flat destination, the gradients are views of it: autograd takes a view over as .grad without a copy, and the flat
-        # tensor (held by the queue until the fold has run) cannot be freed under the fold's feet -- separate tensors referenced by
-        # the queue would be CLONED by AccumulateGrad (a second owner), before the fold has filled them
-        n1, n4 = 2 * S * S, 4 * S * So
-        flat = torch.empty(3 * n1 + n4, dtype=torch.float32, device=dev)
-        fq.append((ws, nparts, 3 * n1 + n4, [(flat, 3 * n1 + n4)]))
-        return (gin, flat[:n1].view_as(w1), flat[n1:2 * n1].view_as(w2), flat[2 * n1:3 * n1].view_as(w3), flat[3 * n1:].view_as(w4))
-    _lib.call('gml_edge_mlp_bwd', _ptr(ea), _ptr(ea_split), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout), _ptr(gin),
-              _ptr(dw1), _ptr(dw2), _ptr(dw3), _ptr(dw4), int(E), int(S), int(So), _ptr(ws), ws.numel(), _stream(dev))
+            _lib.call('gml_edge_mlp_bwd_sym', _ptr(ea_split), _ptr(sym[0]), _ptr(sym[1]), U, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout),
+                      *d, *wsa)
+        nparts = int(_lib.lib().gml_edge_mlp_bwd_sym_parts(U, int(S))) if fq is not None else 0
+        gin = None
+    else:
+        _lib.call('gml_edge_mlp_bwd', _ptr(ea), _ptr(ea_split), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(gout), _ptr(gin), *d, *wsa)
+        nparts = int(_lib.lib().gml_edge_mlp_bwd_parts(int(E), int(S), int(So), 1 if ea_split is not None else 0, 1 if need_gin else 0)) if fq is not None else 0
+    if fq is not None:
+        dw1, dw2, dw3, dw4 = _edge_dw_flat(fq, ws, nparts, S, So, w1, w2, w3, w4)
     return gin, dw1, dw2, dw3, dw4
 
 
@@ -1696,7 +1712,6 @@ class ML3LayerFunction(torch.autograd.Function):
                 src_order = bool(val_is_source) or (fused_b and fwd_gathers(S, Fin, nout1))
                 # (forward kernels without the gather: both orders from the edge kernel, second copy scattered through tpos)
                 dual = fused_b and not src_order and val.numel() * 4 < 0xffffff00
-                _path('edge', 'exact family (one edge per lane, fp32)' if exact_mode() else 'matrix-core chain' if max(val.size(1), w4.size(0)) <= 8 else ('matrix-core chain16' if max(val.size(1), w4.size(0)) <= 16 and not EDGE_VALU else 'VALU kernels'), val.size(1), '-', w4.size(0))
                 if src_order:
                     val_s = val if val_is_source else csr.to_source_order(val, cache=not val.requires_grad)
                     ea_t = ea_pre if val_is_source else None
@@ -1704,8 +1719,7 @@ class ML3LayerFunction(torch.autograd.Function):
                         ws_ = [(w1, w2, w3, w4)] + [tuple(_f32c(t, 'edge branch weight') for t in w) for w in stack[0]]
                         with _Timed('edge_mlp_fwd', 4 * val.numel() * (1 + len(ws_)), 20 * val.size(0) * val.size(1) ** 2 * len(ws_)):
                             outs = edge_mlp_fwd_stack(val_s, csr.presplit(val_s), ws_, csr.sym_index(val_s) if EDGE_SYM else None)
-                        if outs is not None:
-                            _path('edge', 'stack of %d layers in one pass' % len(ws_), val.size(1), '-', w4.size(0))
+                        if outs is not None:                # (GML_VERBOSE: the edge functions record the family the plan named)
                             ea_t = outs[0]
                             stack[1].extend(outs[1:])
                     if ea_t is None:

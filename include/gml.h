@@ -397,8 +397,9 @@ int gml_edge_mlp_wide_bwd(const float* ea, const float* w1, const float* w2, con
 /* The edge branches of a STACK of ML3Layers in one pass: every layer of Zinc12k.py:338-341 / counting.py:361-366 receives the
  * same raw supports (data.edge_attr2), so L launches of gml_edge_mlp_fwd read them L times.  out[l] [num_edges, Sout] =
  * the branch of layer l (weights w1[l] .. w4[l]) applied to the rows whose split image is ea_split (gml_edge_presplit), same
- * edge order.  The five pointer arrays (nlayers entries each) live on the HOST.  GML_E_UNSUPPORTED outside S = Sout in {4, 8},
- * 2 <= nlayers <= 4 (or under GML_EDGE_VALU=1): call gml_edge_mlp_fwd per layer -- same results either way. */
+ * edge order.  The five pointer arrays (nlayers entries each) live on the HOST.  GML_E_UNSUPPORTED wherever gml_edge_mlp_plan
+ * answers GML_EDGE_FAM_NONE for it -- outside S = Sout in {4, 8}, 2 <= nlayers <= 4, or under GML_EDGE_VALU=1: call gml_edge_mlp_fwd
+ * per layer -- same results either way. */
 int gml_edge_mlp_fwd_stack(const void* ea_split, int32_t nlayers, const float* const* w1, const float* const* w2,
                            const float* const* w3, const float* const* w4, float* const* out,
                            int64_t num_edges, int32_t S, int32_t Sout, gml_stream_t stream);
@@ -461,6 +462,30 @@ int gml_edge_mlp_fwd_exact(const float* ea, const float* w1, const float* w2, co
 int gml_edge_mlp_bwd_exact(const float* ea, const float* w1, const float* w2, const float* w3, const float* w4,
                            const float* gout, float* gin, float* dw1, float* dw2, float* dw3, float* dw4,
                            int64_t num_edges, int32_t S, int32_t Sout, void* ws, size_t ws_bytes, gml_stream_t stream);
+
+/* Which kernel family serves an edge-branch call (csrc/gml_edge_plan.h: the one place that decides it; answered on the host, no
+ * device needed).  direction: GML_EDGE_FWD or GML_EDGE_BWD.  nlayers (forward): 0 = the single-layer entry points (gml_edge_mlp_fwd,
+ * _fwd6, _fwd_exact), 1 .. 4 = the stacked ones (_fwd_stack, _fwd_stack6, _fwd_stack6_sym); ignored for the backward.  flags: one
+ * arithmetic (GML_EDGE_TWO_PIECE: gml_edge_mlp_fwd / _fwd_stack / _bwd; GML_EDGE_THREE_PIECE: the ..6 forwards -- the backward
+ * is two-piece either way; GML_EDGE_EXACT: the _exact entries) ored with GML_EDGE_HAS_SPLIT (ea_split is given), GML_EDGE_WANT_GIN
+ * (backward: gin != NULL), GML_EDGE_DUAL (forward: out_t != NULL) and GML_EDGE_UNIQUE (the _sym entries).  Returns the family, or
+ * GML_EDGE_FAM_NONE where the entry point answers GML_E_UNSUPPORTED (S != Sout, S > 16, a stack the library has no kernel for, ...)
+ * and for a flag that does not belong to the direction or is not listed here.
+ * GML_EDGE_VALU=1 in the environment (read once per process) turns every two-piece chain answer into GML_EDGE_FAM_VALU. */
+enum { GML_EDGE_FWD = 0, GML_EDGE_BWD = 1 };
+enum { GML_EDGE_TWO_PIECE = 0, GML_EDGE_THREE_PIECE = 1, GML_EDGE_EXACT = 2, GML_EDGE_ARITH_MASK = 3,
+       GML_EDGE_HAS_SPLIT = 4, GML_EDGE_WANT_GIN = 8, GML_EDGE_DUAL = 16, GML_EDGE_UNIQUE = 32 };
+enum { GML_EDGE_FAM_NONE = 0,
+       GML_EDGE_FAM_VALU = 1,        /* one edge per lane, fp32 FMAs (csrc/gml_edge_mlp_impl.h): S = 1, exact, gin at S > 8 */
+       GML_EDGE_FAM_CHAIN = 2,         /* two-piece matrix-core chain, 2 <= S <= 8 (gml_edge_chain_impl.h); stacks: S in {4, 8}, 2 .. 4 layers */
+       GML_EDGE_FAM_CHAIN16 = 3,       /* two-piece, 8 < S <= 16 (gml_edge_chain16_impl.h): needs ea_split, no gin */
+       GML_EDGE_FAM_CHAIN6 = 4,        /* three-piece forward, 2 <= S <= 8 (gml_edge_chain6_impl.h); stacks: S in {4, 8}, 1 .. 4 layers */
+       GML_EDGE_FAM_CHAIN16X6 = 5,     /* three-piece forward, 8 < S <= 16 (gml_edge_chain16x6_impl.h) */
+       GML_EDGE_FAM_SYM6 = 6,          /* unique rows, three-piece forward, 2 <= S <= 8 (gml_edge_chain_sym_impl.h) */
+       GML_EDGE_FAM_SYM16X6 = 7,       /* unique rows, three-piece forward, 8 < S <= 16, one layer */
+       GML_EDGE_FAM_SYM_CHAIN = 8,     /* unique rows, two-piece backward, 2 <= S <= 8 */
+       GML_EDGE_FAM_SYM_CHAIN16 = 9 }; /* unique rows, two-piece backward, 8 < S <= 16 */
+int32_t gml_edge_mlp_plan(int32_t direction, int32_t S, int32_t Sout, int32_t nlayers, uint32_t flags);
 
 /* ---------------------------------------------------------------- ML3Layer forward without the edge branch
  * (libs/spect_conv.py:204-212): out[:, :nout1] = act(SpectConv(x)), out[:, nout1:nout1+F2] = tanh(fc11 x) * tanh(fc12 x).

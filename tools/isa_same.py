@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Is the device code of the conv kernels the same as at <commit>?
 
-    python tools/isa_same.py <commit> [--forward] [--kernels] [--work DIR] [file.hip ...]
+    python tools/isa_same.py <commit> [--forward | --edge] [--kernels] [--work DIR] [file.hip ...]
 
 Compiles each source to gfx950 device assembly (the flags of gnn_matlang_amd/_build.py plus -S --cuda-device-only), once from
 `git archive <commit>` and once from the working tree, and compares the two files after dropping the lines that contain
 `__hip_cuid_` (a hash of the source text: the only thing that differs when dead code is deleted).  One line per file; exit
 status 1 when any differs.  Without file arguments: every gml_bwd*_fam_*.hip and gml_spectconv_bwd.hip that both trees have, or,
-with --forward, every gml_fwd*_fam*.hip and gml_spectconv.hip.
+with --forward, every gml_fwd*_fam*.hip and gml_spectconv.hip, or, with --edge, every gml_edge_*.hip (the ML3Layer edge branch).
 --kernels compares kernel by kernel (a refactor that deletes SOME instantiations of a file): each assembly is cut at its kernel
 symbols, kernels that both sides have are compared, kernels that one side alone has are listed and are no difference.
 --work DIR keeps the assembly there and reuses <commit>'s side on the next call (a refactor in several steps)."""
@@ -25,6 +25,7 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CSRC = os.path.join('gnn_matlang_amd', 'csrc')
 BACKWARD = ('gml_bwd*_fam*.hip', 'gml_spectconv_bwd.hip')
 FORWARD = ('gml_fwd*_fam*.hip', 'gml_spectconv.hip')
+EDGE = ('gml_edge_*.hip',)
 
 
 def asm(tree, src, out):
@@ -38,7 +39,7 @@ def asm(tree, src, out):
 
 
 _LOCAL = re.compile(r'(\.L|\b)(BB|func_begin|func_end|tmp)\d+(?=_|\b)')
-_NEXT = re.compile(r'\s*\.(protected|globl|weak|hidden|type|section\s+\.text)\b')
+_NEXT = re.compile(r'\s*\.(protected|globl|weak|hidden|type|section\s+\.(text|AMDGPU))\b')
 _LABEL = re.compile(r'([A-Za-z_$][\w$.]*):')
 
 
@@ -78,6 +79,7 @@ def main():
     ap.add_argument('--work', help='directory for the assembly files (kept; the side of <commit> is reused)')
     ap.add_argument('--jobs', type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument('--forward', action='store_true', help='default file list: the conv forward instead of the backward')
+    ap.add_argument('--edge', action='store_true', help='default file list: the edge branch')
     ap.add_argument('--kernels', action='store_true', help='compare kernel by kernel; list the kernels only one side has')
     ap.add_argument('files', nargs='*')
     a = ap.parse_intermixed_args()
@@ -91,7 +93,7 @@ def main():
         subprocess.run(['tar', '-x', '-C', base], stdin=ar.stdout, check=True)
         if ar.wait():
             raise RuntimeError('git archive %s failed' % rev)
-    files = a.files or sorted(os.path.basename(f) for pat in (FORWARD if a.forward else BACKWARD)
+    files = a.files or sorted(os.path.basename(f) for pat in (EDGE if a.edge else FORWARD if a.forward else BACKWARD)
                               for f in glob.glob(os.path.join(ROOT, CSRC, pat)))
     files = [os.path.basename(f) for f in files]
     gone = [f for f in files if not os.path.exists(os.path.join(base, CSRC, f))]
