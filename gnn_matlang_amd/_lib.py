@@ -51,6 +51,8 @@ SIGNATURES = {
                                    _i64, _i32, _i32, _i32, _i32, _u32, _p]),
     'gml_spectconv_bwd_group_rows': (ctypes.c_int, [_i32, _i32, _i32, _u32]),
     'gml_spectconv_bwd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32, _i32, _u32]),
+    'gml_spectconv_bwd_stage_edges': (ctypes.c_int32, [_i32, _i32, _i32, _u32]),
+    'gml_spectconv_bwd_stage_window': (ctypes.c_int32, [_i32, _i32, _i32, _u32]),
     'gml_spectconv_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p,
                                          _i64, _i32, _i32, _i32, _i32, _i32, _u32, _p, _sz, _p]),
     'gml_spectconv_bwd_mix_supported': (ctypes.c_int, [_i32, _i32, _i32, _i32, _u32]),

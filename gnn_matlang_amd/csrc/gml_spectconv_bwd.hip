@@ -130,6 +130,44 @@ extern "C" size_t gml_spectconv_bwd_workspace_bytes(int64_t num_rows, int32_t S,
     return (size_t)pl.grid * S * Fin * Fout * sizeof(float);
 }
 
+/* Host-only: the per-group staging capacities of the kernel the dispatch below selects for this shape and these flags -- the
+   backward twins of gml_spectconv_fwd_stage_edges / _stage_window.  A group inside both takes the kernel's register-batched
+   (staged) road; one beyond either is still served, by the rolled loops of bwd3 / the 64-row kernel, or -- with GML_DMA_RING -- by
+   the whole launch falling back from the ring to bwd3.  0: no fused backward, or a kernel form without a staged road (the 64-row
+   kernel stages float4 value rows only: S % 4 == 0). */
+static bool bwd4_asked_shape(int S, int Fin, int Fout, uint32_t flags) {
+    const int nfb = (Fin + 15) / 16;
+    bool has = false;
+#define GML_BWD4_HAS(SV, A) if (S == SV && nfb == A) has = true;
+    GML_BWD4_SHAPES(GML_BWD4_HAS)
+    return has && bwd3_shape(S, Fin, Fout, flags) && (bwd4_env() || (flags & GML_DMA_RING)) && !(flags & (GML_ACCUM | GML_DVAL_ACCUM));
+}
+
+extern "C" int32_t gml_spectconv_bwd_stage_edges(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
+    const int rows = gml_spectconv_bwd_group_rows(S, Fin, Fout, flags);
+    if (rows == 0) return 0;
+    const int nfb = (Fin + 15) / 16, nob = (Fout + 15) / 16;
+    if (rows == 64) return S % 4 == 0 ? GML_BWD_ECAP_MAX : 0;
+    if (bwd4_asked_shape(S, Fin, Fout, flags)) {
+#define GML_BWD4_STAGE_E(SV, A) if (S == SV && nfb == A) return GmlBwd4Cfg<SV, A>::ECAP - 3;
+        GML_BWD4_SHAPES(GML_BWD4_STAGE_E)
+    }
+#define GML_BWD3_STAGE_E(SV, A, W, B) if (S == SV && nfb == A && nob == B) return GmlBwd3Cfg<SV, A, W, B>::ECAP_MAX;
+    GML_BWD3_SHAPES(GML_BWD3_STAGE_E)
+    return 0;
+}
+
+extern "C" int32_t gml_spectconv_bwd_stage_window(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags) {
+    const int rows = gml_spectconv_bwd_group_rows(S, Fin, Fout, flags);
+    if (rows == 0) return 0;
+    const int nfb = (Fin + 15) / 16, nob = (Fout + 15) / 16;
+    if (rows == 64) return S % 4 == 0 ? GML_BWD_XCAP_MAX : 0;
+    if (bwd4_asked_shape(S, Fin, Fout, flags)) return GmlBwd4Cfg<8, 2>::XCAP - 7;
+#define GML_BWD3_STAGE_W(SV, A, W, B) if (S == SV && nfb == A && nob == B) return GmlBwd3Cfg<SV, A, W, B>::XCAP_MAX;
+    GML_BWD3_SHAPES(GML_BWD3_STAGE_W)
+    return 0;
+}
+
 static int spectconv_bwd_impl(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo, const float* val,
                               const float* x, int64_t ldx, const float* g, int64_t ldg, const float* w,
                               float* dx, int64_t lddx, float* dval, float* dw,
@@ -186,7 +224,9 @@ static int spectconv_bwd_impl(const int32_t* rowptr, const int32_t* col, const i
     bool dma = pl.bf16x3 && (bwd4_env() || (flags & GML_DMA_RING)) && (S == 8 || S == 4) && xvec_strict && p.gvec && !(flags & GML_ACCUM) &&
                (!dx || p.dxvec || dz == nullptr) && (num_rows + 16) * (ldg > ldx ? ldg : ldx) * 4 < (int64_t)INT32_MAX;
     if (flags & GML_DVAL_ACCUM) {                            /* dval += : the 8-wave bf16x3 kernel's copy-out only */
-        if (!pl.bf16x3 || (S == 8 && nob == 2)) return GML_E_UNSUPPORTED;   /* (not compiled into the ZINC shape class) */
+        /* (not compiled into the classes that store dval straight from the edge loop -- DIRECT in gml_spectconv_bwd3_impl.h: the ZINC
+           shape class, and the one-launch 33 .. 48-feature class, which used to take the flag and write dval = ) */
+        if (!pl.bf16x3 || (S == 8 && nob == 2) || nfb == 3) return GML_E_UNSUPPORTED;
         dma = false;
     }
     if (dma) {

@@ -58,7 +58,9 @@ enum {
                          kernel stages at once (the caller knows the maximum from its group records): take the chunked ring kernel
                          (gml_k_spectconv_fwd4), which walks such groups in edge chunks instead of gathering from global memory */
     GML_DVAL_ACCUM = 128, /* gml_spectconv_bwd (8-wave bf16x3 kernel): dval += instead of dval = -- the second of two launches over
-                         slices of the input features (48-wide layers: features 0..31, then 32..47; dval is linear in x) */
+                         slices of the input features (48-wide layers: features 0..31, then 32..47; dval is linear in x).
+                         GML_E_UNSUPPORTED where the selected kernel has no such copy-out: the 64-row kernel, S = 8 with 17 .. 32 output
+                         columns, and 33 .. 48 input features in one launch */
     GML_FWD_ONEWIN = 256, /* gml_spectconv_fwd, 48-feature shapes on the chunked ring kernel: ONE staged X window instead of two, twice the
                          edges per work item -- for batches whose groups need edge chunks (the caller knows the batch's largest group) */
     GML_DMA_RING = 32,  /* gml_spectconv_bwd / _bwd_mix: take the LDS-DMA landing-ring kernel (bwd4) where it applies; the
@@ -311,6 +313,14 @@ int gml_spectconv_fwd_epi(const int32_t* rowptr, const int32_t* col, const int32
 int gml_spectconv_bwd_group_rows(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags);
 size_t gml_spectconv_bwd_workspace_bytes(int64_t num_rows, int32_t S, int32_t Fin, int32_t Fout,
                                          int32_t max_group_edges, int32_t max_group_window, uint32_t flags);
+/* Host-only: edges / target-window rows of ONE group (ints 1 / 3 of its record) the kernel this shape and these flags select keeps
+ * in its staging: the 8-wave kernel's register-batched bounds, 1,024 / 192 for the 64-row kernel, the ring's capacities less its
+ * alignment slack (3 edges, 7 rows) with GML_DMA_RING where the ring applies.  A group beyond either is still served -- by the
+ * kernel's unstaged loops, or with GML_DMA_RING by the launch taking the 8-wave kernel instead of its ring form -- with the same
+ * results; what refuses a batch is the LDS plan alone (gml_spectconv_bwd_workspace_bytes = 0).  0: no fused backward for the shape,
+ * or a kernel form without a staged road (the 64-row kernel at S % 4 != 0). */
+int32_t gml_spectconv_bwd_stage_edges(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags);
+int32_t gml_spectconv_bwd_stage_window(int32_t S, int32_t Fin, int32_t Fout, uint32_t flags);
 int gml_spectconv_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* ginfo, const float* val,
                       const float* x, int64_t ldx, const float* g, int64_t ldg, const float* w,
                       float* dx, int64_t lddx, float* dval, float* dw,

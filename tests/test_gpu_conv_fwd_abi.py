@@ -149,9 +149,9 @@ class _Out(object):
     """an output buffer of _conv_ref.alloc() on the device; `off4`: the output starts 4 bytes past a 16-byte boundary, behind its
     4 guard floats"""
 
-    def __init__(self, dev, n, ncols, ldo, off4=False, out0=None):
-        self.n, self.ncols, self.ldo, self.lead = n, ncols, ldo, 1 if off4 else 0
-        self.host, self.off = R.alloc(n, ncols, ldo, off4, out0)
+    def __init__(self, dev, n, ncols, ldo, off4=False, out0=None, guard_rows=R.GUARD_ROWS):
+        self.n, self.ncols, self.ldo, self.lead, self.guard_rows = n, ncols, ldo, 1 if off4 else 0, guard_rows
+        self.host, self.off = R.alloc(n, ncols, ldo, off4, out0, guard_rows)
         self.t = _up(self.host, dev, self.lead)
         assert (self.t.data_ptr() + 4 * (self.lead + self.off)) % 16 == (4 if off4 else 0)
 
