@@ -107,6 +107,14 @@ SIGNATURES = {
     'gml_gnnml1_fwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     'gml_gnnml1_bwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _i32,
                                       _p, _i64, _p, _i64, _p, _i64, _p]),
+    'gml_gnnml1_sum_supported': (_i32, [_i32, _i32, _i32, _i32]),
+    'gml_gnnml1_sum_g4_cols': (_i32, [_i32, _i32, _i32]),
+    'gml_gnnml1_sum_dw_floats': (_i64, [_i32, _i32, _i32, _i32]),
+    'gml_gnnml1_sum_dw_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    'gml_gnnml1_sum_dw': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),
+    'gml_gnnml1_sum_fwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _i64, _p, _i64, _p]),
+    'gml_gnnml1_sum_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p,
+                                          _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     'gml_edge_mlp_bwd_parts': (_i64, [_i64, _i32, _i32, _i32, _i32]),
     'gml_edge_mlp_plan': (_i32, [_i32, _i32, _i32, _i32, _u32]),
     'gml_edge_mlp_wide_fwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),

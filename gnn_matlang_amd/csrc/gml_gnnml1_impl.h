@@ -25,7 +25,7 @@
 // so that the lane (row, kq) receives columns 16 nb + 4 kq .. + 3 of ITS row: results of one MFMA chain are operands of the next
 // without a shuffle, and rows move as 16-byte accesses.
 #pragma once
-#include "gml_common.h"
+#include "gml_gnnml1_rows.h"
 
 #ifndef G1_M3
 #define G1_M3 0
@@ -37,18 +37,6 @@
 #define G1_K(stem) gml_k_gnnml1_##stem
 #endif
 
-struct GmlG1Params {
-    const int32_t* rowptr; const int32_t* col; const float* val;      // fwd: target-keyed CSR; bwd: source-keyed (rowptr_t, col_t, val_t)
-    const float* x; int64_t ldx;
-    const float* w1; const float* b1; const float* wc; const float* bc;
-    const float* w2; const float* b2; const float* w3; const float* b3;
-    float* out; int64_t ldo;                                             // fwd: written; bwd: the saved output (read)
-    const float* gout; int64_t ldgo;
-    float* dx; int64_t lddx; float* g4; int64_t ldg4; float* q; int64_t ldq;
-    int64_t nrows; int32_t Fin, n1, n2, n3, mode, act, ntiles;
-};
-
-#define G1_NW 8
 template <int FPL>
 struct GmlG1Cfg {
     static constexpr int FP = 4 * FPL;
@@ -57,10 +45,6 @@ struct GmlG1Cfg {
     // transposed-form fragments for dx: [fb][K block][4][64]: lane (f = l & 15, k = l >> 4) holds W[16 nb + 4 k + reg][16 fb + f]
     __host__ __device__ static int tr_floats(int nkb) { return (FP / 16) * nkb * 4 * 64; }
 };
-
-__device__ __forceinline__ float g1_act(float v, int act) { return act == 0 ? gml_tanh(v) : fmaxf(v, 0.f); }
-// derivative of the activation from its OUTPUT value (tanh: 1 - y^2; relu: y > 0)
-__device__ __forceinline__ float g1_dact_out(float y, int act) { return act == 0 ? fmaf(-y, y, 1.f) : (y > 0.f ? 1.f : 0.f); }
 
 template <int FPL>
 __device__ __forceinline__ void g1_fill_fwd(float* dst, const float* w, int n, int Fin, bool conv, int nb0, int nblk, int tid, int nt) {
@@ -97,33 +81,6 @@ __device__ __forceinline__ f32x4 g1_block(const float* wl, int blk, int lane, co
 #pragma unroll
     for (int j = 0; j < FPL; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[j * 64], b[j], acc, 0, 0, 0);
     return acc;
-}
-
-__device__ __forceinline__ f32x4 g1_bias4(const float* b, int c0, int n) {
-    f32x4 r;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) r[u] = (b && c0 + u < n) ? b[c0 + u] : 0.f;
-    return r;
-}
-
-__device__ __forceinline__ void g1_store4(float* base, int64_t ld, int64_t row, int c0, int n, bool valid, f32x4 v) {
-    if (!valid) return;
-    float* p = base + row * ld + c0;
-    if (c0 + 4 <= n && ld % 4 == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0)) { *reinterpret_cast<f32x4*>(p) = v; return; }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-        if (c0 + u < n) p[u] = v[u];
-}
-
-__device__ __forceinline__ f32x4 g1_load4(const float* base, int64_t ld, int64_t row, int c0, int n, bool valid) {
-    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!valid) return v;
-    const float* p = base + row * ld + c0;
-    if (c0 + 4 <= n && ld % 4 == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0)) return *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-        if (c0 + u < n) v[u] = p[u];
-    return v;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ forward

@@ -795,6 +795,82 @@ class GNNML1BlockFunction(torch.autograd.Function):
         return dx, None, None, dw1, db1, dwc.view(1, Fin, n2), dbc, dw2, db2, dw3, db3, None, None
 
 
+def gnnml1_sum_supported(x, Fin, n1, n3):
+    """the sum-and-factors block (GNNML1SumBlockFunction) serves this input: n1 = n2 <= 128, n3 <= 64, Fin <= 192"""
+    return (x.is_cuda and x.dtype == torch.float32 and not _os.environ.get('GML_NO_GNNML1_FUSED')
+            and bool(_lib.lib().gml_gnnml1_sum_supported(int(Fin), int(n1), int(n1), int(n3))))
+
+
+class GNNML1SumBlockFunction(torch.autograd.Function):
+    """One GNNML1 block of enzymes_contfeat.py:284-346 (csrc/gml_gnnml1_sum.hip): [act(fc_i1 x) + act(conv_i1 x) | act(fc_i2 x) *
+    act(fc_i3 x)], [N, n1 + n3] with n1 = n2; act 0 tanh / 1 relu.  One launch forward; backward = phase 1 (g4), q = A dc, dx (only
+    when x needs it) and one weight-gradient pass + fold.  relu: the forward records the two activation patterns of the sum (one byte
+    per 4 columns, saved for backward) and phase 1 reads them; tanh, or record=False: phase 1 recomputes a and c (the same bits).
+    Inputs up to 192 wide, n1 <= 128, n3 <= 64 (gnnml1_sum_supported); rows of any stride.  val: per-edge values in TARGET order or
+    None for ones; they carry no gradient here.  Exact fp32 products."""
+
+    @staticmethod
+    def forward(ctx, x, csr, val, w1, b1, wc, bc, w2, b2, w3, b3, act, record=True):
+        x = _f32rows(x, 'x')
+        N, Fin = int(x.size(0)), int(x.size(1))
+        n1, n2, n3 = int(w1.size(0)), int(wc.size(-1)), int(w2.size(0))
+        w1, w2, w3, wc = _f32c(w1, 'fc1.weight'), _f32c(w2, 'fc2.weight'), _f32c(w3, 'fc3.weight'), _f32c(wc, 'conv.weight')
+        C = n1 + n3
+        dev = x.device
+        if val is not None:
+            val = _f32c(val.reshape(-1), 'edge_attr')
+        with torch.cuda.device(dev):
+            out = torch.empty(N, C, dtype=torch.float32, device=dev)
+            npat = (n1 + 15) // 16 * 4
+            pat = torch.empty(N, npat, dtype=torch.uint8, device=dev) if (int(act) == 1 and record) else None
+            with _Timed('gnnml1_sum_fwd', 4 * (N * (Fin + C) + csr.E + N + Fin * (n1 + n2 + 2 * n3)) if PROFILE is not None else 0, 0):
+                _lib.call('gml_gnnml1_sum_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(x), int(x.stride(0)), N, Fin,
+                          _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, int(act),
+                          _ptr(out), C, _ptr(pat), npat, _stream(dev))
+        ctx.csr, ctx.act, ctx.dims = csr, int(act), (N, Fin, n1, n2, n3, C)
+        ctx.has_b = (b1 is not None, bc is not None, b2 is not None, b3 is not None)
+        ctx.save_for_backward(x, val, w1, b1, wc, bc, w2, b2, w3, b3, pat)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, val, w1, b1, wc, bc, w2, b2, w3, b3, pat = ctx.saved_tensors
+        N, Fin, n1, n2, n3, C = ctx.dims
+        csr, act = ctx.csr, ctx.act
+        dev = x.device
+        gout = _f32rows(gout, 'grad_output')
+        L = _lib.lib()
+        ng4 = int(L.gml_gnnml1_sum_g4_cols(n1, n2, n3))
+        p1, p3 = (n1 + 15) // 16 * 16, (n3 + 15) // 16 * 16
+        need_x = ctx.needs_input_grad[0]
+        with torch.cuda.device(dev):
+            val_t = csr.to_source_order(val.view(-1, 1)).view(-1) if val is not None else None
+            g4 = torch.empty(N, ng4, dtype=torch.float32, device=dev)
+            q = torch.empty(N, p1, dtype=torch.float32, device=dev)
+            dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if need_x else None
+            with _Timed('gnnml1_sum_bwd', 4 * (N * (Fin + C + (Fin if need_x else 0) + ng4 + p1) + 2 * (csr.E + N)) if PROFILE is not None else 0, 0):
+                _lib.call('gml_gnnml1_sum_bwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t),
+                          _ptr(x), int(x.stride(0)), _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2,
+                          _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, act, _ptr(pat), p1 // 4, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p1,
+                          _stream(dev))
+            with _Timed('gnnml1_sum_dw'):
+                nflat = int(L.gml_gnnml1_sum_dw_floats(Fin, n1, n2, n3))
+                nws = int(L.gml_gnnml1_sum_dw_workspace_bytes(N, Fin, n1, n2, n3))
+                flat = torch.empty(nflat, dtype=torch.float32, device=dev)
+                ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=dev)
+                _lib.call('gml_gnnml1_sum_dw', _ptr(x), int(x.stride(0)), _ptr(g4), ng4, _ptr(q), p1, N, Fin, n1, n2, n3, _ptr(flat),
+                          _ptr(ws), ws.numel(), _stream(dev))
+                e1, e2, e3, e4 = n1 * Fin, n1 * Fin + n3 * Fin, n1 * Fin + 2 * n3 * Fin, n1 * Fin + 2 * n3 * Fin + Fin * n2
+                dw1, dw2, dw3, dwc = flat[:e1].view(n1, Fin), flat[e1:e2].view(n3, Fin), flat[e2:e3].view(n3, Fin), flat[e3:e4].view(Fin, n2)
+                sums = flat[e4:]
+        hb1, hbc, hb2, hb3 = ctx.has_b
+        db1 = sums[:n1] if hb1 else None                          # column sums of g4 = [da | dc | df2 | df3]
+        dbc = sums[p1:p1 + n2] if hbc else None
+        db2 = sums[2 * p1:2 * p1 + n3] if hb2 else None
+        db3 = sums[2 * p1 + p3:2 * p1 + p3 + n3] if hb3 else None
+        return dx, None, None, dw1, db1, dwc.view(1, Fin, n2), dbc, dw2, db2, dw3, db3, None, None
+
+
 def xty_wide(a, b):
     """a^T b for a tall wide a [n, p <= 4096] and b [n, q <= 128] on the bf16 matrix cores (bf16x3 products; gml_xty_wide): the dense
     block's dW = Hcat^T g; None if outside the kernel range."""

@@ -377,6 +377,21 @@ def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
                                         fc3.weight, fc3.bias, mode, act)
 
 
+def _gnnml1_sum_block(x, csr, fc1, conv, fc2, fc3, act):
+    """the sum-and-factors block as one fused launch (functional.GNNML1SumBlockFunction, csrc/gml_gnnml1_sum.hip) or None when the
+    widths are outside the kernel (input > 192, n1 = n2 > 128, n3 > 64) or the conv is not the plain K = 1 form.  Unit edge values.
+    No row-count gate: the fused road's 90th percentile is below the composition's 10th for both blocks at 1.7 k and at 500 k rows
+    (tools/bench_gnnml1_sum.py, profiles/gnnml1_sum.json, DESIGN s4.15)."""
+    from . import functional as Fn
+    if conv.weight.size(0) != 1 or conv.selfconn or conv.depthwise:
+        return None
+    Fin, n1, n2, n3 = int(x.size(1)), int(fc1.weight.size(0)), int(conv.weight.size(2)), int(fc2.weight.size(0))
+    if n1 != n2 or not Fn.gnnml1_sum_supported(x, Fin, n1, n3):
+        return None
+    return Fn.GNNML1SumBlockFunction.apply(x, csr, None, fc1.weight, fc1.bias, conv.weight, conv.bias, fc2.weight, fc2.bias,
+                                           fc3.weight, fc3.bias, act)
+
+
 class GNNML1Mutag(torch.nn.Module):
     """mutag.py:214-266: three blocks of [relu(fc x) | relu(SpectConv_{S=1}(x)) | relu(fc x)*relu(fc x)] + BN."""
 
@@ -476,14 +491,16 @@ class GNNML1(torch.nn.Module):
 
 
 class GNNML1Blocks(torch.nn.Module):
-    """The GNNML1 of Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343 and
-    proteins.py:208-257 as one class: `nblocks` concatenating blocks
+    """The GNNML1 of Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343,
+    proteins.py:208-257 and enzymes_contfeat.py:284-346 as one class: `nblocks` concatenating blocks
          form 'product'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]              (kernel mode 1)
          form 'factors'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]        (mode 2)
          form 'tanh_factors':  x <- cat[ act(fc_i1 x), act(conv_i1 x), tanh(fc_i2 x) * tanh(fc_i3 x) ]      (mode 3, ptc.py:311)
+         form 'sum_factors' :  x <- cat[ act(fc_i1 x) + act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]       (mode 4, enzymes_contfeat.py:336;
+                               n1 == n2, block output n1 + n3 wide; csrc/gml_gnnml1_sum.hip: inputs up to 192, n1 <= 128, n3 <= 64)
     of widths = (n1, n2, n3) (fc_i1 -> n1, conv_i1 = SpectConv(K = 1, selfconn=False) over the raw adjacency with unit edge values
-    -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (csrc/gml_gnnml1.hip, block inputs up to 144 wide) with the composition
-    as the road of any other shape.  bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn>
+    -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (csrc/gml_gnnml1.hip, block inputs up to 144 wide; form 'sum_factors':
+    _gnnml1_sum_block, csrc/gml_gnnml1_sum.hip, up to 192 wide) with the composition as the road of any other shape.  bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn>
     are DECLARED (the scripts declare some they never call: the reference's checkpoints load with strict=True).  dropout > 0:
     F.dropout in front of every block in training.  pool: a name or a tuple of names (_pool).  head:
          'mlp32'      : fc2(relu(fc1 x)), fc1: nin -> 32                       (Zinc12k.py:306-307, freqclass.py)
@@ -491,7 +508,7 @@ class GNNML1Blocks(torch.nn.Module):
          'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)
     A padded static batch hands _node_valid to the BatchNorms in training, as GNNML1Mutag does."""
 
-    _MODES = dict(product=1, factors=2, tanh_factors=3)
+    _MODES = dict(product=1, factors=2, tanh_factors=3, sum_factors=4)
 
     def __init__(self, ninp, widths, nblocks, form='product', act='relu', bn_after=(), nbn=0, pool='add', head='mlp32', hidden=0,
                  nclass=1, dropout=0.0):
@@ -499,13 +516,15 @@ class GNNML1Blocks(torch.nn.Module):
         n1, n2, n3 = (int(w) for w in widths)
         if form not in self._MODES or act not in ('tanh', 'relu') or head not in ('mlp32', 'lin2', 'log_softmax'):
             raise ValueError('form: %s; act: tanh / relu; head: mlp32 / lin2 / log_softmax' % ' / '.join(self._MODES))
+        if form == 'sum_factors' and n1 != n2:
+            raise ValueError("form='sum_factors' adds act(fc_i1 x) and act(conv_i1 x): widths[0] == widths[1]")
         if any(not 1 <= int(b) <= min(nblocks, nbn) for b in bn_after):
             raise ValueError('bn_after names blocks 1 .. nblocks whose BatchNorm is declared (nbn)')
         if head == 'lin2' and not hidden > 0:
             raise ValueError("head='lin2' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)")
         self.nblocks, self.form, self.act, self.pool, self.head = int(nblocks), form, act, pool, head
         self.bn_after = frozenset(int(b) for b in bn_after)
-        nin = n1 + n2 + n3
+        nin = n1 + n3 if form == 'sum_factors' else n1 + n2 + n3
         for i in range(1, nbn + 1):
             setattr(self, 'bn%d' % i, BatchNorm1d(nin))
         for i, fin in enumerate([ninp] + [nin] * (nblocks - 1), start=1):
@@ -524,11 +543,16 @@ class GNNML1Blocks(torch.nn.Module):
     def _block(self, i, x, csr, ones):
         g = lambda n: getattr(self, n % i)
         mode, actid = self._MODES[self.form], 0 if self.act == 'tanh' else 1
-        y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), mode, actid)
+        if mode == 4:
+            y = _gnnml1_sum_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), actid)
+        else:
+            y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), mode, actid)
         if y is not None:
             return y
         A = torch.tanh if actid == 0 else F.relu
         a, c, f2, f3 = g('fc%d1')(x), g('conv%d1')(x, csr, ones), g('fc%d2')(x), g('fc%d3')(x)
+        if mode == 4:
+            return torch.cat([A(a) + A(c), A(f2) * A(f3)], 1)
         h = A(f2 * f3) if mode == 1 else (A(f2) * A(f3) if mode == 2 else torch.tanh(f2) * torch.tanh(f3))
         return torch.cat([A(a), A(c), h], 1)
 
@@ -590,6 +614,15 @@ def enzymes_gnnml1(ninp=4, dropout=0.1):   # enzymes.py:278-343 (four blocks 16 
 def proteins_gnnml1(ninp=4, dropout=0.1):  # proteins.py:208-257 (two blocks 64 | 64 | 16, factor form, relu; bn1, bn2 declared, never called; (mean, max) pools, log_softmax(fc2: 288 -> 2))
     return GNNML1Blocks(ninp, (64, 64, 16), 2, form='factors', act='relu', nbn=2, pool=('mean', 'max'), head='log_softmax',
                         nclass=2, dropout=dropout)
+
+
+def enzymes_contfeat_gnnml1(ninp=22, dropout=0.2):
+    """enzymes_contfeat.py:284-346: two blocks 128 | 128 | 64 of [relu + relu | relu . relu] (192 wide), a BatchNorm after each,
+    (mean, max) pools, log_softmax(fc2: 384 -> 6); the input: the 21 continuous ENZYMES features and the degree column
+    (readers.load_tu(contfeat=True), standardize_tu).  bn1 / bn2 are 192 wide: beyond the masked BatchNorm kernel (C <= 64), so a padded
+    static batch in TRAINING raises BatchNorm1d's NotImplementedError, as ptc_gnnml1 does; plain batches and evaluation run."""
+    return GNNML1Blocks(ninp, (128, 128, 64), 2, form='sum_factors', act='relu', bn_after=(1, 2), nbn=2, pool=('mean', 'max'),
+                        head='log_softmax', nclass=6, dropout=dropout)
 
 
 def sr25_gnnml1(ninp=2):                   # sr25.py:192-246 (nout = 64, sum form, tanh, add-pool, fc1 -> 10)

@@ -187,10 +187,11 @@ def exp_classify_splits(graphs):
 _TU_COLS = dict(ptc=None, enzymes=3, proteins=3)
 
 
-def load_tu(path, name):
+def load_tu(path, name, contfeat=False):
     """libs/utils.py:24-174: graphs of ptc.mat / enzymes.mat / proteins.mat (name 'ptc' | 'enzymes' | 'proteins') as
     (x, edge_index, y): edges where A > 0, x = the kept feature columns as float32, y = the int64 class label from Y ([G, 1] in
-    ptc.mat and proteins.mat, [1, G] in enzymes.mat)."""
+    ptc.mat and proteins.mat, [1, G] in enzymes.mat).  contfeat=True keeps EVERY column of F for 'enzymes' and 'proteins'
+    (libs/utils.py:105-107, 157-160: the continuous attributes behind the three label columns; enzymes_contfeat.py)."""
     if name not in _TU_COLS:
         raise ValueError("load_tu: name must be 'ptc', 'enzymes' or 'proteins', got %r" % (name,))
     a = read_mat(path)
@@ -198,8 +199,25 @@ def load_tu(path, name):
     Y = np.asarray(a['Y']).astype(np.int64).reshape(-1)
     if Y.size != A.size:
         raise ValueError('%s: %d labels for %d graphs' % (path, Y.size, A.size))
-    k = _TU_COLS[name]
+    k = None if contfeat else _TU_COLS[name]
     return [(np.asarray(F[i] if k is None else F[i][:, 0:k], dtype=np.float32), _edges(A[i]), np.int64(Y[i])) for i in range(A.size)]
+
+
+def standardize_tu(graphs, train_idx):
+    """enzymes_contfeat.py:366-370: x <- (x - mean) / std of EVERY graph, mean and std (unbiased, as torch.std) per column over
+    the nodes of the training graphs `train_idx`.  graphs: the tuples of load_tu or the records of SpectralDesign.design_many
+    (the script standardises after the degree column is appended).  Returns (graphs, (mean, std)): new tuples / records with
+    float32 x, the statistics as float64 arrays."""
+    xs = lambda g: np.asarray(g['x'] if isinstance(g, dict) else g[0])
+    tr = np.concatenate([xs(graphs[int(i)]) for i in train_idx], 0).astype(np.float64)
+    if tr.shape[0] < 2:
+        raise ValueError('standardize_tu: the training graphs have %d nodes; the unbiased std needs two' % tr.shape[0])
+    mean, std = tr.mean(0), tr.std(0, ddof=1)
+    out = []
+    for g in graphs:
+        x = ((xs(g).astype(np.float64) - mean) / std).astype(np.float32)
+        out.append(dict(g, x=x) if isinstance(g, dict) else (x,) + tuple(g[1:]))
+    return out, (mean, std)
 
 
 def load_twodgrid(path):

@@ -868,6 +868,39 @@ int gml_gnnml1_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* v
                    const float* b3, int32_t n3, int32_t mode, int32_t act, float* dx, int64_t lddx, float* g4, int64_t ldg4,
                    float* q, int64_t ldq, gml_stream_t stream);
 
+/* GNNML1 block in the sum-and-factors form (block mode 4; csrc/gml_gnnml1_sum.hip) -- enzymes_contfeat.py:284-346:
+ *   out [N, n1 + n3] = [ act(a) + act(c) | act(f2) * act(f3) ],   a, c, f2, f3 and the arguments as for gml_gnnml1_fwd,  n1 == n2.
+ * Fin <= 192, n1 = n2 <= 128, n3 <= 64 (gml_gnnml1_sum_supported), else GML_E_UNSUPPORTED; n1 != n2: GML_E_BADARG.  Rows of any stride;
+ * exact fp32 products, aggregation in edge order, no atomics.  The weight image is split over the grid's second dimension by column
+ * groups (64 columns of fc_i1 and conv_i1 each, one group for fc_i2 / fc_i3): at most 98,304 bytes of LDS per workgroup.
+ * pattern (optional, [N, ldp >= 4 ceil(n1 / 16)] bytes): the forward records where a and c are positive -- byte j of a row: bit u = a > 0,
+ * bit 4 + u = c > 0 of column 4 j + u -- because the sum does not tell the two relu patterns apart.
+ * Backward: with the forward's pattern (act = 1 only, else GML_E_BADARG) da and dc come from gout and the bits; with pattern = NULL
+ * (tanh needs the values) a and c are RECOMPUTED from x over the TARGET-keyed view (rowptr / col / val, as the forward).  f2, f3 are
+ * always recomputed; no forward output is read.  q and dx use the SOURCE-keyed view (rowptr_t / col_t / val_t):
+ *   g4 [N, ldg4 >= gml_gnnml1_sum_g4_cols()] = [da | dc | df2 | df3],  da = g act'(a), dc = g act'(c); each part 16 ceil(n / 16) wide
+ *   q  [N, ldq >= 16 ceil(n1 / 16)] = A dc;      dx (optional) = da W1 + q Wc^T + df2 W2 + df3 W3
+ * g4, q: 16-byte aligned, ldg4 and ldq multiples of 4.  gml_gnnml1_sum_dw: all weight gradients and the column sums of g4 (the bias
+ * gradients) in one pass over the rows + one ordered fold:
+ *   out_flat = [dW1 (n1 x Fin) | dW2 (n3 x Fin) | dW3 (n3 x Fin) | dWc (Fin x n2) | column sums of g4 (gml_gnnml1_sum_g4_cols floats)] */
+int gml_gnnml1_sum_supported(int32_t Fin, int32_t n1, int32_t n2, int32_t n3);
+int gml_gnnml1_sum_g4_cols(int32_t n1, int32_t n2, int32_t n3);
+int gml_gnnml1_sum_fwd(const int32_t* rowptr, const int32_t* col, const float* val, const float* x, int64_t ldx, int64_t num_rows,
+                       int32_t Fin, const float* w1, const float* b1, int32_t n1, const float* wc, const float* bc, int32_t n2,
+                       const float* w2, const float* b2, const float* w3, const float* b3, int32_t n3, int32_t act,
+                       float* out, int64_t ldo, uint8_t* pattern, int64_t ldp, gml_stream_t stream);
+int gml_gnnml1_sum_bwd(const int32_t* rowptr, const int32_t* col, const float* val, const int32_t* rowptr_t, const int32_t* col_t,
+                       const float* val_t, const float* x, int64_t ldx, const float* gout, int64_t ldgo, int64_t num_rows,
+                       int32_t Fin, const float* w1, const float* b1, int32_t n1, const float* wc, const float* bc, int32_t n2,
+                       const float* w2, const float* b2, const float* w3, const float* b3, int32_t n3, int32_t act,
+                       const uint8_t* pattern, int64_t ldp, float* dx, int64_t lddx, float* g4, int64_t ldg4, float* q, int64_t ldq,
+                       gml_stream_t stream);
+int64_t gml_gnnml1_sum_dw_floats(int32_t Fin, int32_t n1, int32_t n2, int32_t n3);
+size_t gml_gnnml1_sum_dw_workspace_bytes(int64_t num_rows, int32_t Fin, int32_t n1, int32_t n2, int32_t n3);
+int gml_gnnml1_sum_dw(const float* x, int64_t ldx, const float* g4, int64_t ldg4, const float* q, int64_t ldq, int64_t num_rows,
+                      int32_t Fin, int32_t n1, int32_t n2, int32_t n3, float* out_flat, void* ws, size_t ws_bytes,
+                      gml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
