@@ -719,72 +719,101 @@ def xty(a, b):
 
 
 def gnnml1_block_supported(x, Fin, n1, n2, n3, mode):
-    return (x.is_cuda and x.dtype == torch.float32 and not _os.environ.get('GML_NO_GNNML1_FUSED')
-            and bool(_lib.lib().gml_gnnml1_supported(int(Fin), int(n1), int(n2), int(n3), int(mode))))
+    """the fused block (GNNML1BlockFunction) serves this input.  Modes 0..3: inputs up to 144 wide, parts up to 64; mode 4 (its own
+    kernel family): n1 = n2 <= 128, n3 <= 64, Fin <= 192"""
+    if not (x.is_cuda and x.dtype == torch.float32) or _os.environ.get('GML_NO_GNNML1_FUSED'):
+        return False
+    if int(mode) == 4:
+        return bool(_lib.lib().gml_gnnml1_sum_supported(int(Fin), int(n1), int(n2), int(n3)))
+    return bool(_lib.lib().gml_gnnml1_supported(int(Fin), int(n1), int(n2), int(n3), int(mode)))
 
 
 class GNNML1BlockFunction(torch.autograd.Function):
-    """One GNNML1 block (sr25.py:231-240, mnist75.py:296-318, mutag.py:253-262) as ONE launch forward and one launch + four gml_xty
-    backward (csrc/gml_gnnml1.hip): a = fc_i1 x, c = conv_i1 x (SpectConv K = 1), f2 = fc_i2 x, f3 = fc_i3 x;
+    """One GNNML1 block (sr25.py:231-240, mnist75.py:296-318, mutag.py:253-262, enzymes_contfeat.py:284-346) as ONE launch forward;
+    backward = one launch (g4, q = A dc, dx only when x needs it) and one weight-gradient pass + fold.  a = fc_i1 x, c = conv_i1 x
+    (SpectConv K = 1), f2 = fc_i2 x, f3 = fc_i3 x;
     mode 0: act(a + c + f2 f3); 1: [act a | act c | act(f2 f3)]; 2: [act a | act c | act f2 . act f3]; 3: [act a | act c | tanh f2 . tanh f3]
-    (ptc.py:311); act 0 tanh / 1 relu.  Inputs up to 144 wide, parts up to 64 (gnnml1_block_supported); rows of any stride.
-    val: per-edge values in TARGET order ([E] / [E, 1]) or None for ones (the scripts pass torch.ones); they carry no gradient here
-    (the module takes the unfused road when edge_attr requires one).  Exact fp32 products."""
+    (ptc.py:311); 4: [act a + act c | act f2 . act f3] with n1 = n2; act 0 tanh / 1 relu.  Modes 0..3 (csrc/gml_gnnml1.hip): inputs up
+    to 144 wide, parts up to 64; mode 4 (csrc/gml_gnnml1_sum.hip): inputs up to 192 wide, n1 <= 128, n3 <= 64
+    (gnnml1_block_supported); rows of any stride.  Mode 4 differs in three places: its entry points, the pattern buffer and what is
+    saved.  With relu its forward records the two activation patterns of the sum (one byte per 4 columns, saved for backward instead of
+    `out`) and phase 1 reads them; tanh, or record=False: phase 1 recomputes a and c (the same bits).  record has no effect in modes
+    0..3.  val: per-edge values in TARGET order ([E] / [E, 1]) or None for ones (the scripts pass torch.ones); they carry no gradient
+    here (the module takes the unfused road when edge_attr requires one).  Exact fp32 products."""
 
     @staticmethod
-    def forward(ctx, x, csr, val, w1, b1, wc, bc, w2, b2, w3, b3, mode, act):
+    def forward(ctx, x, csr, val, w1, b1, wc, bc, w2, b2, w3, b3, mode, act, record=True):
         x = _f32rows(x, 'x')
+        mode, act = int(mode), int(act)
         N, Fin = int(x.size(0)), int(x.size(1))
         n1, n2, n3 = int(w1.size(0)), int(wc.size(-1)), int(w2.size(0))
         w1, w2, w3, wc = _f32c(w1, 'fc1.weight'), _f32c(w2, 'fc2.weight'), _f32c(w3, 'fc3.weight'), _f32c(wc, 'conv.weight')
-        C = n1 if mode == 0 else n1 + n2 + n3
+        C = n1 if mode == 0 else (n1 + n3 if mode == 4 else n1 + n2 + n3)
         dev = x.device
         if val is not None:
             val = _f32c(val.reshape(-1), 'edge_attr')
+        nbytes = 4 * (N * (Fin + C) + csr.E + N + Fin * (n1 + n2 + 2 * n3)) if PROFILE is not None else 0
+        head = (_ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(x), int(x.stride(0)), N, Fin,
+                _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3)
         with torch.cuda.device(dev):
             out = torch.empty(N, C, dtype=torch.float32, device=dev)
-            with _Timed('gnnml1_fwd', 4 * (N * (Fin + C) + csr.E + N + Fin * (n1 + n2 + 2 * n3)) if PROFILE is not None else 0, 0):
-                _lib.call('gml_gnnml1_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(x), int(x.stride(0)), N, Fin,
-                          _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, int(mode), int(act),
-                          _ptr(out), C, _stream(dev))
-        ctx.csr, ctx.mode, ctx.act, ctx.dims = csr, int(mode), int(act), (N, Fin, n1, n2, n3, C)
+            if mode == 4:
+                npat = (n1 + 15) // 16 * 4
+                pat = torch.empty(N, npat, dtype=torch.uint8, device=dev) if (act == 1 and record) else None
+                with _Timed('gnnml1_sum_fwd', nbytes, 0):
+                    _lib.call('gml_gnnml1_sum_fwd', *head, act, _ptr(out), C, _ptr(pat), npat, _stream(dev))
+            else:
+                with _Timed('gnnml1_fwd', nbytes, 0):
+                    _lib.call('gml_gnnml1_fwd', *head, mode, act, _ptr(out), C, _stream(dev))
+        ctx.csr, ctx.mode, ctx.act, ctx.dims = csr, mode, act, (N, Fin, n1, n2, n3, C)
         ctx.has_b = (b1 is not None, bc is not None, b2 is not None, b3 is not None)
-        ctx.save_for_backward(x, val, w1, wc, w2, b2, w3, b3, out)
+        # mode 4 recomputes a and c from the biases (or reads the pattern) and never reads `out`; modes 0..3 read `out`
+        ctx.save_for_backward(x, val, w1, wc, w2, b2, w3, b3, *((b1, bc, pat) if mode == 4 else (out,)))
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        x, val, w1, wc, w2, b2, w3, b3, out = ctx.saved_tensors
+        x, val, w1, wc, w2, b2, w3, b3, *rest = ctx.saved_tensors
         N, Fin, n1, n2, n3, C = ctx.dims
         csr, mode, act = ctx.csr, ctx.mode, ctx.act
         dev = x.device
         gout = _f32rows(gout, 'grad_output')
         L = _lib.lib()
-        ng4 = int(L.gml_gnnml1_g4_cols(n1, n2, n3, mode))
+        sfx, m = ('_sum', ()) if mode == 4 else ('', (mode,))          # the entry points of mode 4 take no mode argument
+        ng4 = int(getattr(L, 'gml_gnnml1%s_g4_cols' % sfx)(n1, n2, n3, *m))
         p1, p2, p3 = (n1 + 15) // 16 * 16, (n2 + 15) // 16 * 16, (n3 + 15) // 16 * 16
         need_x = ctx.needs_input_grad[0]
         with torch.cuda.device(dev):
             val_t = csr.to_source_order(val.view(-1, 1)).view(-1) if val is not None else None
             g4 = torch.empty(N, ng4, dtype=torch.float32, device=dev)
-            q = torch.empty(N, p2, dtype=torch.float32, device=dev)
+            q = torch.empty(N, p2, dtype=torch.float32, device=dev)                   # (mode 4: p2 == p1)
             dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if need_x else None
-            with _Timed('gnnml1_bwd', 4 * (N * (Fin + 2 * C + (Fin if need_x else 0) + ng4 + p2) + csr.E + N) if PROFILE is not None else 0, 0):
-                _lib.call('gml_gnnml1_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t), _ptr(x), int(x.stride(0)), _ptr(out), C,
-                          _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), n1, _ptr(wc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3,
-                          mode, act, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p2, _stream(dev))
-            oa, oc = 0, p1
-            o2 = p1 if mode == 0 else p1 + p2
-            o3 = o2 + p3
-            with _Timed('gnnml1_dw'):
-                nflat = int(L.gml_gnnml1_dw_floats(Fin, n1, n2, n3, mode))
-                nws = int(L.gml_gnnml1_dw_workspace_bytes(N, Fin, n1, n2, n3, mode))
+            if mode == 4:
+                b1, bc, pat = rest
+                with _Timed('gnnml1_sum_bwd', 4 * (N * (Fin + C + (Fin if need_x else 0) + ng4 + p1) + 2 * (csr.E + N)) if PROFILE is not None else 0, 0):
+                    _lib.call('gml_gnnml1_sum_bwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t),
+                              _ptr(x), int(x.stride(0)), _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2,
+                              _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, act, _ptr(pat), p1 // 4, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p1,
+                              _stream(dev))
+            else:
+                out, = rest
+                with _Timed('gnnml1_bwd', 4 * (N * (Fin + 2 * C + (Fin if need_x else 0) + ng4 + p2) + csr.E + N) if PROFILE is not None else 0, 0):
+                    _lib.call('gml_gnnml1_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t), _ptr(x), int(x.stride(0)), _ptr(out), C,
+                              _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), n1, _ptr(wc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3,
+                              mode, act, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p2, _stream(dev))
+            with _Timed('gnnml1%s_dw' % sfx):
+                nflat = int(getattr(L, 'gml_gnnml1%s_dw_floats' % sfx)(Fin, n1, n2, n3, *m))
+                nws = int(getattr(L, 'gml_gnnml1%s_dw_workspace_bytes' % sfx)(N, Fin, n1, n2, n3, *m))
                 flat = torch.empty(nflat, dtype=torch.float32, device=dev)
                 ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=dev)
-                _lib.call('gml_gnnml1_dw', _ptr(x), int(x.stride(0)), _ptr(g4), ng4, _ptr(q), p2, N, Fin, n1, n2, n3, mode, _ptr(flat),
+                _lib.call('gml_gnnml1%s_dw' % sfx, _ptr(x), int(x.stride(0)), _ptr(g4), ng4, _ptr(q), p2, N, Fin, n1, n2, n3, *m, _ptr(flat),
                           _ptr(ws), ws.numel(), _stream(dev))
                 e1, e2, e3, e4 = n1 * Fin, n1 * Fin + n3 * Fin, n1 * Fin + 2 * n3 * Fin, n1 * Fin + 2 * n3 * Fin + Fin * n2
                 dw1, dw2, dw3, dwc = flat[:e1].view(n1, Fin), flat[e1:e2].view(n3, Fin), flat[e2:e3].view(n3, Fin), flat[e3:e4].view(Fin, n2)
-                sums = flat[e4:]
+                sums = flat[e4:]                                      # column sums of g4: mode 0 [da = dc | df2 | df3], else [da | dc | df2 | df3]
+        oa, oc = 0, p1
+        o2 = p1 if mode == 0 else p1 + p2
+        o3 = o2 + p3
         hb1, hbc, hb2, hb3 = ctx.has_b
         db1 = sums[oa:oa + n1] if hb1 else None
         # mode 0: fc_i1's and conv_i1's biases receive the SAME column sums -- as two tensors with their own memory (autograd adopts a
@@ -792,83 +821,7 @@ class GNNML1BlockFunction(torch.autograd.Function):
         dbc = ((sums[oa:oa + n2].clone() if hb1 else sums[oa:oa + n2]) if mode == 0 else sums[oc:oc + n2]) if hbc else None
         db2 = sums[o2:o2 + n3] if hb2 else None
         db3 = sums[o3:o3 + n3] if hb3 else None
-        return dx, None, None, dw1, db1, dwc.view(1, Fin, n2), dbc, dw2, db2, dw3, db3, None, None
-
-
-def gnnml1_sum_supported(x, Fin, n1, n3):
-    """the sum-and-factors block (GNNML1SumBlockFunction) serves this input: n1 = n2 <= 128, n3 <= 64, Fin <= 192"""
-    return (x.is_cuda and x.dtype == torch.float32 and not _os.environ.get('GML_NO_GNNML1_FUSED')
-            and bool(_lib.lib().gml_gnnml1_sum_supported(int(Fin), int(n1), int(n1), int(n3))))
-
-
-class GNNML1SumBlockFunction(torch.autograd.Function):
-    """One GNNML1 block of enzymes_contfeat.py:284-346 (csrc/gml_gnnml1_sum.hip): [act(fc_i1 x) + act(conv_i1 x) | act(fc_i2 x) *
-    act(fc_i3 x)], [N, n1 + n3] with n1 = n2; act 0 tanh / 1 relu.  One launch forward; backward = phase 1 (g4), q = A dc, dx (only
-    when x needs it) and one weight-gradient pass + fold.  relu: the forward records the two activation patterns of the sum (one byte
-    per 4 columns, saved for backward) and phase 1 reads them; tanh, or record=False: phase 1 recomputes a and c (the same bits).
-    Inputs up to 192 wide, n1 <= 128, n3 <= 64 (gnnml1_sum_supported); rows of any stride.  val: per-edge values in TARGET order or
-    None for ones; they carry no gradient here.  Exact fp32 products."""
-
-    @staticmethod
-    def forward(ctx, x, csr, val, w1, b1, wc, bc, w2, b2, w3, b3, act, record=True):
-        x = _f32rows(x, 'x')
-        N, Fin = int(x.size(0)), int(x.size(1))
-        n1, n2, n3 = int(w1.size(0)), int(wc.size(-1)), int(w2.size(0))
-        w1, w2, w3, wc = _f32c(w1, 'fc1.weight'), _f32c(w2, 'fc2.weight'), _f32c(w3, 'fc3.weight'), _f32c(wc, 'conv.weight')
-        C = n1 + n3
-        dev = x.device
-        if val is not None:
-            val = _f32c(val.reshape(-1), 'edge_attr')
-        with torch.cuda.device(dev):
-            out = torch.empty(N, C, dtype=torch.float32, device=dev)
-            npat = (n1 + 15) // 16 * 4
-            pat = torch.empty(N, npat, dtype=torch.uint8, device=dev) if (int(act) == 1 and record) else None
-            with _Timed('gnnml1_sum_fwd', 4 * (N * (Fin + C) + csr.E + N + Fin * (n1 + n2 + 2 * n3)) if PROFILE is not None else 0, 0):
-                _lib.call('gml_gnnml1_sum_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(x), int(x.stride(0)), N, Fin,
-                          _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, int(act),
-                          _ptr(out), C, _ptr(pat), npat, _stream(dev))
-        ctx.csr, ctx.act, ctx.dims = csr, int(act), (N, Fin, n1, n2, n3, C)
-        ctx.has_b = (b1 is not None, bc is not None, b2 is not None, b3 is not None)
-        ctx.save_for_backward(x, val, w1, b1, wc, bc, w2, b2, w3, b3, pat)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        x, val, w1, b1, wc, bc, w2, b2, w3, b3, pat = ctx.saved_tensors
-        N, Fin, n1, n2, n3, C = ctx.dims
-        csr, act = ctx.csr, ctx.act
-        dev = x.device
-        gout = _f32rows(gout, 'grad_output')
-        L = _lib.lib()
-        ng4 = int(L.gml_gnnml1_sum_g4_cols(n1, n2, n3))
-        p1, p3 = (n1 + 15) // 16 * 16, (n3 + 15) // 16 * 16
-        need_x = ctx.needs_input_grad[0]
-        with torch.cuda.device(dev):
-            val_t = csr.to_source_order(val.view(-1, 1)).view(-1) if val is not None else None
-            g4 = torch.empty(N, ng4, dtype=torch.float32, device=dev)
-            q = torch.empty(N, p1, dtype=torch.float32, device=dev)
-            dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if need_x else None
-            with _Timed('gnnml1_sum_bwd', 4 * (N * (Fin + C + (Fin if need_x else 0) + ng4 + p1) + 2 * (csr.E + N)) if PROFILE is not None else 0, 0):
-                _lib.call('gml_gnnml1_sum_bwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(val), _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t),
-                          _ptr(x), int(x.stride(0)), _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2,
-                          _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, act, _ptr(pat), p1 // 4, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p1,
-                          _stream(dev))
-            with _Timed('gnnml1_sum_dw'):
-                nflat = int(L.gml_gnnml1_sum_dw_floats(Fin, n1, n2, n3))
-                nws = int(L.gml_gnnml1_sum_dw_workspace_bytes(N, Fin, n1, n2, n3))
-                flat = torch.empty(nflat, dtype=torch.float32, device=dev)
-                ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=dev)
-                _lib.call('gml_gnnml1_sum_dw', _ptr(x), int(x.stride(0)), _ptr(g4), ng4, _ptr(q), p1, N, Fin, n1, n2, n3, _ptr(flat),
-                          _ptr(ws), ws.numel(), _stream(dev))
-                e1, e2, e3, e4 = n1 * Fin, n1 * Fin + n3 * Fin, n1 * Fin + 2 * n3 * Fin, n1 * Fin + 2 * n3 * Fin + Fin * n2
-                dw1, dw2, dw3, dwc = flat[:e1].view(n1, Fin), flat[e1:e2].view(n3, Fin), flat[e2:e3].view(n3, Fin), flat[e3:e4].view(Fin, n2)
-                sums = flat[e4:]
-        hb1, hbc, hb2, hb3 = ctx.has_b
-        db1 = sums[:n1] if hb1 else None                          # column sums of g4 = [da | dc | df2 | df3]
-        dbc = sums[p1:p1 + n2] if hbc else None
-        db2 = sums[2 * p1:2 * p1 + n3] if hb2 else None
-        db3 = sums[2 * p1 + p3:2 * p1 + p3 + n3] if hb3 else None
-        return dx, None, None, dw1, db1, dwc.view(1, Fin, n2), dbc, dw2, db2, dw3, db3, None, None
+        return dx, None, None, dw1, db1, dwc.view(1, Fin, n2), dbc, dw2, db2, dw3, db3, None, None, None
 
 
 def xty_wide(a, b):

@@ -365,9 +365,11 @@ class GNNML3(torch.nn.Module):
 
 
 def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
-    """the block as one fused launch (functional.GNNML1BlockFunction) or None when the widths are outside the kernel (input > 144,
-    a part > 64) or the conv is not the plain K = 1 form the scripts use.  Unit edge values (sr25.py:231, mutag.py:253: torch.ones)."""
-    from . import functional as Fn
+    """the block as one fused launch (functional.GNNML1BlockFunction) or None when the widths are outside the kernel (modes 0..3,
+    csrc/gml_gnnml1.hip: input > 144, a part > 64; mode 4, csrc/gml_gnnml1_sum.hip: input > 192, n1 = n2 > 128, n3 > 64) or the conv
+    is not the plain K = 1 form the scripts use.  Unit edge values (sr25.py:231, mutag.py:253: torch.ones).  No row-count gate in
+    mode 4: the fused road's 90th percentile is below the composition's 10th for both blocks at 1.7 k and at 500 k rows
+    (tools/bench_gnnml1_sum.py, profiles/gnnml1_sum.json, DESIGN s4.15)."""
     if conv.weight.size(0) != 1 or conv.selfconn or conv.depthwise:
         return None
     Fin, n1, n2, n3 = int(x.size(1)), int(fc1.weight.size(0)), int(conv.weight.size(2)), int(fc2.weight.size(0))
@@ -377,154 +379,53 @@ def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
                                         fc3.weight, fc3.bias, mode, act)
 
 
-def _gnnml1_sum_block(x, csr, fc1, conv, fc2, fc3, act):
-    """the sum-and-factors block as one fused launch (functional.GNNML1SumBlockFunction, csrc/gml_gnnml1_sum.hip) or None when the
-    widths are outside the kernel (input > 192, n1 = n2 > 128, n3 > 64) or the conv is not the plain K = 1 form.  Unit edge values.
-    No row-count gate: the fused road's 90th percentile is below the composition's 10th for both blocks at 1.7 k and at 500 k rows
-    (tools/bench_gnnml1_sum.py, profiles/gnnml1_sum.json, DESIGN s4.15)."""
-    from . import functional as Fn
-    if conv.weight.size(0) != 1 or conv.selfconn or conv.depthwise:
-        return None
-    Fin, n1, n2, n3 = int(x.size(1)), int(fc1.weight.size(0)), int(conv.weight.size(2)), int(fc2.weight.size(0))
-    if n1 != n2 or not Fn.gnnml1_sum_supported(x, Fin, n1, n3):
-        return None
-    return Fn.GNNML1SumBlockFunction.apply(x, csr, None, fc1.weight, fc1.bias, conv.weight, conv.bias, fc2.weight, fc2.bias,
-                                           fc3.weight, fc3.bias, act)
-
-
-class GNNML1Mutag(torch.nn.Module):
-    """mutag.py:214-266: three blocks of [relu(fc x) | relu(SpectConv_{S=1}(x)) | relu(fc x)*relu(fc x)] + BN."""
-
-    def __init__(self, ninp, nout1=16, nout2=32, nout3=16):
-        super().__init__()
-        nin = nout1 + nout2 + nout3
-        for i, fin in enumerate([ninp, nin, nin], start=1):
-            setattr(self, 'bn%d' % i, BatchNorm1d(nin))
-            setattr(self, 'conv%d1' % i, SpectConv(fin, nout2, 1, selfconn=False))
-            setattr(self, 'fc%d1' % i, torch.nn.Linear(fin, nout1))
-            setattr(self, 'fc%d2' % i, torch.nn.Linear(fin, nout3))
-            setattr(self, 'fc%d3' % i, torch.nn.Linear(fin, nout3))
-        self.fc1 = torch.nn.Linear(nin, 32)
-        self.fc2 = torch.nn.Linear(32, 1)
-
-    def forward(self, data):
-        x = data.x
-        csr = _adjacency(data)
-        # a padded static batch: padding nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only
-        nvalid = _node_valid(data) if getattr(data, 'pad_graph', False) and self.training else None
-        ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)      # mutag.py:253
-        for i in (1, 2, 3):
-            g = lambda n: getattr(self, n % i)
-            y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), 2, 1)      # one launch (csrc/gml_gnnml1.hip)
-            if y is None:
-                y = torch.cat([F.relu(g('fc%d1')(x)), F.relu(g('conv%d1')(x, csr, ones)),
-                               F.relu(g('fc%d2')(x)) * F.relu(g('fc%d3')(x))], 1)
-            x = g('bn%d')(y) if nvalid is None else g('bn%d')(y, valid=nvalid)
-        x = global_mean_pool(x, data)
-        return tall_linear(F.relu(tall_linear(x, self.fc1)), self.fc2)
-
-
-class GNNML1(torch.nn.Module):
-    """GNNML1 as sr25.py:192-246 / graph8c.py:205-246 / mnist75.py:262-326 write it: three blocks of
-         concat=False:  x <- act( fc_i1(x) + conv_i1(x) + fc_i2(x) * fc_i3(x) )            (the scripts' setting)
-         concat=True :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]
-    with conv_i1 = SpectConv(K=1, selfconn=False) over the RAW adjacency with unit edge values, then pooling and
-    head 'lin10' (sr25 / graph8c: fc1: nin -> 10), 'bn_mlp' (mnist75: bn1, relu(fc1: nin -> 32), log_softmax(fc2: 32 -> 10)) or
-    'lin2' (exp_classify.py:240-241, :261-262: fc2(fc1 x), fc1: nin -> 10, fc2: 10 -> nclass, NO activation in between).
-    Same attribute names as the reference, so its state_dict loads.  (mutag.py's variant -- relu on the factors, BatchNorm
-    per block -- is GNNML1Mutag.)"""
-
-    def __init__(self, ninp, nout=64, concat=False, act='tanh', pool='add', head='lin10', nclass=10, dropout=0.0):
-        super().__init__()
-        self.concat, self.pool, self.head = concat, pool, head
-        self.act = {'tanh': torch.tanh, 'relu': F.relu}[act]
-        nin = 3 * nout if concat else nout
-        for i, fin in enumerate([ninp, nin, nin], start=1):
-            setattr(self, 'conv%d1' % i, SpectConv(fin, nout, selfconn=False))
-            for j in (1, 2, 3):
-                setattr(self, 'fc%d%d' % (i, j), torch.nn.Linear(fin, nout))
-        if head == 'lin10':
-            self.fc1 = torch.nn.Linear(nin, nclass)
-        elif head == 'lin2':
-            self.fc1 = torch.nn.Linear(nin, 10)
-            self.fc2 = torch.nn.Linear(10, nclass)
-        else:
-            self.bn1 = torch.nn.BatchNorm1d(nin)
-            self.fc1 = torch.nn.Linear(nin, 32)
-            self.fc2 = torch.nn.Linear(32, nclass)
-        _init_dropout(self, dropout)           # dropout > 0: F.dropout in front of every block in training (mnist75.py:299-317)
-
-    def forward(self, data, _features=False):
-        x = data.x
-        if self.head not in ('lin10', 'lin2') and self.training and getattr(data, 'pad_graph', False):
-            # bn1 normalises the pooled rows: the padding graph's row and absent slots would enter its statistics
-            raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
-                                      'graph and absent slots in the statistics of bn1')
-        csr = _adjacency(data)
-        ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)      # sr25.py:231
-        actid = 0 if self.act is torch.tanh else 1
-        drop = _dropout_pass(self)
-        for i in (1, 2, 3):
-            g = lambda n: getattr(self, n % i)
-            if drop:
-                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
-            y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), 1 if self.concat else 0, actid)
-            if y is not None:
-                x = y
-                continue
-            a, c, h = g('fc%d1')(x), g('conv%d1')(x, csr, ones), g('fc%d2')(x) * g('fc%d3')(x)
-            x = torch.cat([self.act(a), self.act(c), self.act(h)], 1) if self.concat else self.act(a + c + h)
-        x = _pool(self.pool, x, data)
-        if _features:
-            return x
-        if self.head == 'lin10':
-            return tall_linear(x, self.fc1)
-        if self.head == 'lin2':
-            return tall_linear(tall_linear(x, self.fc1), self.fc2)
-        x = F.relu(tall_linear(self.bn1(x), self.fc1))
-        return F.log_softmax(tall_linear(x, self.fc2), dim=1)
-
-    def features(self, data, pad_grad_zero=False):
-        """the pooled graph features the head is applied to: [num_graphs, nin] (pad_grad_zero: accepted for symmetry with
-        GNNML3.features; the pool here masks the padding graph's gradient itself)."""
-        return self.forward(data, _features=True)
-
-
 class GNNML1Blocks(torch.nn.Module):
-    """The GNNML1 of Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343,
-    proteins.py:208-257 and enzymes_contfeat.py:284-346 as one class: `nblocks` concatenating blocks
-         form 'product'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]              (kernel mode 1)
-         form 'factors'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]        (mode 2)
+    """The GNNML1 of every experiment script (mutag.py:214-266, sr25.py:192-246, graph8c.py:205-246, mnist75.py:262-326,
+    exp_classify.py:209-262, Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343,
+    proteins.py:208-257, enzymes_contfeat.py:284-346) as one class: `nblocks` blocks
+         form 'sum'         :  x <- act( fc_i1 x + conv_i1 x + fc_i2 x * fc_i3 x )                          (kernel mode 0, sr25.py:231-240;
+                               n1 == n2 == n3, block output n1 wide)
+         form 'product'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]              (mode 1)
+         form 'factors'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]        (mode 2, mutag.py:253-262)
          form 'tanh_factors':  x <- cat[ act(fc_i1 x), act(conv_i1 x), tanh(fc_i2 x) * tanh(fc_i3 x) ]      (mode 3, ptc.py:311)
          form 'sum_factors' :  x <- cat[ act(fc_i1 x) + act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]       (mode 4, enzymes_contfeat.py:336;
-                               n1 == n2, block output n1 + n3 wide; csrc/gml_gnnml1_sum.hip: inputs up to 192, n1 <= 128, n3 <= 64)
+                               n1 == n2, block output n1 + n3 wide)
     of widths = (n1, n2, n3) (fc_i1 -> n1, conv_i1 = SpectConv(K = 1, selfconn=False) over the raw adjacency with unit edge values
-    -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (csrc/gml_gnnml1.hip, block inputs up to 144 wide; form 'sum_factors':
-    _gnnml1_sum_block, csrc/gml_gnnml1_sum.hip, up to 192 wide) with the composition as the road of any other shape.  bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn>
-    are DECLARED (the scripts declare some they never call: the reference's checkpoints load with strict=True).  dropout > 0:
-    F.dropout in front of every block in training.  pool: a name or a tuple of names (_pool).  head:
-         'mlp32'      : fc2(relu(fc1 x)), fc1: nin -> 32                       (Zinc12k.py:306-307, freqclass.py)
-         'lin2'       : fc2(fc1 x), fc1: nin -> hidden, NO activation          (counting.py:332-333)
+    -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (one fused launch) with the composition as the road of any other shape.
+    bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn> are DECLARED (the scripts declare
+    some they never call: the reference's checkpoints load with strict=True).  dropout > 0: F.dropout in front of every block in
+    training.  pool: a name or a tuple of names (_pool).  head:
+         'mlp32'      : fc2(relu(fc1 x)), fc1: nin -> 32                       (Zinc12k.py:306-307, freqclass.py, mutag.py:264-266)
+         'lin2'       : fc2(fc1 x), fc1: nin -> hidden, NO activation          (counting.py:332-333, exp_classify.py:240-241)
+         'lin10'      : fc1 x, fc1: nin -> nclass, no fc2                      (sr25.py, graph8c.py)
+         'bn_mlp'     : log_softmax(fc2(relu(fc1(bn1 x)))), fc1: nin -> 32, bn1 a plain torch BatchNorm of the pooled rows
+                        (mnist75.py; the name bn1 is the head's: nbn == 0)
          'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)
-    A padded static batch hands _node_valid to the BatchNorms in training, as GNNML1Mutag does."""
+    Same attribute names as the reference, so its state_dict loads.  A padded static batch hands _node_valid to the bnI in training:
+    padding nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only."""
 
-    _MODES = dict(product=1, factors=2, tanh_factors=3, sum_factors=4)
+    _MODES = dict(sum=0, product=1, factors=2, tanh_factors=3, sum_factors=4)
+    _HEADS = ('mlp32', 'lin2', 'lin10', 'bn_mlp', 'log_softmax')
 
     def __init__(self, ninp, widths, nblocks, form='product', act='relu', bn_after=(), nbn=0, pool='add', head='mlp32', hidden=0,
                  nclass=1, dropout=0.0):
         super().__init__()
         n1, n2, n3 = (int(w) for w in widths)
-        if form not in self._MODES or act not in ('tanh', 'relu') or head not in ('mlp32', 'lin2', 'log_softmax'):
-            raise ValueError('form: %s; act: tanh / relu; head: mlp32 / lin2 / log_softmax' % ' / '.join(self._MODES))
+        if form not in self._MODES or act not in ('tanh', 'relu') or head not in self._HEADS:
+            raise ValueError('form: %s; act: tanh / relu; head: %s' % (' / '.join(self._MODES), ' / '.join(self._HEADS)))
+        if form == 'sum' and not n1 == n2 == n3:
+            raise ValueError("form='sum' adds fc_i1 x, conv_i1 x and fc_i2 x * fc_i3 x: three equal widths")
         if form == 'sum_factors' and n1 != n2:
             raise ValueError("form='sum_factors' adds act(fc_i1 x) and act(conv_i1 x): widths[0] == widths[1]")
         if any(not 1 <= int(b) <= min(nblocks, nbn) for b in bn_after):
             raise ValueError('bn_after names blocks 1 .. nblocks whose BatchNorm is declared (nbn)')
         if head == 'lin2' and not hidden > 0:
             raise ValueError("head='lin2' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)")
+        if head == 'bn_mlp' and nbn:
+            raise ValueError("head='bn_mlp' names its BatchNorm bn1: no block BatchNorms (nbn == 0)")
         self.nblocks, self.form, self.act, self.pool, self.head = int(nblocks), form, act, pool, head
         self.bn_after = frozenset(int(b) for b in bn_after)
-        nin = n1 + n3 if form == 'sum_factors' else n1 + n2 + n3
+        nin = {'sum': n1, 'sum_factors': n1 + n3}.get(form, n1 + n2 + n3)
         for i in range(1, nbn + 1):
             setattr(self, 'bn%d' % i, BatchNorm1d(nin))
         for i, fin in enumerate([ninp] + [nin] * (nblocks - 1), start=1):
@@ -533,24 +434,28 @@ class GNNML1Blocks(torch.nn.Module):
             setattr(self, 'fc%d2' % i, torch.nn.Linear(fin, n3))
             setattr(self, 'fc%d3' % i, torch.nn.Linear(fin, n3))
         nin *= len(pool) if isinstance(pool, tuple) else 1
-        if head == 'mlp32':
-            hidden = 32
-        if hidden:
-            self.fc1 = torch.nn.Linear(nin, hidden)
-        self.fc2 = torch.nn.Linear(hidden or nin, nclass)
-        _init_dropout(self, dropout)
+        if head == 'lin10':
+            self.fc1 = torch.nn.Linear(nin, nclass)
+        else:
+            if head == 'bn_mlp':
+                self.bn1 = torch.nn.BatchNorm1d(nin)
+            if head in ('mlp32', 'bn_mlp'):
+                hidden = 32
+            if hidden:
+                self.fc1 = torch.nn.Linear(nin, hidden)
+            self.fc2 = torch.nn.Linear(hidden or nin, nclass)
+        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
 
     def _block(self, i, x, csr, ones):
         g = lambda n: getattr(self, n % i)
         mode, actid = self._MODES[self.form], 0 if self.act == 'tanh' else 1
-        if mode == 4:
-            y = _gnnml1_sum_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), actid)
-        else:
-            y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), mode, actid)
+        y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), mode, actid)
         if y is not None:
             return y
         A = torch.tanh if actid == 0 else F.relu
         a, c, f2, f3 = g('fc%d1')(x), g('conv%d1')(x, csr, ones), g('fc%d2')(x), g('fc%d3')(x)
+        if mode == 0:
+            return A(a + c + f2 * f3)
         if mode == 4:
             return torch.cat([A(a) + A(c), A(f2) * A(f3)], 1)
         h = A(f2 * f3) if mode == 1 else (A(f2) * A(f3) if mode == 2 else torch.tanh(f2) * torch.tanh(f3))
@@ -558,8 +463,13 @@ class GNNML1Blocks(torch.nn.Module):
 
     def forward(self, data, _features=False):
         x = data.x
+        padded = getattr(data, 'pad_graph', False)
+        if self.head == 'bn_mlp' and self.training and padded:
+            # bn1 normalises the pooled rows: the padding graph's row and absent slots would enter its statistics
+            raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
+                                      'graph and absent slots in the statistics of bn1')
         csr = _adjacency(data)
-        nvalid = _node_valid(data) if getattr(data, 'pad_graph', False) and self.training and self.bn_after else None
+        nvalid = _node_valid(data) if padded and self.training and self.bn_after else None
         ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)
         drop = _dropout_pass(self)
         for i in range(1, self.nblocks + 1):
@@ -572,17 +482,25 @@ class GNNML1Blocks(torch.nn.Module):
         x = _pool(self.pool, x, data)
         if _features:
             return x
+        if self.head == 'lin10':
+            return tall_linear(x, self.fc1)
         if self.head == 'lin2':
             return tall_linear(tall_linear(x, self.fc1), self.fc2)
+        if self.head == 'bn_mlp':
+            x = self.bn1(x)
         if hasattr(self, 'fc1'):
             x = F.relu(tall_linear(x, self.fc1))
         x = tall_linear(x, self.fc2)
-        return F.log_softmax(x, dim=1) if self.head == 'log_softmax' else x
+        return x if self.head == 'mlp32' else F.log_softmax(x, dim=1)
 
     def features(self, data, pad_grad_zero=False):
         """the pooled graph features the head is applied to: [num_graphs, nin] (pad_grad_zero: accepted for symmetry with
         GNNML3.features; the pool here masks the padding graph's gradient itself)."""
         return self.forward(data, _features=True)
+
+
+def mutag_gnnml1(ninp=8):                  # mutag.py:214-266 (three blocks 16 | 32 | 16, factor form, relu, a BatchNorm after each, mean-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
+    return GNNML1Blocks(ninp, (16, 32, 16), 3, form='factors', act='relu', bn_after=(1, 2, 3), nbn=3, pool='mean', head='mlp32')
 
 
 def zinc_gnnml1(ninp=25):                  # Zinc12k.py:248-307 (four blocks 16 | 16 | 16, product form, relu, add-pool, relu(fc1: 48 -> 32), fc2: 32 -> 1)
@@ -626,15 +544,15 @@ def enzymes_contfeat_gnnml1(ninp=22, dropout=0.2):
 
 
 def sr25_gnnml1(ninp=2):                   # sr25.py:192-246 (nout = 64, sum form, tanh, add-pool, fc1 -> 10)
-    return GNNML1(ninp, 64, concat=False, act='tanh', pool='add', head='lin10')
+    return GNNML1Blocks(ninp, (64, 64, 64), 3, form='sum', act='tanh', pool='add', head='lin10', nclass=10)
 
 
 def graph8c_gnnml1(ninp=2):                # graph8c.py:195-246 (nout = 64, sum form, tanh, add-pool, fc1 -> 10)
-    return GNNML1(ninp, 64, concat=False, act='tanh', pool='add', head='lin10')
+    return GNNML1Blocks(ninp, (64, 64, 64), 3, form='sum', act='tanh', pool='add', head='lin10', nclass=10)
 
 
 def mnist75_gnnml1(ninp=3, dropout=0.0):   # mnist75.py:262-326 (relu, mean-pool, bn1, 32 -> 10; the script's dropout: p = 0.1)
-    return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='bn_mlp', dropout=dropout)
+    return GNNML1Blocks(ninp, (64, 64, 64), 3, form='sum', act='relu', pool='mean', head='bn_mlp', nclass=10, dropout=dropout)
 
 
 def filtering_gnnml3(ninp=1, ne=11):      # filtering.py:252-280 (node-level: three layers 32 + 16, fc2: 48 -> 1, no pooling, no fc1)
@@ -666,7 +584,7 @@ def exp_classify_gnnml3(ninp=2, ne=6):     # exp_classify.py:264-295 (three laye
 
 
 def exp_classify_gnnml1(ninp=2):           # exp_classify.py:209-262 (nout = 64, sum form, relu, mean-pool, fc1: 64 -> 10, fc2: 10 -> 1, no activation between)
-    return GNNML1(ninp, 64, concat=False, act='relu', pool='mean', head='lin2', nclass=1)
+    return GNNML1Blocks(ninp, (64, 64, 64), 3, form='sum', act='relu', pool='mean', head='lin2', hidden=10, nclass=1)
 
 
 def mnist_gnnml3(ninp=2, ne=6, dense_n=0):  # mnist75_gnnml3_tf.py:62, libs/models_tf.py:223-268 (DSGCNN)
@@ -769,12 +687,10 @@ def exp_classify_loss(pre, y, valid=None):   # exp_classify.py:328-329
 
 
 def _exp_head(model):
-    """(fc1, fc2, act) of a model whose readout is fc2(act(fc1 x)): GNNML3 head 'mlp' (relu), GNNML1 head 'lin2' (identity),
-    GNNML1Blocks heads 'mlp32' (relu) / 'lin2' (identity)"""
+    """(fc1, fc2, act) of a model whose readout is fc2(act(fc1 x)): GNNML3 head 'mlp' (relu), GNNML1Blocks heads 'mlp32' (relu) /
+    'lin2' (identity)"""
     if isinstance(model, GNNML3) and model.head == 'mlp':
         return model.fc1, model.fc2, 1
-    if isinstance(model, GNNML1) and model.head == 'lin2':
-        return model.fc1, model.fc2, 0
     if isinstance(model, GNNML1Blocks) and model.head in ('mlp32', 'lin2'):        # freqclass.py:298-300: relu(fc1: 96 -> 32), fc2
         return model.fc1, model.fc2, 1 if model.head == 'mlp32' else 0
     return None

@@ -36,7 +36,7 @@ elif cfg in ('mutag_gnnml1', 'sr25_gnnml1'):   # round 5: the fused GNNML1 block
             x7[np.arange(x.shape[0]), rng.integers(7, size=x.shape[0])] = 1
             raw.append((x7, ei, np.float32(rng.integers(2))))
         pool = SpectralDesign(recfield=1, dv=4, nfreq=3, adddegree=True).design_many(raw)
-        ctor, loss = (lambda: models.GNNML1Mutag(8)), models.mutag_loss
+        ctor, loss = (lambda: models.mutag_gnnml1(8)), models.mutag_loss
     else:
         from gnn_matlang_amd import readers
         root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -15,11 +15,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _gnnml1_ref as R
+from _gnnml1_ref import TOL, check as _check
 from conftest import GOLDEN, ROOT, rel_err
 
 pytestmark = pytest.mark.gpu
-
-TOL = 2e-5
 
 
 @pytest.fixture(scope='module')
@@ -30,96 +30,25 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _check(got, ref64, ref32, what, case, tol=TOL):
-    """max|got - ref64| <= tol max|ref64|, with the figures printed first"""
-    g = got.detach().cpu().double().numpy()
-    r = ref64.detach().double().numpy()
-    assert g.shape == r.shape, (what, g.shape, r.shape)
-    assert np.isfinite(g).all(), what
-    e, e32 = rel_err(g, r), rel_err(ref32.detach().double().numpy(), r)
-    print('%s %s: err %.3e (float32 restatement %.3e, tol %.1e)' % (case, what, e, e32, tol))
-    assert e <= tol, '%s %s: rel err %.3e > %.1e (float32 restatement: %.3e)' % (case, what, e, tol, e32)
-
-
-# ------------------------------------------------------------------------------------------------ the block, restated
+# ------------------------------------------------------------------------------------------------ the block (restated in _gnnml1_ref)
 def _parts_ref(x, ei, v, W):
-    """libs/spect_conv.py:98-99 aggregates at the TARGET; the four linears"""
-    h = torch.zeros_like(x).index_add_(0, ei[1], v.unsqueeze(1) * x[ei[0]])
-    a, c = x @ W['w1'].t() + W['b1'], h @ W['wc'][0] + W['bc']
-    f2, f3 = x @ W['w2'].t() + W['b2'], x @ W['w3'].t() + W['b3']
-    return a, c, f2, f3
+    return R.parts_ref(x, ei, v, W)
 
 
 def _block_ref(x, ei, v, W, act):
-    """enzymes_contfeat.py:336"""
-    A = torch.tanh if act == 0 else torch.relu
-    a, c, f2, f3 = _parts_ref(x, ei, v, W)
-    return torch.cat([A(a) + A(c), A(f2) * A(f3)], 1)
-
-
-def _graph(N, seed):
-    """a directed random graph (its transposed view is another matrix) with node 0 without in-edge, node 1 without out-edge and
-    node 2 of in-degree >= 40 (as many as N allows below 42 nodes); N = 1: one self loop"""
-    if N == 1:
-        return torch.zeros(2, 1, dtype=torch.int64)
-    rng = np.random.default_rng(seed)
-    src = rng.integers(0, N, size=N * 5)
-    dst = np.clip(src + rng.integers(-20, 21, size=src.shape), 0, N - 1)
-    hub = rng.permutation(np.arange(2, N))[:min(48, N - 2)]
-    src, dst = np.concatenate((src, hub)), np.concatenate((dst, np.full(hub.shape, 2)))
-    keep = (dst != 0) & (src != 1)
-    ei = np.unique(np.vstack((src[keep], dst[keep])), axis=1).astype(np.int64)
-    assert not (ei[1] == 0).any() and not (ei[0] == 1).any() and (ei[1] == 2).sum() >= min(40, N - 3)
-    assert not np.array_equal(ei, np.unique(ei[::-1], axis=1))
-    return torch.from_numpy(ei)
+    return R.block_ref(x, ei, v, W, 4, act)
 
 
 def _block_case(N, Fin, n1, n3, unit):
-    torch.manual_seed(N + Fin)
-    ei = _graph(N, N + Fin)
-    E = ei.size(1)
-    val = torch.ones(E) if unit else torch.randn(E)
-    x = torch.randn(N, Fin)
-    W = dict(w1=torch.randn(n1, Fin) * 0.3, b1=torch.randn(n1) * 0.1, wc=torch.randn(1, Fin, n1) * 0.2, bc=torch.randn(n1) * 0.1,
-             w2=torch.randn(n3, Fin) * 0.3, b2=torch.randn(n3) * 0.1, w3=torch.randn(n3, Fin) * 0.3, b3=torch.randn(n3) * 0.1)
-    gout = torch.randn(N, n1 + n3)
-    return ei, val, x, W, gout
+    return R.block_case(N, Fin, n1, n1, n3, 4, unit)
 
 
 def _block_cpu(x, ei, val, W, gout, act, dtype):
-    xr = x.detach().to(dtype).clone().requires_grad_(True)      # (fresh leaves: .to() of the same dtype returns its argument)
-    Wr = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in W.items()}
-    y = _block_ref(xr, ei, val.to(dtype), Wr, act)
-    (y * gout.to(dtype)).sum().backward()
-    return y.detach(), xr.grad, {k: v.grad for k, v in Wr.items()}
+    return R.block_cpu(x, ei, val, W, gout, 4, act, dtype)
 
 
-def _block_gpu(dev, x, ei, val, W, gout, act, unit, need_dx=True, strided=False, record=True):
-    from gnn_matlang_amd import functional as Fn
-    from gnn_matlang_amd.graph import GraphCSR
-    N, Fin = x.shape
-    n1, n3 = W['w1'].size(0), W['w2'].size(0)
-    csr = GraphCSR.from_edge_index(ei.to(dev), N)
-    if strided:                                                  # x: rows of a wider buffer (ldx > Fin); gout: a column slice
-        buf = torch.zeros(N, Fin + 5, device=dev)
-        buf[:, :Fin] = x.to(dev)
-        xl = buf.requires_grad_(need_dx)
-        xd = xl[:, :Fin]
-        gbuf = torch.randn(N, n1 + n3 + 7, device=dev)
-        gbuf[:, 3:3 + n1 + n3] = gout.to(dev)
-        gd = gbuf[:, 3:3 + n1 + n3]
-        assert xd.stride(0) > Fin and gd.stride(0) > n1 + n3 and not xd.is_contiguous()
-    else:
-        xl = xd = x.detach().to(dev).requires_grad_(need_dx)
-        gd = gout.to(dev)
-    Wd = {k: v.detach().to(dev).requires_grad_(True) for k, v in W.items()}
-    vs = None if unit else csr.sort_values(val.to(dev).view(-1, 1)).view(-1)
-    assert Fn.gnnml1_sum_supported(xd, Fin, n1, n3)
-    y = Fn.GNNML1SumBlockFunction.apply(xd, csr, vs, Wd['w1'], Wd['b1'], Wd['wc'], Wd['bc'], Wd['w2'], Wd['b2'], Wd['w3'], Wd['b3'], act, record)
-    assert y.shape == (N, n1 + n3)
-    y.backward(gd)
-    dx = xl.grad[:, :Fin] if (strided and need_dx) else xl.grad
-    return y.detach(), dx, {k: v.grad for k, v in Wd.items()}
+def _block_gpu(dev, x, ei, val, W, gout, act, unit, **kw):
+    return R.block_gpu(dev, x, ei, val, W, gout, 4, act, unit, **kw)
 
 
 # (N, Fin, n1 = n2, n3, act)
@@ -279,7 +208,7 @@ def test_model_vs_fp64(dev):
     m = models.enzymes_contfeat_gnnml1(dropout=0.0).to(dev).train()
     data = host.to(dev)
     for fin in (22, 192):
-        assert Fn.gnnml1_sum_supported(data.x, fin, 128, 64), fin
+        assert Fn.gnnml1_block_supported(data.x, fin, 128, 128, 64, 4), fin
     pre = m(data)
     loss = models.tu_step_loss(m, data)
     loss.backward()
@@ -307,7 +236,7 @@ def test_outside_the_range_runs_on_the_composition(dev):
     from gnn_matlang_amd import functional as Fn, models
     host = _host_batch()
     data = host.to(dev)
-    assert not Fn.gnnml1_sum_supported(data.x, 22, 129, 64) and not Fn.gnnml1_sum_supported(data.x, 193, 128, 64)
+    assert not Fn.gnnml1_block_supported(data.x, 22, 129, 129, 64, 4) and not Fn.gnnml1_block_supported(data.x, 193, 128, 128, 64, 4)
     torch.manual_seed(4)
     m = models.GNNML1Blocks(22, (129, 129, 64), 2, form='sum_factors', bn_after=(1, 2), nbn=2, pool=('mean', 'max'), head='log_softmax',
                             nclass=6).to(dev).train()
@@ -335,7 +264,7 @@ def test_composition_via_environment_equals_the_fused_road(dev, tmp_path):
             "from gnn_matlang_amd import functional as Fn, models\n"
             "d = torch.device('cuda:0')\n"
             "data = T._host_batch().to(d)\n"
-            "assert not Fn.gnnml1_sum_supported(data.x, 22, 128, 64)\n"
+            "assert not Fn.gnnml1_block_supported(data.x, 22, 128, 128, 64, 4)\n"
             "torch.manual_seed(3)\n"
             "m = models.enzymes_contfeat_gnnml1(dropout=0.0).to(d).train()\n"
             "with torch.no_grad():\n"

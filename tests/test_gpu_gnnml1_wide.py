@@ -12,11 +12,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _gnnml1_ref as R
+from _gnnml1_ref import TOL, block_case as _block_case, block_cpu as _block_cpu, block_gpu as _block_gpu
 from conftest import GOLDEN, rel_err
 
 pytestmark = pytest.mark.gpu
 
-TOL = 2e-5
 COMPUTED_TOL = set()                                       # ids of the cases whose bound is computed from the float32 restatement
 
 
@@ -29,82 +30,10 @@ def dev():
 
 
 def _check(got, ref64, ref32, what, case):
-    """max|got - ref64| <= tol max|ref64|, with the figures printed first"""
-    g = got.detach().cpu().double().numpy()
-    r = ref64.detach().double().numpy()
-    assert g.shape == r.shape, (what, g.shape, r.shape)
-    assert np.isfinite(g).all(), what
-    e, e32 = rel_err(g, r), rel_err(ref32.detach().double().numpy(), r)
-    tol = max(TOL, 4 * e32) if case in COMPUTED_TOL else TOL
-    print('%s %s: err %.3e (float32 restatement %.3e, tol %.1e)' % (case, what, e, e32, tol))
-    assert e <= tol, '%s %s: rel err %.3e > %.1e (float32 restatement: %.3e)' % (case, what, e, tol, e32)
+    R.check(got, ref64, ref32, what, case, TOL, computed=case in COMPUTED_TOL)
 
 
-# ------------------------------------------------------------------------------------------------ the block, restated
-def _block_ref(x, ei, v, W, mode, act):
-    """libs/spect_conv.py:98-99 aggregates at the TARGET; the four linears; the forms (mode 3: ptc.py:311)"""
-    A = torch.tanh if act == 0 else torch.relu
-    h = torch.zeros_like(x).index_add_(0, ei[1], v.unsqueeze(1) * x[ei[0]])
-    a, c = x @ W['w1'].t() + W['b1'], h @ W['wc'][0] + W['bc']
-    f2, f3 = x @ W['w2'].t() + W['b2'], x @ W['w3'].t() + W['b3']
-    if mode == 0:
-        return A(a + c + f2 * f3)
-    third = A(f2 * f3) if mode == 1 else (A(f2) * A(f3) if mode == 2 else torch.tanh(f2) * torch.tanh(f3))
-    return torch.cat([A(a), A(c), third], 1)
-
-
-def _graph(N, seed):
-    """a directed random graph (its transposed view is another matrix) with node 0 without in-edge, node 1 without out-edge and
-    node 2 of in-degree >= 40 (as many as N allows below 42 nodes); N = 1: one self loop"""
-    if N == 1:
-        return torch.zeros(2, 1, dtype=torch.int64)
-    rng = np.random.default_rng(seed)
-    src = rng.integers(0, N, size=N * 5)
-    dst = np.clip(src + rng.integers(-20, 21, size=src.shape), 0, N - 1)
-    hub = rng.permutation(np.arange(2, N))[:min(48, N - 2)]
-    src, dst = np.concatenate((src, hub)), np.concatenate((dst, np.full(hub.shape, 2)))
-    keep = (dst != 0) & (src != 1)
-    ei = np.unique(np.vstack((src[keep], dst[keep])), axis=1).astype(np.int64)
-    assert not (ei[1] == 0).any() and not (ei[0] == 1).any() and (ei[1] == 2).sum() >= min(40, N - 3)
-    assert not np.array_equal(ei, np.unique(ei[::-1], axis=1))
-    return torch.from_numpy(ei)
-
-
-def _block_case(N, Fin, n1, n2, n3, mode, unit):
-    torch.manual_seed(N + Fin)
-    ei = _graph(N, N + Fin)
-    E = ei.size(1)
-    val = torch.ones(E) if unit else torch.randn(E)
-    x = torch.randn(N, Fin)
-    W = dict(w1=torch.randn(n1, Fin) * 0.3, b1=torch.randn(n1) * 0.1, wc=torch.randn(1, Fin, n2) * 0.2, bc=torch.randn(n2) * 0.1,
-             w2=torch.randn(n3, Fin) * 0.3, b2=torch.randn(n3) * 0.1, w3=torch.randn(n3, Fin) * 0.3, b3=torch.randn(n3) * 0.1)
-    gout = torch.randn(N, n1 if mode == 0 else n1 + n2 + n3)
-    return ei, val, x, W, gout
-
-
-def _block_cpu(x, ei, val, W, gout, mode, act, dtype):
-    xr = x.detach().to(dtype).clone().requires_grad_(True)      # (fresh leaves: .to() of the same dtype returns its argument)
-    Wr = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in W.items()}
-    y = _block_ref(xr, ei, val.to(dtype), Wr, mode, act)
-    (y * gout.to(dtype)).sum().backward()
-    return y.detach(), xr.grad, {k: v.grad for k, v in Wr.items()}
-
-
-def _block_gpu(dev, x, ei, val, W, gout, mode, act, unit, need_dx=True):
-    from gnn_matlang_amd import functional as Fn
-    from gnn_matlang_amd.graph import GraphCSR
-    N, Fin = x.shape
-    n1, n2, n3 = W['w1'].size(0), W['wc'].size(2), W['w2'].size(0)
-    csr = GraphCSR.from_edge_index(ei.to(dev), N)
-    xd = x.detach().to(dev).requires_grad_(need_dx)
-    Wd = {k: v.detach().to(dev).requires_grad_(True) for k, v in W.items()}
-    vs = None if unit else csr.sort_values(val.to(dev).view(-1, 1)).view(-1)
-    assert Fn.gnnml1_block_supported(xd, Fin, n1, n2, n3, mode)
-    y = Fn.GNNML1BlockFunction.apply(xd, csr, vs, Wd['w1'], Wd['b1'], Wd['wc'], Wd['bc'], Wd['w2'], Wd['b2'], Wd['w3'], Wd['b3'], mode, act)
-    (y * gout.to(dev)).sum().backward()
-    return y.detach(), xd.grad, {k: v.grad for k, v in Wd.items()}
-
-
+# ------------------------------------------------------------------------------------------------ the block (restated in _gnnml1_ref)
 SHAPES = [(130, 65, 16, 16, 16, 1, 1),       # first width past the old limit, unaligned rows
           (300, 96, 32, 32, 32, 1, 1),       # counting / freqclass
           (300, 98, 32, 64, 2, 3, 1),        # ptc: 98 % 4 != 0, n3 = 2
@@ -327,6 +256,51 @@ def test_outside_the_range_runs_on_the_composition(dev, widths):
     e = rel_err(pre.detach().cpu().double().numpy(), p64.numpy())
     print('outside %s: err %.3e' % (widths, e))
     assert e <= 1e-4
+
+
+# ------------------------------------------------------------------------------------------------ every form through the one class
+_FORMS = ('sum', 'product', 'factors', 'tanh_factors', 'sum_factors')
+
+
+def _small_batch():
+    """3 graphs of 13 nodes, 5 random features (rows not float4-addressable), labels 0 / 1 / 2"""
+    from gnn_matlang_amd import collate, synthetic
+    if 'small' not in _HOST:
+        _HOST['small'] = collate([dict(x=np.random.default_rng(i).standard_normal((x.shape[0], 5)).astype(np.float32), edge_index=ei, y=i % 3)
+                                  for i, (x, ei, y) in enumerate(synthetic.make_graphs('counting', 3, seed=5, nmin=13, nmax=13))])
+    return _HOST['small']
+
+
+@pytest.mark.parametrize('act', ['tanh', 'relu'])
+@pytest.mark.parametrize('form', _FORMS)
+def test_every_form_fused_against_composed(dev, monkeypatch, form, act):
+    """GNNML1Blocks of two blocks in each form: loss and every parameter gradient on the fused road (both blocks through
+    GNNML1BlockFunction; the second reads 16, 48 or 24 features) against the composition road of the same process
+    (GML_NO_GNNML1_FUSED=1, read at call time), at the bound for exact fp32 products"""
+    from gnn_matlang_amd import functional as Fn, models
+    data = _small_batch().to(dev)
+    assert tuple(data.x.shape) == (39, 5)
+    widths = (16, 16, 8) if form == 'sum_factors' else (16, 16, 16)
+    torch.manual_seed(7)
+    m = models.GNNML1Blocks(5, widths, 2, form=form, act=act, pool='add', head='log_softmax', nclass=3).to(dev).train()
+    calls, apply = [], Fn.GNNML1BlockFunction.apply
+    monkeypatch.setattr(Fn.GNNML1BlockFunction, 'apply', lambda *a: (calls.append(a[11]), apply(*a))[1])
+
+    def run():
+        m.zero_grad(set_to_none=True)
+        loss = models.tu_step_loss(m, data)
+        loss.backward()
+        return dict([('loss', loss.detach().reshape(1).clone())] + [(n, q.grad.clone()) for n, q in m.named_parameters()])
+    fused = run()
+    assert calls == [models.GNNML1Blocks._MODES[form]] * 2
+    monkeypatch.setenv('GML_NO_GNNML1_FUSED', '1')
+    composed = run()
+    assert len(calls) == 2                                      # the composition road: the fused function not at all
+    assert len(fused) == 1 + 8 * 2 + 2
+    for k in composed:
+        e = rel_err(fused[k].cpu().double().numpy(), composed[k].cpu().double().numpy())
+        print('%s %s %s: fused against composed %.3e' % (form, act, k, e))
+        assert e <= TOL, (form, act, k, e)
 
 
 # ------------------------------------------------------------------------------------------------ dropout

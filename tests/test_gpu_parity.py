@@ -676,7 +676,7 @@ def _batch_from(g, dev):
     ('model_zinc_gnnml3.npz', 'zinc_gnnml3', 'zinc_loss'),
     ('model_counting_gnnml3.npz', 'counting_gnnml3', 'counting_loss'),
     ('model_mutag_gnnml3.npz', 'mutag_gnnml3', 'mutag_loss'),
-    ('model_mutag_gnnml1.npz', 'GNNML1Mutag', 'mutag_loss'),
+    pytest.param('model_mutag_gnnml1.npz', 'mutag_gnnml1', 'mutag_loss', id='model_mutag_gnnml1.npz-GNNML1Mutag-mutag_loss'),   # (the id it has always had)
 ])
 def test_model_step_golden(dev, golden, fname, ctor, loss, arith):
     """logits, loss, every parameter gradient and the 5-step Adam loss trajectory against the reference's own outputs.
@@ -686,7 +686,7 @@ def test_model_step_golden(dev, golden, fname, ctor, loss, arith):
     from gnn_matlang_amd import models
     g = golden(fname)
     data = _batch_from(g, dev)
-    m = getattr(models, ctor)(8) if ctor == 'GNNML1Mutag' else getattr(models, ctor)()
+    m = getattr(models, ctor)()
     m.load_state_dict({k: T(v) for k, v in g.sub('param/').items()})      # reference state_dict keys
     m = m.to(dev).train()
     loss_fn = getattr(models, loss)
@@ -2109,7 +2109,7 @@ def test_gnnml1_block_bias_gradients_do_not_share_memory(dev):
     raw = synthetic.make_graphs('counting', 12, seed=9)
     b = collate(SpectralDesign(recfield=1, dv=1, nfreq=10, adddegree=True, laplacien=False, addadj=True).design_many(raw)).to(dev)
     torch.manual_seed(1)
-    m = models.GNNML1(int(b.x.size(1)), nout=16, concat=False).to(dev)
+    m = models.GNNML1Blocks(int(b.x.size(1)), (16, 16, 16), 3, form='sum', act='tanh', head='lin10', nclass=10).to(dev)
     m(b).square().sum().backward()
     spans = {}
     for n, p in m.named_parameters():

@@ -170,7 +170,7 @@ def test_padded_batch_step_equals_the_plain_batch(dev, mutag, which):
     dd = mutag if which != 'sr25_gnnml1' else _dataset('sr25', dev)
     G = len(dd)
     torch.manual_seed(3)
-    m = {'mutag_gnnml3': lambda: models.mutag_gnnml3(), 'GNNML1Mutag': lambda: models.GNNML1Mutag(8),
+    m = {'mutag_gnnml3': lambda: models.mutag_gnnml3(), 'GNNML1Mutag': lambda: models.mutag_gnnml1(8),
          'sr25_gnnml1': lambda: models.sr25_gnnml1(2)}[which]().to(dev).train()
     mp, ms = m, copy.deepcopy(m)
     sl = [11, 0, G, 7, 3, G, 14, 2, 9, 1, 5, G, 12, 4, 8, 6]
@@ -208,7 +208,7 @@ def _perms(G, epochs, seed):
 def _model(which, dev):
     from gnn_matlang_amd import models
     torch.manual_seed(21)
-    return (models.mutag_gnnml3() if which == 'mutag_gnnml3' else models.GNNML1Mutag(8)).to(dev).train()
+    return (models.mutag_gnnml3() if which == 'mutag_gnnml3' else models.mutag_gnnml1(8)).to(dev).train()
 
 
 def _train(which, dd, dev, captured, epochs=2):

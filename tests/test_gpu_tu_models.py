@@ -61,7 +61,7 @@ def _by_hand(m, data, masks, p):
     from gnn_matlang_amd import models
     from gnn_matlang_amd.functional import tall_linear
     x = data.x
-    if isinstance(m, models.GNNML1):
+    if getattr(m, 'form', None) == 'sum':
         csr = data.csr('edge_index')
         for i in (1, 2, 3):
             g = lambda n: getattr(m, n % i)

@@ -99,7 +99,7 @@ def test_module_surface_matches_reference(golden):
         assert l.learnedge == bool(learnedge) and l.nout2 == nout2
     # model assemblies load the reference state_dicts
     for f, ctor in (('model_zinc_gnnml3.npz', models.zinc_gnnml3), ('model_counting_gnnml3.npz', models.counting_gnnml3),
-                    ('model_mutag_gnnml3.npz', models.mutag_gnnml3), ('model_mutag_gnnml1.npz', lambda: models.GNNML1Mutag(8))):
+                    ('model_mutag_gnnml3.npz', models.mutag_gnnml3), ('model_mutag_gnnml1.npz', lambda: models.mutag_gnnml1(8))):
         ctor().load_state_dict({k: T(v) for k, v in golden(f).sub('param/').items()})
     assert sum(p.numel() for p in models.zinc_gnnml3().parameters()) == 33309
     assert sum(p.numel() for p in models.counting_gnnml3().parameters()) == 37649

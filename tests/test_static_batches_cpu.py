@@ -178,7 +178,7 @@ def test_models_refuse_padded_batches_they_cannot_take(mutag):
     ds, dd = mutag
     bd = dd.bounds(BS)
     b = dd.batch_padded(torch.arange(BS), bd)                      # no adjacency
-    for m in (models.GNNML1Mutag(8), models.sr25_gnnml1(8)):
+    for m in (models.mutag_gnnml1(8), models.sr25_gnnml1(8)):
         with pytest.raises(ValueError, match='adjacency=True'):
             m(b)
     ba = dd.batch_padded(torch.arange(BS), bd, adjacency=True)

@@ -39,7 +39,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     for name, kind, make in (('sr25_gnnml1 (sum form, tanh, 64 wide)', 'sr25', lambda: models.sr25_gnnml1(2)),
-                             ('mutag_gnnml1 (factor form, relu, 16 + 32 + 16, BatchNorm)', 'mutag', lambda: models.GNNML1Mutag(8))):
+                             ('mutag_gnnml1 (factor form, relu, 16 + 32 + 16, BatchNorm)', 'mutag', lambda: models.mutag_gnnml1(8))):
         b = batch(kind, a.graphs, dev)
         torch.manual_seed(0)
         m = make().to(dev)

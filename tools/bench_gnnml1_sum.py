@@ -46,7 +46,7 @@ def measure(name, big, rounds, iters, dev):
     ones = torch.ones(csr.E, 1, device=dev)
     gout = torch.randn(N, WIDTHS[0] + WIDTHS[2], device=dev)
     os.environ.pop('GML_NO_GNNML1_FUSED', None)
-    if not Fn.gnnml1_sum_supported(x, fin, WIDTHS[0], WIDTHS[2]):
+    if not Fn.gnnml1_block_supported(x, fin, WIDTHS[0], WIDTHS[1], WIDTHS[2], 4):
         sys.exit('%s: the library does not serve this block shape' % name)
 
     def run():

@@ -1,5 +1,5 @@
 """mutag at the reference's batch size (bsize = 16, mutag.py:320-351) on the real graphs (tests/golden/raw/mutag.mat), for mutag GNNML3
-and GNNML1Mutag, three ways each:
+and mutag GNNML1 (models.mutag_gnnml1), three ways each:
     eager   over DeviceDataset.epoch()          plain batches, per-batch CSR build with host reads
     static  over DeviceDataset.epoch_static()   padded batches from gml_batch_assemble (+ _edges), masked BatchNorm, no host read
     graph   one captured step replayed per batch (assembly + forward + masked loss + backward + running statistics + OneLaunchAdam)
@@ -38,10 +38,10 @@ def main():
     dd.prepare()
     G = len(dd)
     bd = dd.bounds(BS)
-    ctors = {'mutag_gnnml3': lambda: models.mutag_gnnml3(), 'GNNML1Mutag': lambda: models.GNNML1Mutag(8)}
+    ctors = {'mutag_gnnml3': lambda: models.mutag_gnnml3(), 'mutag_gnnml1': lambda: models.mutag_gnnml1()}
     rows = []
     for name, ctor in ctors.items():
-        adj = name == 'GNNML1Mutag'
+        adj = name == 'mutag_gnnml1'
         for way in ('eager', 'static', 'graph'):
             torch.manual_seed(0)
             m = ctor().to(dev).train()

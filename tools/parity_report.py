@@ -32,10 +32,10 @@ for mode in ('bf16x3', 'f32'):
     for fname, ctor, loss in (('model_zinc_gnnml3.npz', 'zinc_gnnml3', 'zinc_loss'),
                               ('model_counting_gnnml3.npz', 'counting_gnnml3', 'counting_loss'),
                               ('model_mutag_gnnml3.npz', 'mutag_gnnml3', 'mutag_loss'),
-                              ('model_mutag_gnnml1.npz', 'GNNML1Mutag', 'mutag_loss')):
+                              ('model_mutag_gnnml1.npz', 'mutag_gnnml1', 'mutag_loss')):
         g = Golden(fname)
         data = batch_from(g)
-        m = getattr(models, ctor)(8) if ctor == 'GNNML1Mutag' else getattr(models, ctor)()
+        m = getattr(models, ctor)()
         m.load_state_dict({k: T(v) for k, v in g.sub('param/').items()})
         m = m.to(dev).train()
         lf = getattr(models, loss)
