@@ -17,6 +17,7 @@ One LARGE graph (96 < n <= 1024, F <= 64: the 2-D grid of filtering.py, 900 node
 csrc/gml_dense_big.hip: the work is cut across (support, row block, K slice) instead of across graphs, the projection stays the
 tall GEMM (``_SupportProduct`` dispatches by n; the chained one-launch kernels are n <= 96 only).
 """
+import ctypes
 import os
 
 import torch
@@ -262,5 +263,148 @@ def spectconv_dense(x, sup, weight, bias, n, relu=False):
         if CHAIN and Fout <= 128 and n <= SMALL_N:
             return _DenseConv.apply(x, weight, bias, sup, relu)
         h = _SupportProduct.apply(x, sup)
+    out = _TallGemm.apply(h, weight.reshape(S * Fin, Fout), bias)
+    return torch.relu(out) if relu else out
+
+
+# ---------------------------------------------------------------------------- graphs of different sizes (csrc/gml_dense_rag.hip)
+# The TF GNNML3 of enzymes_contfeats_gnnml3_tf.py (libs/models_tf.py:275-343, libs/layers_tf.py:276-298): dense per-graph blocks
+# matmul(dropout(support[:, i]), x) over ENZYMES graphs of 2 .. 126 nodes whose recfield-5 masks are 97 % full.  The supports of the
+# whole data set are packed ONCE into a bank of bf16 (hi, lo) images [G, S, 2, 128, 128]; a batch names its graphs by bank slot
+# (gid), its node rows stay compact, and the kernel walks only the row tiles and K steps each graph has.
+RAG_NP = 128                 # gml_dense_rag.hip: at most 128 nodes per graph
+RAG_F = 256                  # and at most 256 features per product
+
+
+class RaggedSupports(object):
+    """Support bank of a data set of G graphs (collated COO supports: edge_index2 [2, E] with global node ids, edge_attr2 [E, S],
+    batch [N], ptr [G + 1]).  fwd / bwd: int16 [G, S, 2, 128, 128] bf16 (hi, lo) images of the blocks (row = target node) / of their
+    transposes (gml_dense_rag_pack); sizes: the node counts as host integers; blocks: fp32 [G, S, 128, 128], built on first use --
+    the library road only (functional.exact_mode())."""
+
+    def __init__(self, edge_index2, edge_attr2, batch, ptr):
+        sizes = (ptr[1:] - ptr[:-1]).cpu().tolist()
+        for g, n in enumerate(sizes):
+            if n > RAG_NP:
+                raise ValueError('graph %d has %d nodes: the ragged dense blocks take at most %d per graph' % (g, n, RAG_NP))
+        self.G, self.S, self.sizes = len(sizes), int(edge_attr2.size(1)), [int(n) for n in sizes]
+        dev = edge_attr2.device
+        self._ei = edge_index2.to(torch.int64).contiguous()
+        self._ea = edge_attr2.to(torch.float32).contiguous()
+        self._batch = batch.to(torch.int64).contiguous()
+        self.ptr = Fn._ptr32(ptr)
+        self._blocks = None
+        self.fwd = torch.empty(self.G, self.S, 2, RAG_NP, RAG_NP, dtype=torch.int16, device=dev)
+        self.bwd = torch.empty_like(self.fwd)
+        _lib.call('gml_dense_rag_pack', _ptr(self._ei), _ptr(self._ea), _ptr(self._batch), _ptr(self.ptr), _ptr(self.fwd), _ptr(self.bwd),
+                  int(self._ei.size(1)), int(self._batch.numel()), self.G, self.S, _stream(dev))
+
+    @property
+    def blocks(self):
+        if self._blocks is None:
+            src, dst = self._ei[0], self._ei[1]
+            g = self._batch[src]
+            off = self.ptr.to(torch.int64)[g]
+            blk = torch.zeros(self.G, self.S, RAG_NP, RAG_NP, dtype=torch.float32, device=self._ea.device)
+            blk[g, :, dst - off, src - off] = self._ea
+            self._blocks = blk
+        return self._blocks
+
+
+def attach_bank(batch, bank, gid=None):
+    """batch with the fields a ragged dense model reads: bank (RaggedSupports) and gid (int32 [B] on the bank's device: the bank slot
+    of every graph of the batch; None = the batch is the bank's first B graphs in order)."""
+    batch.bank, batch.gid = bank, (None if gid is None else gid.to(torch.int32).contiguous())
+    return batch
+
+
+def ragged_keep_bits(ptr, B, S, p, state, site, need_bwd=True):
+    """(mask_fwd, mask_bwd or None, scale): the keep bits of one dropout site over the support entries of a batch of B graphs,
+    int32 [B, S, 128, 4] each way (gml_dense_rag_mask; include/gml.h has the element index)."""
+    t, scale = Fn.dropout_threshold(p)
+    dev = ptr.device
+    mf = torch.empty(B, S, RAG_NP, 4, dtype=torch.int32, device=dev)
+    mb = torch.empty_like(mf) if need_bwd else None
+    _lib.call('gml_dense_rag_mask', _ptr(ptr), _ptr(mf), _ptr(mb), B, S, ctypes.c_uint64(t), _ptr(state),
+              ctypes.c_uint32(int(site) & 0xffffffff), _stream(dev))
+    return mf, mb, scale
+
+
+def ragged_support_mm(img, mask, scale, gid, ptr, act, G, S, F, sa, so, sum_s):
+    """gml_dense_rag_support_mm: act [N, >= F (+ s sa)] -> [N, F] (sum_s) or [N, S so] on the compact node rows of the batch."""
+    act = act.contiguous()
+    out = torch.empty(int(act.size(0)), F if sum_s else S * so, dtype=torch.float32, device=act.device)
+    _lib.call('gml_dense_rag_support_mm', _ptr(img), _ptr(mask), ctypes.c_float(scale), _ptr(gid), _ptr(ptr), _ptr(act), int(act.stride(0)),
+              int(sa), _ptr(out), int(out.stride(0)), int(so), int(bool(sum_s)), int(ptr.numel() - 1), int(S), int(G), int(F),
+              _stream(act.device))
+    return out
+
+
+class _RaggedProduct(torch.autograd.Function):
+    """Hcat = [(D_0 o M_0) X | ... ] per graph (M: the keep bits times scale, or all ones); d X = sum_s (D_s o M_s)^T d Hcat_s on the
+    transposed images with the transposed bits the forward saved."""
+
+    @staticmethod
+    def forward(ctx, x, bank, gid, ptr, mf, mb, scale):
+        ctx.bank, ctx.gid, ctx.ptr, ctx.mb, ctx.scale, ctx.Fin, ctx.masked = bank, gid, ptr, mb, scale, int(x.size(1)), mf is not None
+        Fn._path('dense', 'ragged support product fwd (bf16x3 HIP)', bank.S, ctx.Fin, ctx.Fin)
+        return ragged_support_mm(bank.fwd, mf, scale, gid, ptr, x, bank.G, bank.S, ctx.Fin, 0, ctx.Fin, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        if ctx.masked and ctx.mb is None:
+            raise RuntimeError('the transposed keep bits were not produced: x did not require a gradient in the forward')
+        bank = ctx.bank
+        Fn._path('dense', 'ragged support product bwd (bf16x3 HIP)', bank.S, ctx.Fin, ctx.Fin)
+        return (ragged_support_mm(bank.bwd, ctx.mb, ctx.scale, ctx.gid, ctx.ptr, g, bank.G, bank.S, ctx.Fin, ctx.Fin, 0, True),) + (None,) * 6
+
+
+def _ragged_library(x, bank, gid, ptr, mf, scale):
+    """The library road: the same product by torch in fp32 on blocks padded to 128 (torch.bmm + the elementwise mask from the SAME
+    keep bits); autograd differentiates it.  No host read: the pad positions come from ptr on the device."""
+    B, S, N, Fin = int(ptr.numel() - 1), bank.S, int(x.size(0)), int(x.size(1))
+    dev = x.device
+    D = bank.blocks[:B] if gid is None else bank.blocks[gid.long()]
+    if mf is not None:
+        sh = torch.arange(32, device=dev, dtype=torch.int32)
+        keep = ((mf.view(B, S, RAG_NP, 4, 1) >> sh) & 1).view(B, S, RAG_NP, RAG_NP)
+        D = D * keep.to(torch.float32) * scale
+    p64 = ptr.to(torch.int64)
+    r = torch.arange(RAG_NP, device=dev)
+    valid = r.unsqueeze(0) < (p64[1:] - p64[:-1]).unsqueeze(1)                       # [B, 128]
+    rows = (p64[:-1].unsqueeze(1) + r.unsqueeze(0)).clamp_(max=max(N - 1, 0))
+    xpad = x[rows.reshape(-1)].view(B, RAG_NP, Fin) * valid.unsqueeze(2).to(x.dtype)
+    h = torch.bmm(D.reshape(B, S * RAG_NP, RAG_NP), xpad).view(B, S, RAG_NP, Fin).permute(0, 2, 1, 3)   # [B, 128, S, Fin]
+    node = torch.arange(N, device=dev)
+    b = torch.searchsorted(p64[1:].contiguous(), node, right=True)
+    return h.reshape(B * RAG_NP, S * Fin)[b * RAG_NP + (node - p64[b])]
+
+
+def spectconv_ragged(x, bank, gid, ptr, weight, bias=None, relu=False, p=0.0, state=None, site=0, training=False):
+    """act(sum_s ((D_s o M_s) x) W_s + bias) on the compact node rows x [N, Fin] of a batch of graphs of different sizes: bank
+    (RaggedSupports), gid int32 [B] (bank slot per graph, None = identity), ptr int32 [B + 1], weight [S, Fin, Fout].  M_s: dropout
+    of the support entries with probability p (training and p > 0: one gml_dense_rag_mask launch with the RNG state `state` and
+    `site`; otherwise no mask launch).  The projection is _TallGemm (its dW = Hcat^T g is a library GEMM: gml_xty_wide stops at 128
+    output columns and these layers are 200 wide).  functional.exact_mode(): the library road (_ragged_library)."""
+    S, Fin, Fout = weight.shape
+    if S != bank.S or Fin != x.size(1):
+        raise ValueError('bank with S=%d does not match x %s / weight %s' % (bank.S, tuple(x.shape), tuple(weight.shape)))
+    ptr = Fn._ptr32(ptr)
+    B = int(ptr.numel() - 1)
+    x = x.contiguous()
+    mf = mb = None
+    scale = 1.0
+    lib = _library()
+    if training and p > 0:
+        mf, mb, scale = ragged_keep_bits(ptr, B, S, p, state, site, need_bwd=x.requires_grad and not lib)
+    if lib:
+        Fn._path('dense', 'ragged support product (torch.bmm fp32)', S, Fin, Fout)
+        h = _ragged_library(x, bank, gid, ptr, mf, scale)
+    else:
+        if Fin > RAG_F:
+            raise ValueError('the ragged dense-block kernel covers Fin <= %d, got %d' % (RAG_F, Fin))
+        h = _RaggedProduct.apply(x, bank, gid, ptr, mf, mb, scale)
     out = _TallGemm.apply(h, weight.reshape(S * Fin, Fout), bias)
     return torch.relu(out) if relu else out

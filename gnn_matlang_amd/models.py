@@ -364,6 +364,53 @@ class GNNML3(torch.nn.Module):
         return self.forward(data, _features=True, _pad_grad_zero=pad_grad_zero)
 
 
+class DSSGCN(torch.nn.Module):
+    """DSSGCN_GC_BATCH (libs/models_tf.py:275-343) as enzymes_contfeats_gnnml3_tf.py:25-32 configures it: two bias-free graph
+    convolutions relu(sum_s (dropout(C_s) dropout(x)) W_s) (GraphConvolutionwithDephSepBatch, libs/layers_tf.py:247-298: dropout on the
+    layer input AND on the support entries, independently per support and layer), the 'meanmax' aggregation, relu(fc1), fc2 (both with
+    bias, dropout on their inputs).  conv1 / conv2 are SpectConv modules used as the parameter holders (convN.weight [S, Fin, Fout],
+    every support slice initialised as libs/inits_tf.py's glorot([Fin, Fout])); the layers run as ragged dense blocks
+    (dense_block.spectconv_ragged on csrc/gml_dense_rag.hip).  forward takes a Batch with `bank` and `gid` attached
+    (dense_block.attach_bank).  Dropout sites: the input dropout of layer i (conv1, conv2, fc1, fc2 = 0 .. 3) is site 2 i, its
+    support dropout site 2 i + 1; one counter step per training forward."""
+
+    def __init__(self, ninp, ne, widths=(200, 200), pool=('mean', 'max'), dense=(100,), nclass=6, dropout=0.1, kernel_dropout=True):
+        super().__init__()
+        Fn.dropout_threshold(dropout)
+        self.nconv, self.pool, self.kernel_dropout = len(widths), pool, bool(kernel_dropout)
+        fin = ninp
+        for i, w in enumerate(widths):
+            setattr(self, 'conv%d' % (i + 1), SpectConv(fin, w, K=ne, selfconn=False, bias=False))
+            fin = w
+        fin *= len(pool) if isinstance(pool, tuple) else 1
+        dims = list(dense) + [nclass]
+        self.nfc = len(dims)
+        for i, w in enumerate(dims):
+            setattr(self, 'fc%d' % (i + 1), torch.nn.Linear(fin, w))
+            fin = w
+        _init_dropout(self, dropout)
+
+    def forward(self, data):
+        from .dense_block import spectconv_ragged
+        drop = _dropout_pass(self)
+        state = self.dropout_state if drop else None
+        x = data.x
+        for i in range(self.nconv):
+            conv = getattr(self, 'conv%d' % (i + 1))
+            x = Fn.dropout(x, self.dropout, drop, state, site=2 * i)
+            x = spectconv_ragged(x, data.bank, data.gid, data.ptr, conv.weight, None, relu=True,
+                                 p=self.dropout if self.kernel_dropout else 0.0, state=state, site=2 * i + 1, training=drop)
+        # pools on the compact rows.  The script's reduce_max (libs/layers_tf.py:320) runs over rows zero-padded to the largest graph:
+        # the conv layers have no bias and end in relu, so every real row is >= 0 and a padding row is exactly 0 -- the same maximum.
+        x = _pool(self.pool, x, data)
+        for i in range(self.nfc):
+            x = Fn.dropout(x, self.dropout, drop, state, site=2 * (self.nconv + i))
+            x = getattr(self, 'fc%d' % (i + 1))(x)
+            if i + 1 < self.nfc:
+                x = torch.relu(x)
+        return x
+
+
 def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
     """the block as one fused launch (functional.GNNML1BlockFunction) or None when the widths are outside the kernel (modes 0..3,
     csrc/gml_gnnml1.hip: input > 144, a part > 64; mode 4, csrc/gml_gnnml1_sum.hip: input > 192, n1 = n2 > 128, n3 > 64) or the conv
@@ -610,6 +657,12 @@ def proteins_gnnml3(ninp=4, ne=4, dropout=0.1):  # proteins.py:259-289
     return GNNML3(ninp, ne, 64, 0, 2, learnedge=False, pool=('mean', 'max'), head='log_softmax', nclass=2, dropout=dropout)
 
 
+def enzymes_contfeat_gnnml3(ninp=22, ne=4, dropout=0.1):  # enzymes_contfeats_gnnml3_tf.py:25-32, libs/models_tf.py:275-343 (two bias-free convs 22 -> 200 -> 200 over ne = 4 supports with input + support dropout, (mean, max) pools, relu(fc1: 400 -> 100), fc2: 100 -> 6)
+    # support order: the script's is [identity, band 0, band 1, band 2], SpectralDesign's [band 0, band 1, band 2, identity]:
+    # weights_i <-> weight[(3, 0, 1, 2)[i]]
+    return DSSGCN(ninp, ne, widths=(200, 200), pool=('mean', 'max'), dense=(100,), nclass=6, dropout=dropout)
+
+
 def zinc_loss(pre, y):                     # Zinc12k.py:365
     return F.l1_loss(pre, y.unsqueeze(-1), reduction='sum')
 
@@ -770,3 +823,9 @@ def tu_step_loss(model, data, valid=None):
     """tu_loss(model(data), data.y) for plain and padded batches alike -- the ``loss_fn(model, data)`` of dist.TrainStep."""
     valid = valid if valid is not None else getattr(data, 'graph_valid', None)
     return tu_loss(model(data), data.y, valid)
+
+
+def dssgcn_loss(model, logits, y, weight_decay=1e-4):   # libs/models_tf.py:286-301
+    """mean softmax cross entropy over the batch + weight_decay . sum of tf.nn.l2_loss(W) = |W|^2 / 2 over every non-bias parameter."""
+    l2 = sum(w.square().sum() for n, w in model.named_parameters() if not n.endswith('bias'))
+    return F.cross_entropy(logits, y.long()) + (0.5 * weight_decay) * l2

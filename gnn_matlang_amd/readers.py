@@ -203,16 +203,18 @@ def load_tu(path, name, contfeat=False):
     return [(np.asarray(F[i] if k is None else F[i][:, 0:k], dtype=np.float32), _edges(A[i]), np.int64(Y[i])) for i in range(A.size)]
 
 
-def standardize_tu(graphs, train_idx):
+def standardize_tu(graphs, train_idx, ddof=1):
     """enzymes_contfeat.py:366-370: x <- (x - mean) / std of EVERY graph, mean and std (unbiased, as torch.std) per column over
-    the nodes of the training graphs `train_idx`.  graphs: the tuples of load_tu or the records of SpectralDesign.design_many
+    the nodes of the training graphs `train_idx`.  ddof=0: the population std, np.std as normalize_wrt_train of
+    enzymes_contfeats_gnnml3_tf.py:119-129 takes it.  graphs: the tuples of load_tu or the records of SpectralDesign.design_many
     (the script standardises after the degree column is appended).  Returns (graphs, (mean, std)): new tuples / records with
     float32 x, the statistics as float64 arrays."""
     xs = lambda g: np.asarray(g['x'] if isinstance(g, dict) else g[0])
     tr = np.concatenate([xs(graphs[int(i)]) for i in train_idx], 0).astype(np.float64)
-    if tr.shape[0] < 2:
-        raise ValueError('standardize_tu: the training graphs have %d nodes; the unbiased std needs two' % tr.shape[0])
-    mean, std = tr.mean(0), tr.std(0, ddof=1)
+    if tr.shape[0] < 1 + ddof:
+        raise ValueError('standardize_tu: the training graphs have %d nodes; the %s std needs %d' %
+                         (tr.shape[0], 'unbiased' if ddof else 'population', 1 + ddof))
+    mean, std = tr.mean(0), tr.std(0, ddof=ddof)
     out = []
     for g in graphs:
         x = ((xs(g).astype(np.float64) - mean) / std).astype(np.float32)

@@ -662,6 +662,33 @@ int gml_dense_big_pack(const float* blocks, uint16_t* img, int64_t nblocks, int3
 int gml_dense_big_support_mm(const uint16_t* dimg, const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo,
                              int32_t so, int32_t sum_s, int32_t S, int32_t n, int32_t KP, int32_t F, void* ws, size_t ws_bytes,
                              gml_stream_t stream);
+/* The same product for a batch of graphs of DIFFERENT sizes, every one of at most NP = 128 nodes, with optional dropout of the
+ * support entries (the TF GNNML3 of enzymes_contfeats_gnnml3_tf.py; libs/layers_tf.py:276-298).  csrc/gml_dense_rag.hip.
+ *   pack       : the bank of a whole data set of G graphs from its collated COO supports (edge_index2 int64 [2][E] with global node
+ *                ids, edge_attr2 fp32 [E][S], batch int64 [N] = the graph of each node, ptr int32 [G + 1]): two bf16 (hi, lo) images
+ *                [G][S][2][NP][NP], img_fwd[g][s][.][j - ptr[g]][i - ptr[g]] = edge_attr2[e][s] for edge e = (i -> j) and img_bwd
+ *                its transposes; hi + lo as the equal-size pack above; entries without an edge are zero (the function zero-fills both
+ *                images itself).  The caller guarantees n_g <= NP: edges that fall outside their graph's block are skipped.
+ *   mask       : the keep bits of ONE dropout site for a batch of B graphs (ptr int32 [B + 1]), uint32 [B][S][NP][4] each way: bit
+ *                (k & 31) of word (k >> 5) of row r of mask_fwd is the decision of the logical element e = ((b S + s) NP + r) NP + k
+ *                under the dropout contract above (Philox4x32-10, counter block (j lo, j hi, site, counter lo), j = e >> 2, word
+ *                e & 3, keep iff draw >= t); mask_bwd (may be NULL) holds the same decisions transposed (bit (r & 31) of word (r >> 5)
+ *                of row k).  Bits with r >= n_b or k >= n_b are zero.  b is the position in the batch, not the bank slot.
+ *   support_mm : out[(ptr[b] + r) ldo + s so + f]  =  scale . sum_{k < n_b} keep(b, s, r, k) . D[gid[b]][s][r][k] . act[(ptr[b] + k) lda + s sa + f]
+ *                for r < n_b = ptr[b + 1] - ptr[b] <= NP and f < F <= 256, summed over s into out[(ptr[b] + r) ldo + f] when sum_s != 0.
+ *                gid int32 [B] maps a batch position to a bank slot (< G; NULL = the identity), the node rows are compact (no padding
+ *                rows).  mask == NULL: no dropout, scale is taken as 1.  The direction is chosen by the image and the bits passed:
+ *                (img_fwd, mask_fwd) with sa = 0 gives Hcat, (img_bwd, mask_bwd) with sa = Fin, sum_s = 1 its adjoint.  bf16x3
+ *                products, fp32 accumulate, no atomics: two launches on the same inputs agree bitwise.
+ * GML_E_UNSUPPORTED outside 1 <= F <= 256, S >= 1; GML_E_BADARG for NULL or misaligned pointers (images and bits 16 bytes, the rest
+ * their element size) and for lda / ldo smaller than the columns used; nothing is launched then. */
+int gml_dense_rag_pack(const int64_t* edge_index2, const float* edge_attr2, const int64_t* batch, const int32_t* ptr,
+                       uint16_t* img_fwd, uint16_t* img_bwd, int64_t E, int64_t N, int32_t G, int32_t S, gml_stream_t stream);
+int gml_dense_rag_mask(const int32_t* ptr, uint32_t* mask_fwd, uint32_t* mask_bwd, int32_t B, int32_t S, uint64_t t,
+                       const int64_t* state, uint32_t site, gml_stream_t stream);
+int gml_dense_rag_support_mm(const uint16_t* dimg, const uint32_t* mask, float scale, const int32_t* gid, const int32_t* ptr,
+                             const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo, int32_t so, int32_t sum_s,
+                             int32_t B, int32_t S, int32_t G, int32_t F, gml_stream_t stream);
 
 /* ---------------------------------------------------------------- node-level readout + masked squared loss (filtering.py:268, :320-327)
  *   gml_node_head_fwd : pre[r] = x[r ldx ..] . w + b[0]  (F <= 64; b may be NULL), loss[0] = sum_r (mask[r ldm] (pre[r] - y[r ldy]))^2;
