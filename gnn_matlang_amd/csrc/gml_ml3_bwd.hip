@@ -381,10 +381,16 @@ __global__ __launch_bounds__((MM ? 2 : 1) * SB_ROWS, (FINP <= 32 || MM ? 2 : 1))
                     const int rr = rbx + j * RPX;
                     if (rr < nr && f < Fin) {
                         const int off = __umul24(rr, lddx) + f;
-                        if constexpr (VX == 4)
-                            *reinterpret_cast<f32x4*>(dxb + off) = f32x4{xs[rr * LDX + f], xs[rr * LDX + f + 1],
-                                                                         xs[rr * LDX + f + 2], xs[rr * LDX + f + 3]};
-                        else dxb[off] = xs[rr * LDX + f];
+                        if constexpr (VX == 4) {
+                            if (f + 4 <= Fin) {
+                                *reinterpret_cast<f32x4*>(dxb + off) = f32x4{xs[rr * LDX + f], xs[rr * LDX + f + 1],
+                                                                             xs[rr * LDX + f + 2], xs[rr * LDX + f + 3]};
+                            } else {                           // the last group of a Fin that is no multiple of 4: dx is [num_rows, Fin],
+#pragma unroll
+                                for (int k = 0; k < 3; ++k)    // the columns between Fin and lddx are the caller's
+                                    if (f + k < Fin) dxb[off + k] = xs[rr * LDX + f + k];
+                            }
+                        } else dxb[off] = xs[rr * LDX + f];
                     }
                 }
             }

@@ -530,6 +530,7 @@ int gml_node_mix_bwd(const float* x, int64_t ldx, const float* w11, const float*
  *   G[:, :nout1] = gy[:, :nout1] * (y[:, :nout1] > 0), G[:, nout1:ldg] = 0      gradient at the conv output
  *   dcb          = column sums of G                                             (NULL: not wanted)
  *   dx           = dz11 w11 + dz12 w12  -- WRITTEN (follow with gml_spectconv_bwd + GML_ACCUM); NULL: not wanted
+ *                  (dx is [num_rows, Fin] in rows of lddx: columns [Fin, lddx) are never written)
  *   dw11, db11, dw12, db12 as gml_node_mix_bwd, from gy[:, nout1:nout1+F2].
  * F2 == 0: no Hadamard branch (x, w*, dw*, dx ignored) -- relu mask + bias sums of a plain SpectConv.
  * workspace_bytes == 0: shape not supported (caller uses gml_relu_bwd + gml_node_mix_bwd). */
