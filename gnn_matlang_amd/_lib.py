@@ -152,6 +152,7 @@ SIGNATURES = {
     'gml_dense_big_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
     'gml_dense_big_pack': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p]),
     'gml_dense_big_support_mm': (ctypes.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p]),
+    'gml_dense_mid_support_mm': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     'gml_dense_rag_pack': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _p]),
     'gml_dense_rag_mask': (ctypes.c_int, [_p, _p, _p, _i32, _i32, ctypes.c_uint64, _p, _u32, _p]),
     'gml_dense_rag_support_mm': (ctypes.c_int, [_p, _p, ctypes.c_float, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p]),

@@ -122,6 +122,48 @@ class DeviceDataset(object):
             out['edge_attr2'] = self.edge_attr2[epos2]
         return Batch(**out)
 
+    # ------------------------------------------------------------------ equal-size graphs of 97 .. 256 nodes: dense blocks from a bank
+    def equal_bank(self):
+        """dense_block.EqualSupports of the whole data set (cached): its graphs must all have the same n, 96 < n <= 256 (freqclass.py:
+        bandclass graphs of 200 nodes) -- ValueError otherwise.  One host read (the graph sizes)."""
+        bank = getattr(self, '_equal_bank', None)
+        if bank is None:
+            from .dense_block import EqualSupports
+            if self.edge_index2 is None:
+                raise ValueError('equal_bank: the data set has no supports (edge_index2 / edge_attr2)')
+            sizes = (self.node_ptr[1:] - self.node_ptr[:-1])
+            lo, hi = (int(v) for v in torch.stack([sizes.min(), sizes.max()]).cpu()) if sizes.numel() else (0, 0)
+            if lo != hi:
+                raise ValueError('equal_bank: the graphs have %d .. %d nodes; the equal-size bank takes ONE size' % (lo, hi))
+            E = int(self.edge_index2.size(1))
+            eg = torch.searchsorted(self.edge_ptr2[1:].contiguous(), torch.arange(E, device=self.edge_ptr2.device), right=True)
+            bank = self._equal_bank = EqualSupports(self.edge_index2 + (eg * lo).unsqueeze(0), self.edge_attr2, self.node_ptr)
+        return bank
+
+    def batch_dense(self, ids, out=None):
+        """Batch of the graphs ``ids`` (int64 tensor on the data set's device, or a sequence) for the batched dense road
+        (models.GNNML3 with the EqualSupports bank of equal_bank()): x [B n, F], y [B], batch, ptr, bank and gid = the bank slots --
+        and NO edge tensors: the layers read the supports from the bank.  The shape depends on B alone, so ONE captured step serves
+        an epoch: out = a batch of an earlier call with as many ids -- its x, y and gid are overwritten in place and it is returned.
+        No host read when ids is a device tensor."""
+        bank = self.equal_bank()
+        dev = self.x.device
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.as_tensor(ids, dtype=torch.int64)
+        ids = ids.to(device=dev, dtype=torch.int64)
+        B, n, F = int(ids.numel()), bank.n, int(self.x.size(1))
+        xs = self.x.view(bank.G, n, F)
+        if out is not None:
+            if getattr(out, 'bank', None) is not bank or int(out.gid.numel()) != B:
+                raise ValueError('batch_dense: out= must be a batch_dense batch of this data set with %d graphs' % B)
+            torch.index_select(xs, 0, ids, out=out.x.view(B, n, F))
+            torch.index_select(self.y, 0, ids, out=out.y)
+            out.gid.copy_(ids)
+            return out
+        return Batch(x=xs[ids].reshape(B * n, F), y=self.y[ids], gid=ids.to(torch.int32),
+                     batch=torch.arange(B, device=dev).repeat_interleave(n, output_size=B * n),
+                     ptr=torch.arange(B + 1, device=dev, dtype=torch.int32) * n, bank=bank)
+
     # ------------------------------------------------------------------ static shapes: one captured step for every batch
     def bounds(self, batch_size):
         """dict(n_pad, e2_pad, dmax, deal, caps) that hold for EVERY batch of batch_size graphs of this data set -- what a

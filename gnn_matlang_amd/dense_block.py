@@ -16,6 +16,11 @@ baseline of tools/bench_mnist.py.  Same parameters and values as ``SpectConv`` o
 One LARGE graph (96 < n <= 1024, F <= 64: the 2-D grid of filtering.py, 900 nodes, a 40 % full mask) takes the same form on
 csrc/gml_dense_big.hip: the work is cut across (support, row block, K slice) instead of across graphs, the projection stays the
 tall GEMM (``_SupportProduct`` dispatches by n; the chained one-launch kernels are n <= 96 only).
+
+Batches of equal-size graphs of 96 < n <= 256 nodes (freqclass.py: bandclass graphs of 200 nodes, 2-hop masks 6-8 % full, S = 6,
+layers 66 -> 64 + 2) take csrc/gml_dense_mid.hip: one workgroup per (graph, 64-row block, support), F <= 128 in one pass.  The
+supports of the whole data set are packed once into an ``EqualSupports`` bank; a batch names its graphs by bank slot (gid), so a
+batch is x, y and gid only -- a static shape without edge tensors (``DeviceDataset.batch_dense``).
 """
 import ctypes
 import os
@@ -63,16 +68,76 @@ def big_applies(num_graphs, n, F):
     return num_graphs == 1 and SMALL_N < n <= BIG_N and 1 <= F <= BIG_F
 
 
+MID_N, MID_F = 256, 128     # gml_dense_mid.hip: B graphs (or a bank) of SMALL_N < n <= MID_N nodes each, F <= MID_F features
+
+
+def mid_applies(num_graphs, n, F, bank=False):
+    """True when the batched-blocks support product (csrc/gml_dense_mid.hip) covers this batch (host integers only): two or more
+    graphs -- or any number of graphs that name their slots in a bank (EqualSupports) -- of SMALL_N < n <= MID_N nodes each."""
+    return (num_graphs >= 2 or (bool(bank) and num_graphs >= 1)) and SMALL_N < n <= MID_N and 1 <= F <= MID_F
+
+
+def _coo_blocks(src, dst, val, g0, g1, S, n):
+    """fp32 blocks [g1 - g0, S, n, n] of the graphs g0 .. g1 - 1 from COO supports with global node ids (graph = id // n):
+    block[g, s][j, i] = value of edge i -> j"""
+    b = torch.div(src, n, rounding_mode='floor')
+    sel = (b >= g0) & (b < g1)
+    src, dst, val, b = src[sel], dst[sel], val[sel], b[sel]
+    blocks = torch.zeros(g1 - g0, S, n, n, dtype=torch.float32, device=val.device)
+    blocks[b - g0, :, dst - b * n, src - b * n] = val
+    return blocks
+
+
+class EqualSupports(object):
+    """Support bank of a data set of G graphs of EQUAL size n, SMALL_N < n <= MID_N (collated COO supports: edge_index2 [2, E] with
+    global node ids, edge_attr2 [E, S], ptr [G + 1]; the mask lists every (i, j) once).  fwd / bwd: int16 [G, S, 2, n, KP] bf16
+    (hi, lo) images of the blocks (row = target node) / of their transposes (gml_dense_big_pack), packed in slabs of graphs whose
+    transient fp32 blocks stay below SLAB_BYTES; blocks: fp32 [G, S, n, n], built on first use -- the library road only
+    (functional.exact_mode() / GML_DENSE_LIB=1).  A batch names its graphs by bank slot (attach_bank: gid)."""
+
+    SLAB_BYTES = 256 << 20
+
+    def __init__(self, edge_index2, edge_attr2, ptr):
+        sizes = (ptr[1:] - ptr[:-1]).cpu().tolist()                # (one host read per data set)
+        if not sizes or min(sizes) != max(sizes) or not SMALL_N < int(sizes[0]) <= MID_N:
+            raise ValueError('the equal-size bank takes graphs of one size n, %d < n <= %d: got sizes %s .. %s over %d graphs'
+                             % (SMALL_N, MID_N, min(sizes) if sizes else '-', max(sizes) if sizes else '-', len(sizes)))
+        self.G = self.B = len(sizes)
+        self.S, self.n = int(edge_attr2.size(1)), int(sizes[0])
+        self.KP = (self.n + 31) // 32 * 32
+        self._ei = edge_index2.to(torch.int64).contiguous()
+        self._ea = edge_attr2.to(torch.float32).contiguous()
+        self._blocks = None
+        dev = self._ea.device
+        G, S, n, KP = self.G, self.S, self.n, self.KP
+        self.fwd = torch.empty(G, S, 2, n, KP, dtype=torch.int16, device=dev)
+        self.bwd = torch.empty_like(self.fwd)
+        slab = max(1, self.SLAB_BYTES // (4 * S * n * n))
+        for g0 in range(0, G, slab):
+            g1 = min(G, g0 + slab)
+            blk = _coo_blocks(self._ei[0], self._ei[1], self._ea, g0, g1, S, n)
+            for img, tr in ((self.fwd, 0), (self.bwd, 1)):
+                _lib.call('gml_dense_big_pack', _ptr(blk), _ptr(img[g0:g1]), (g1 - g0) * S, n, KP, tr, _stream(dev))
+            del blk
+
+    @property
+    def blocks(self):
+        if self._blocks is None:
+            self._blocks = _coo_blocks(self._ei[0], self._ei[1], self._ea, 0, self.G, self.S, self.n)
+        return self._blocks
+
+
 def dense_supports(edge_index2, edge_attr2, ptr, n):
     """DenseSupports of a batch whose graphs all have exactly n nodes (ptr [B+1]): block[b, s][j, i] = value of edge
-    i -> j of support s (the mask lists every (i, j) once)."""
+    i -> j of support s (the mask lists every (i, j) once).  n <= SMALL_N: any number of graphs; ONE graph of up to BIG_N nodes;
+    two or more graphs of up to MID_N nodes (the bank of the batch itself, slots in batch order)."""
     B = int(ptr.numel() - 1)
     S = int(edge_attr2.size(1))
     if B * n != int(ptr[-1]):
         raise ValueError('dense blocks need equal-size graphs: %d graphs, %d nodes, n=%d' % (B, int(ptr[-1]), n))
-    if n > SMALL_N and not (B == 1 and n <= BIG_N):
-        raise ValueError('dense blocks are built for n <= %d nodes per graph, or one graph of up to %d nodes: got %d graphs of %d'
-                         % (SMALL_N, BIG_N, B, n))
+    if n > SMALL_N and not (B == 1 and n <= BIG_N) and not mid_applies(B, n, 1):
+        raise ValueError('dense blocks are built for n <= %d nodes per graph, graphs of up to %d nodes, or one graph of up to %d nodes: '
+                         'got %d graphs of %d' % (SMALL_N, MID_N, BIG_N, B, n))
     src, dst = edge_index2[0], edge_index2[1]
     b = torch.div(src, n, rounding_mode='floor')
     i, j = src - b * n, dst - b * n
@@ -81,10 +146,30 @@ def dense_supports(edge_index2, edge_attr2, ptr, n):
     return DenseSupports(blocks, keep_blocks=_library())
 
 
-def support_mm(img, act, sup, F, sa, so, sum_s):
+def _kind(sup):
+    """the kernel that serves these supports: '' (gml_dense.hip), 'large graph' (gml_dense_big.hip), 'batched blocks' (gml_dense_mid.hip)"""
+    if sup.n <= SMALL_N:
+        return ''
+    return 'large graph' if sup.B == 1 and not isinstance(sup, EqualSupports) else 'batched blocks'
+
+
+def support_mm(img, act, sup, F, sa, so, sum_s, gid=None):
     """gml_dense_support_mm on packed images: act [B n, >= F (+ s sa)] -> [B n, F] (sum_s) or [B n, S so].
-    One graph of more than SMALL_N nodes: gml_dense_big_support_mm (csrc/gml_dense_big.hip)."""
+    One graph of more than SMALL_N nodes: gml_dense_big_support_mm (csrc/gml_dense_big.hip); several, or a bank (EqualSupports) whose
+    slots gid (int32 [B]; None = the first B slots in order) names: gml_dense_mid_support_mm (csrc/gml_dense_mid.hip)."""
     act = act.contiguous()
+    kind = _kind(sup)
+    if kind == 'batched blocks':
+        B = int(act.size(0)) // sup.n
+        if B * sup.n != int(act.size(0)) or (gid is not None and int(gid.numel()) != B) or (gid is None and B > sup.B):
+            raise ValueError('%d rows do not match %s graphs of %d nodes' % (int(act.size(0)), 'the bank slots of %d' % int(gid.numel())
+                                                                             if gid is not None else 'at most %d' % sup.B, sup.n))
+        out = torch.empty(B * sup.n, F if sum_s else sup.S * so, dtype=torch.float32, device=act.device)
+        _lib.call('gml_dense_mid_support_mm', _ptr(img), _ptr(gid), _ptr(act), int(act.stride(0)), int(sa), _ptr(out), int(out.stride(0)),
+                  int(so), int(bool(sum_s)), B, sup.B, sup.S, sup.n, sup.KP, int(F), _stream(act.device))
+        return out
+    if gid is not None:
+        raise ValueError('bank slots (gid) go with an EqualSupports bank')
     out = torch.empty(sup.B * sup.n, F if sum_s else sup.S * so, dtype=torch.float32, device=act.device)
     if sup.n > SMALL_N:
         nws = int(_lib.lib().gml_dense_big_workspace_bytes(sup.S, sup.n, int(F), int(bool(sum_s))))
@@ -101,17 +186,19 @@ class _SupportProduct(torch.autograd.Function):
     """Hcat = [D_0 X | ... | D_{S-1} X] per graph; gradient d X = sum_s D_s^T d Hcat_s (the supports are constants)."""
 
     @staticmethod
-    def forward(ctx, x, sup):
-        ctx.sup, ctx.Fin = sup, int(x.size(1))
-        Fn._path('dense', 'support product fwd (bf16x3 HIP%s)' % (', large graph' if sup.n > SMALL_N else ''), sup.S, ctx.Fin, ctx.Fin)
-        return support_mm(sup.fwd, x, sup, ctx.Fin, 0, ctx.Fin, False)
+    def forward(ctx, x, sup, gid=None):
+        ctx.sup, ctx.Fin, ctx.gid = sup, int(x.size(1)), gid
+        kind = _kind(sup)
+        Fn._path('dense', 'support product fwd (bf16x3 HIP%s)' % (', ' + kind if kind else ''), sup.S, ctx.Fin, ctx.Fin)
+        return support_mm(sup.fwd, x, sup, ctx.Fin, 0, ctx.Fin, False, gid)
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
-            return None, None
-        Fn._path('dense', 'support product bwd (bf16x3 HIP%s)' % (', large graph' if ctx.sup.n > SMALL_N else ''), ctx.sup.S, ctx.Fin, ctx.Fin)
-        return support_mm(ctx.sup.bwd, g, ctx.sup, ctx.Fin, ctx.Fin, 0, True), None
+            return None, None, None
+        kind = _kind(ctx.sup)
+        Fn._path('dense', 'support product bwd (bf16x3 HIP%s)' % (', ' + kind if kind else ''), ctx.sup.S, ctx.Fin, ctx.Fin)
+        return support_mm(ctx.sup.bwd, g, ctx.sup, ctx.Fin, ctx.Fin, 0, True, ctx.gid), None, None
 
 
 def _splits(rows, lo=1024):
@@ -247,22 +334,28 @@ class _DenseConv(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-def spectconv_dense(x, sup, weight, bias, n, relu=False):
-    """x [B*n, Fin], sup from dense_supports, weight [S, Fin, Fout] -> [B*n, Fout] = act(sum_s (D_s x) W_s + bias), act = relu or none."""
+def spectconv_dense(x, sup, weight, bias, n, relu=False, gid=None):
+    """x [B*n, Fin], sup from dense_supports, weight [S, Fin, Fout] -> [B*n, Fout] = act(sum_s (D_s x) W_s + bias), act = relu or none.
+    sup an EqualSupports bank: gid int32 [B] names the bank slot of every graph of x (None: the bank's first B graphs in order)."""
     S, Fin, Fout = weight.shape
-    if sup.n != n or sup.S != S or x.size(0) != sup.B * n:
-        raise ValueError('supports [%d graphs, S=%d, n=%d] do not match x %s / weight %s' %
-                         (sup.B, sup.S, sup.n, tuple(x.shape), tuple(weight.shape)))
-    if sup.blocks is not None:                         # library path (GML_DENSE_LIB=1 / GML_F32_MFMA=1)
+    bank = isinstance(sup, EqualSupports)
+    B = int(x.size(0)) // max(n, 1) if bank else sup.B
+    if sup.n != n or sup.S != S or x.size(0) != B * n or (gid is not None and (not bank or int(gid.numel()) != B)) or (gid is None and B > sup.B):
+        raise ValueError('supports [%d graphs, S=%d, n=%d] do not match x %s / weight %s%s' %
+                         (sup.B, sup.S, sup.n, tuple(x.shape), tuple(weight.shape), '' if gid is None else ' / %d bank slots' % int(gid.numel())))
+    if _library() if bank else sup.blocks is not None:   # library path (GML_DENSE_LIB=1 / GML_F32_MFMA=1)
         Fn._path('dense', 'support product (torch.bmm fp32)', S, Fin, Fout)
-        h = torch.bmm(sup.blocks.view(sup.B, S * n, n), x.view(sup.B, n, Fin))
-        h = h.view(sup.B, S, n, Fin).permute(0, 2, 1, 3).reshape(sup.B * n, S * Fin)
+        D = sup.blocks if not bank else (sup.blocks[:B] if gid is None else sup.blocks[gid.long()])
+        h = torch.bmm(D.reshape(B, S * n, n), x.view(B, n, Fin))
+        h = h.view(B, S, n, Fin).permute(0, 2, 1, 3).reshape(B * n, S * Fin)
     else:
-        if Fin > (BIG_F if n > SMALL_N else 128):
-            raise ValueError('the dense-block kernel covers Fin <= %d at n = %d, got %d' % (BIG_F if n > SMALL_N else 128, n, Fin))
+        kind = _kind(sup)
+        fmax = MID_F if kind == 'batched blocks' else BIG_F if kind else 128
+        if Fin > fmax:
+            raise ValueError('the dense-block kernel covers Fin <= %d at n = %d, got %d' % (fmax, n, Fin))
         if CHAIN and Fout <= 128 and n <= SMALL_N:
             return _DenseConv.apply(x, weight, bias, sup, relu)
-        h = _SupportProduct.apply(x, sup)
+        h = _SupportProduct.apply(x, sup, gid)
     out = _TallGemm.apply(h, weight.reshape(S * Fin, Fout), bias)
     return torch.relu(out) if relu else out
 
@@ -312,7 +405,7 @@ class RaggedSupports(object):
 
 
 def attach_bank(batch, bank, gid=None):
-    """batch with the fields a ragged dense model reads: bank (RaggedSupports) and gid (int32 [B] on the bank's device: the bank slot
+    """batch with the fields a bank-reading dense model reads: bank (RaggedSupports or EqualSupports) and gid (int32 [B] on the bank's device: the bank slot
     of every graph of the batch; None = the batch is the bank's first B graphs in order)."""
     batch.bank, batch.gid = bank, (None if gid is None else gid.to(torch.int32).contiguous())
     return batch

@@ -262,20 +262,35 @@ class GNNML3(torch.nn.Module):
             return False
         return big_applies(int(data.ptr.numel()) - 1, N, fmax) and E >= DENSE_BIG_MIN_FILL * N * N
 
-    def _forward_dense_big(self, data, x, drop):
+    def _dense_mid(self, data):
+        """True when this batch can take the batched dense road (dense_block.py on csrc/gml_dense_mid.hip): it carries an
+        EqualSupports bank (DeviceDataset.batch_dense / dense_block.attach_bank), no layer learns its supports, and none of bn /
+        dense_n / pad_graph is on.  The road is opt-in through the bank: no fill threshold picks it."""
+        from .dense_block import EqualSupports
+        if not isinstance(getattr(data, 'bank', None), EqualSupports):
+            return False
+        if self.dense_n or self.bn or getattr(data, 'pad_graph', False):
+            return False
+        return not any(getattr(self, 'conv%d' % (i + 1)).learnedge for i in range(self.nlayers))
+
+    def _forward_dense_big(self, data, x, drop, bank=None, gid=None):
         """cat[relu(dense conv), tanh(fc11 x) * tanh(fc12 x)] per layer on the dense blocks of the one graph (cached on the batch
-        like the CSR).  The support product and its adjoint are gml_dense_big_support_mm, the projection and its gradients the
-        tall GEMM of dense_block.py; under exact_products() the fp32 library product serves."""
+        like the CSR), or on the slots gid of an EqualSupports bank.  The support product and its adjoint are
+        gml_dense_big_support_mm (bank: gml_dense_mid_support_mm), the projection and its gradients the tall GEMM of dense_block.py;
+        under exact_products() the fp32 library product serves."""
         from .dense_block import dense_supports, spectconv_dense, _library
-        n = int(x.size(0))
-        sp = getattr(data, '_spT', None)
-        if sp is None or sp.n != n or (sp.blocks is not None) != bool(_library()):
-            sp = data._spT = dense_supports(data.edge_index2, data.edge_attr2, data.ptr, n)
+        if bank is not None:
+            sp, n = bank, bank.n
+        else:
+            n = int(x.size(0))
+            sp = getattr(data, '_spT', None)
+            if sp is None or sp.n != n or (sp.blocks is not None) != bool(_library()):
+                sp = data._spT = dense_supports(data.edge_index2, data.edge_attr2, data.ptr, n)
         for i in range(self.nlayers):
             layer = getattr(self, 'conv%d' % (i + 1))
             if drop:
                 x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i)
-            a = spectconv_dense(x, sp, layer.conv1.weight, layer.conv1.bias, n, relu=True)
+            a = spectconv_dense(x, sp, layer.conv1.weight, layer.conv1.bias, n, relu=True, gid=gid)
             if layer.nout2 > 0:
                 Fn._path('dense', 'Hadamard half (library GEMMs + tanh)', '-', int(x.size(1)), layer.nout2)
                 a = torch.cat([a, torch.tanh(tall_linear(x, layer.fc11)) * torch.tanh(tall_linear(x, layer.fc12))], 1)
@@ -284,7 +299,8 @@ class GNNML3(torch.nn.Module):
 
     def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False, _road=None):
         """_road (tests and tools/bench_filtering.py): 'dense' / 'sparse' overrides the road choice of _dense_big for a batch both
-        roads cover; None: the choice."""
+        roads cover; None: the choice.  A batch with an EqualSupports bank (_dense_mid) takes the batched dense road unless
+        _road='sparse', which needs the batch's edge tensors (ValueError without them)."""
         x = data.x
         padded = getattr(data, 'pad_graph', False)
         if padded and self.training and (self.readout_bn or self.pool_bn is not None):
@@ -295,13 +311,25 @@ class GNNML3(torch.nn.Module):
         if self._chain and self.dropout > 0:
             self._declare_chain(not drop)
         nvalid = _node_valid(data) if padded and self.training and self.bn else None     # the bnN layers: real nodes only
-        big = self._dense_big(data) if _road is None else (_road == 'dense')
+        mid = self._dense_mid(data) and _road != 'sparse'        # a batch with an EqualSupports bank: the batched dense road
+        if not mid and getattr(data, 'bank', None) is not None and getattr(data, 'edge_index2', None) is None:
+            raise ValueError("the sparse road cannot serve this batch: it has no edge tensors (DeviceDataset.batch_dense: x, y and bank slots only); "
+                             "the sparse road needs a batch collated with edge_index2 / edge_attr2")
+        big = False if mid else self._dense_big(data) if _road is None else (_road == 'dense')
         if self.head == 'node' and self._chain:
             # the relu hand-over between stacked sparse layers is withdrawn on the dense road (as dense_n does at construction)
             self._declare_chain(not big and not drop)
+        if self._chain and (mid or getattr(self, '_mid_withdrawn', False)):
+            self._declare_chain(not mid and not big and not drop)   # withdrawn on the batched dense road too, back for the next sparse batch
+            self._mid_withdrawn = mid
         if big:
             x = self._forward_dense_big(data, x, drop)
             return x if _features else tall_linear(x, self.fc2)
+        if mid:
+            x = self._forward_dense_big(data, x, drop, bank=data.bank, gid=getattr(data, 'gid', None))
+            if self.head == 'node':
+                return x if _features else tall_linear(x, self.fc2)
+            return self._readout(x, data, False, _features, _capture)
         if self.dense_n:
             from .dense_block import dense_supports, spectconv_dense, _library
             sp = getattr(data, '_spT', None)                    # per-batch data, like the CSR
@@ -337,6 +365,10 @@ class GNNML3(torch.nn.Module):
                 x = bn(x) if nvalid is None else bn(x, valid=nvalid)
         if self.head == 'node':
             return x if _features else tall_linear(x, self.fc2)
+        return self._readout(x, data, pooled, _features, _capture)
+
+    def _readout(self, x, data, pooled, _features, _capture):
+        """pool (unless the last layer pooled already), the readout normalisations and the head of a graph-level model"""
         if not pooled:
             x = _pool(self.pool, x, data)
         if self.readout_bn:
@@ -562,6 +594,15 @@ def freqclass_gnnml1(ninp=1, dropout=0.2):  # freqclass.py:235-300 (three blocks
     return GNNML1Blocks(ninp, (32, 32, 32), 3, form='product', act='relu', pool='mean', head='mlp32', dropout=dropout)
 
 
+def freqclass_gnnml3(ninp=1, ne=6, dropout=0.2):
+    """freqclass.py:300-338, the script's default model (:344): three ML3Layer(learnedge=False, nout1=64, nout2=2) over the ne = 6
+    supports of SpectralDesign(recfield=2, dv=4, nfreq=5), dropout 0.2 in front of every layer, mean-pool, relu(fc1: 66 -> 32),
+    fc2: 32 -> 1.  The bandclass graphs all have 200 nodes: batches of DeviceDataset.batch_dense (an EqualSupports bank, no edge
+    tensors) take the batched dense road (csrc/gml_dense_mid.hip); batches collated with edges the sparse road.  Loss and accuracy:
+    freqclass_step_loss / accuracy_from_stats."""
+    return GNNML3(ninp, ne, 64, 2, 3, learnedge=False, pool='mean', head='mlp', hidden=32, dropout=dropout)
+
+
 def ptc_gnnml1(ninp=20, dropout=0.1):
     """ptc.py:273-321: two blocks 32 | 64 | 2 of [relu | relu | tanh . tanh], bn1 after block 1 only (bn2 .. bn4 declared, never
     called), (add, max) pools, relu(fc1: 196 -> 100), log_softmax(fc2: 100 -> 2).  bn1 is 98 wide: beyond the masked BatchNorm
@@ -777,6 +818,12 @@ def exp_classify_step_loss(model, data, valid=None, stats=None):
             ok = ((pre[:nl, 0] > 0) == (data.y[:nl] == 1)).to(pre.dtype)
             stats[:3].add_(torch.stack([loss.detach(), (ok * v).sum(), (v != 0).to(pre.dtype).sum()]))
     return loss
+
+
+# freqclass.py:368-375 / :385-390: the same sum BCE on sigmoid(pre[:, 0]) and the same count of round(sigmoid) == y.  The head of
+# freqclass_gnnml3 has 66 inputs, outside gml_head_bce.hip's 64: it takes the torch-op road of the function above (the GNNML1 model's
+# 96 inputs do too); accuracy_from_stats reads the sums.
+freqclass_step_loss = exp_classify_step_loss
 
 
 def accuracy_from_stats(stats):

@@ -12,6 +12,7 @@ libs/utils.py:509) inside PyG ``InMemoryDataset.process`` bodies; neither PyG no
   load_graph8c  libs/utils.py:453-487  (graph8c.g6 -> x = ones, undirected edge_index, y = 0)
   load_exp      libs/utils.py:424-451  (EXP's GRAPHSAT.pkl as converted by tools/convert_exp.py -> x, edge_index, y)
   load_twodgrid libs/utils.py:333-355  (TwoDGrid30.mat -> train / test / val records of ONE grid: x, per-node y [n, 3], mask)
+  load_bandclass libs/utils.py:289-305 (bandclass.mat -> x [n, 1], edge_index, 0 / 1 label per graph; freqclass.py)
 
 Each returns graphs as (x [n, f] float32, edge_index [2, e] int64 in row-major ``np.where`` order, y), the input format
 of ``SpectralDesign.design_many`` / ``graph.collate``.
@@ -235,6 +236,18 @@ def load_twodgrid(path):
     mask = np.ascontiguousarray(F[:, 12:13])
     return [dict(x=np.ascontiguousarray(F[:, c:c + 1]), edge_index=ei, y=np.ascontiguousarray(F[:, c + 1:c + 4]), mask=mask)
             for c in (0, 4, 8)]
+
+
+def load_bandclass(path):
+    """libs/utils.py:289-305 (BandClassDataset): the graphs of bandclass.mat -- A [G, n, n] adjacencies, F [G, n] one signal per
+    node, Y [G, 1] the 0 / 1 label -- as (x float32 [n, 1], edge_index where A > 0, y float32), the records freqclass.py trains
+    on (its sum BCE takes data.y as a float)."""
+    a = read_mat(path)
+    A, F, Y = np.asarray(a['A']), np.asarray(a['F']), np.asarray(a['Y'])
+    if A.ndim != 3 or A.shape[1] != A.shape[2] or F.shape != A.shape[:2] or Y.reshape(-1).size != A.shape[0]:
+        raise ValueError('%s: expected A [G, n, n], F [G, n], Y [G, 1], got %s, %s, %s' % (path, A.shape, F.shape, Y.shape))
+    Y = Y.reshape(-1)
+    return [(np.ascontiguousarray(F[i].astype(np.float32).reshape(-1, 1)), _edges(A[i]), np.float32(Y[i])) for i in range(A.shape[0])]
 
 
 def design_twodgrid(records, design):

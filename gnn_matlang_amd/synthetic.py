@@ -10,6 +10,9 @@ tests use these generators:
   C  counting-like  : G(n,p), n ~ U{10..30}, p = 0.3; x = [1]; targets = triangle
                       count trace(A^3)/6 (libs/utils.py:395-397)
   M  MNIST-75-like  : n = 75, k-NN graph on random 2-D points, 2 features U(0,1)
+  B  bandclass-like : n = 200, k-NN graph (k = 5), one band-pass filtered noise signal
+                      per node, y = whether its centre frequency lies in a fixed band
+                      (stand-in for freqclass.py's bandclass.mat)
   R  sr25-like      : the 15 real strongly-regular graphs ship as a fixture
                       (tests/golden/data_sr25.npz); ``random_regular`` here is the
                       synthetic stand-in for benches.
@@ -94,8 +97,37 @@ def random_regular(rng, n=25, d=12):
     return x, _edges_from_adj(A), np.float32(0)
 
 
+# the label band of bandclass_like_graph on the normalised-Laplacian spectrum [0, 2]: about half of the eigenvalues of these k-NN
+# graphs lie inside it (139 of 256 graphs at n = 200, seed 0, carry label 1)
+BANDCLASS_BAND = (0.7, 1.3)
+
+
+def bandclass_like_graph(rng, n=200, k=5, width=0.1):
+    """A STAND-IN for the graphs of bandclass.mat (freqclass.py; the file is not available: it is one of the reference's missing
+    large blobs, so neither its graphs' degree nor their mask fill is known here).  Symmetrised k-NN graph over n random 2-D points
+    (mean degree 5-6 at k = 5), one signal per node, a 0 / 1 label: a centre frequency c is drawn among the eigenvalues of the
+    graph's normalised Laplacian L = I - D^-1/2 A D^-1/2, the signal is white noise filtered by the narrow Gaussian band-pass
+    exp(-((lambda - c) / width)^2) around c and scaled to unit variance, and y = 1 when c lies in BANDCLASS_BAND.  Telling the two
+    classes apart needs a spectral filter of the kind the supports of SpectralDesign(nfreq=5) span."""
+    pts = rng.random((n, 2))
+    d2 = ((pts[:, None, :] - pts[None, :, :]) ** 2).sum(-1)
+    np.fill_diagonal(d2, np.inf)
+    nn = np.argsort(d2, axis=1)[:, :k]
+    A = np.zeros((n, n), dtype=np.float32)
+    A[np.repeat(np.arange(n), k), nn.ravel()] = 1
+    A = np.maximum(A, A.T)
+    dis = 1.0 / np.sqrt(A.sum(1).astype(np.float64))
+    L = np.eye(n) - dis[:, None] * A.astype(np.float64) * dis[None, :]
+    lam, U = np.linalg.eigh(L)
+    c = float(lam[int(rng.integers(n))])
+    sig = U @ (np.exp(-((lam - c) / width) ** 2) * (U.T @ rng.standard_normal(n)))
+    x = (sig / max(float(sig.std()), 1e-12)).astype(np.float32).reshape(n, 1)
+    y = np.int64(BANDCLASS_BAND[0] <= c < BANDCLASS_BAND[1])
+    return x, _edges_from_adj(A), y
+
+
 _GEN = dict(zinc=zinc_like_graph, counting=counting_like_graph,
-            mnist75=mnist75_like_graph, regular=random_regular)
+            mnist75=mnist75_like_graph, regular=random_regular, bandclass=bandclass_like_graph)
 
 
 def make_graphs(kind, count, seed=0, **kw):

@@ -663,6 +663,22 @@ int gml_dense_big_pack(const float* blocks, uint16_t* img, int64_t nblocks, int3
 int gml_dense_big_support_mm(const uint16_t* dimg, const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo,
                              int32_t so, int32_t sum_s, int32_t S, int32_t n, int32_t KP, int32_t F, void* ws, size_t ws_bytes,
                              gml_stream_t stream);
+/* The same product for a BATCH of equal-size graphs of 96 < n <= 256 nodes, F <= 128, any S >= 1 (freqclass.py: graphs of 200 nodes,
+ * S = 6, layers 66 -> 64 + 2).  csrc/gml_dense_mid.hip.  dimg is a bank [G][S][2][n][KP] of the images above
+ * (gml_dense_big_pack with nblocks = G S; KP = 32 ceil(n / 32)); graph b of the batch reads slot g_b = gid ? gid[b] : b (gid int32 [B],
+ * the caller guarantees 0 <= gid[b] < G; gid = NULL needs B <= G).
+ *   gml_dense_mid_support_mm : out[(b n + r) ldo + s so + f]  =  sum_{k < n} D[g_b][s][r][k] . act[(b n + k) lda + s sa + f]   (r < n, f < F),
+ *                              summed over s into out[(b n + r) ldo + f] when sum_s != 0.  Forward: sa = 0, so = F; adjoint: the
+ *                              transposed bank, sa = F, sum_s = 1.  Rows >= B n of act and columns outside [s sa, s sa + F) are never
+ *                              read; only the named columns of rows < B n of out are written.  Rows of any stride: float4 accesses
+ *                              where rows are 16-byte addressable, scalar ones otherwise.
+ * One workgroup per (graph, 64-row block, support) -- per (graph, 64-row block) with sum_s, the supports in ascending order -- forms
+ * the whole K sum: one launch, no workspace, no atomics, bitwise the same result on every run.  bf16x3 products, fp32 accumulate.
+ * GML_E_UNSUPPORTED outside 96 < n <= 256, 1 <= F <= 128, KP = 32 ceil(n / 32), S, B, G >= 1; GML_E_BADARG for NULL dimg / act / out,
+ * images that are not 16-byte aligned, or lda / ldo smaller than the columns used.  Nothing is launched on either. */
+int gml_dense_mid_support_mm(const uint16_t* dimg, const int32_t* gid, const float* act, int64_t lda, int32_t sa, float* out,
+                             int64_t ldo, int32_t so, int32_t sum_s, int32_t B, int32_t G, int32_t S, int32_t n, int32_t KP,
+                             int32_t F, gml_stream_t stream);
 /* The same product for a batch of graphs of DIFFERENT sizes, every one of at most NP = 128 nodes, with optional dropout of the
  * support entries (the TF GNNML3 of enzymes_contfeats_gnnml3_tf.py; libs/layers_tf.py:276-298).  csrc/gml_dense_rag.hip.
  *   pack       : the bank of a whole data set of G graphs from its collated COO supports (edge_index2 int64 [2][E] with global node
