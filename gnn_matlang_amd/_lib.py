@@ -115,6 +115,10 @@ SIGNATURES = {
     'gml_gnnml1_sum_fwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _i64, _p, _i64, _p]),
     'gml_gnnml1_sum_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p,
                                           _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
+    'gml_gnnml1_actsum_supported': (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    'gml_gnnml1_actsum_fwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _i64, _p, _i64, _p]),
+    'gml_gnnml1_actsum_bwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32,
+                                             _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     'gml_edge_mlp_bwd_parts': (_i64, [_i64, _i32, _i32, _i32, _i32]),
     'gml_edge_mlp_plan': (_i32, [_i32, _i32, _i32, _i32, _u32]),
     'gml_edge_mlp_wide_fwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),

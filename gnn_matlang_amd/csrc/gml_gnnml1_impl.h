@@ -6,12 +6,15 @@
 //   mode 1 (CAT_PROD, concat = True):         out = [act(a) | act(c) | act(f2 * f3)]                     [N, n1 + n2 + n3]
 //   mode 2 (CAT_FACT, mutag.py):              out = [act(a) | act(c) | act(f2) * act(f3)]
 //   mode 3 (CAT_TANH, ptc.py:311):            out = [act(a) | act(c) | tanh(f2) * tanh(f3)]            (mode 2 with the factors' activation fixed)
+//   mode 5 (ACT_SUM,  filtering.py:246):      out = act(a) + act(c) + act(f2 * f3)                       [N, n]   (G1_M5 units only)
 //
-// This header holds the device code; two translation units compile it, each under its own kernel names (G1_K):
+// This header holds the device code; three translation units compile it, each under its own kernel names (G1_K):
 //   gml_gnnml1.hip       gml_k_gnnml1_*:  FPL = 4 / 16 (Fin <= 64), modes 0 .. 2, 4 x blocks in the weight gradients -- the kernels of
 //                        rounds 5-6, their device code unchanged (G1_M3 = 0, G1_NXB = 4: the defaults)
 //   gml_gnnml1_wide.hip  gml_k_gnnml1w_*: FPL = 24 / 28 / 36 (Fin <= 96 / 112 / 144), and every FPL with mode 3 compiled in
 //                        (G1_M3 = 1); 9 x blocks in the weight gradients (G1_NXB = 9: 72 accumulator registers)
+//   gml_gnnml1_act.hip   gml_k_gnnml1a_*: mode 5 (G1_M5 = 1), every FPL; its forward and phase 1 read / write the recorded relu
+//                        patterns; phase 2 and the weight gradients are mode 1's (the g4 layout is the same)
 //
 // Rounds 1-4 ran the block as three library Linears, one S = 1 SpectConv launch, a product, two sums / a concatenation and the
 // activation: ~9 launches forward, ~25 backward, every intermediate through HBM.  Here: ONE launch forward; backward = one launch
@@ -35,6 +38,14 @@
 #endif
 #ifndef G1_K
 #define G1_K(stem) gml_k_gnnml1_##stem
+#endif
+// G1_M5 = 1 (gml_gnnml1_act.hip) compiles mode 5 in: out = act(a) + act(c) + act(f2 * f3), whose forward records the relu patterns of
+// a and c into G1_P::pat (G1_P: the kernels' parameter struct, there GmlG1Params extended by `pat, ldp`)
+#ifndef G1_M5
+#define G1_M5 0
+#endif
+#ifndef G1_P
+#define G1_P GmlG1Params
 #endif
 
 template <int FPL>
@@ -85,7 +96,7 @@ __device__ __forceinline__ f32x4 g1_block(const float* wl, int blk, int lane, co
 
 // ------------------------------------------------------------------------------------------------------------------ forward
 template <int FPL>
-__global__ __launch_bounds__(64 * G1_NW) void G1_K(fwd)(const GmlG1Params p) {
+__global__ __launch_bounds__(64 * G1_NW) void G1_K(fwd)(const G1_P p) {
     constexpr bool M3 = G1_M3;
     extern __shared__ __attribute__((aligned(16))) float wl[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, kq = lane >> 4;
@@ -113,6 +124,28 @@ __global__ __launch_bounds__(64 * G1_NW) void G1_K(fwd)(const GmlG1Params p) {
 #pragma unroll
             for (int j = 0; j < FPL; ++j) hr[j] = fmaf(v, xn[j], hr[j]);
         }
+#if G1_M5
+        if (p.mode == 5) {                                                         // three activated parts in the same columns
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) {
+                if (nb >= nb1) break;
+                const int c0 = 16 * nb + 4 * kq;
+                const f32x4 a = g1_block<FPL>(wl, o1 + nb, lane, xr) + g1_bias4(p.b1, c0, p.n1);
+                const f32x4 c = g1_block<FPL>(wl, oc + nb, lane, hr) + g1_bias4(p.bc, c0, p.n2);
+                const f32x4 f2 = g1_block<FPL>(wl, o2 + nb, lane, xr) + g1_bias4(p.b2, c0, p.n3);
+                const f32x4 f3 = g1_block<FPL>(wl, o3 + nb, lane, xr) + g1_bias4(p.b3, c0, p.n3);
+                f32x4 y;
+                unsigned bits = 0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    y[u] = g1_act(a[u], p.act) + g1_act(c[u], p.act) + g1_act(f2[u] * f3[u], p.act);
+                    bits |= (a[u] > 0.f ? 1u << u : 0u) | (c[u] > 0.f ? 16u << u : 0u);
+                }
+                g1_store4(p.out, p.ldo, row, c0, p.n1, valid, y);
+                if (p.pat && valid) p.pat[row * p.ldp + (c0 >> 2)] = (uint8_t)bits;   // byte 4 nb + kq: the lane's 4 columns
+            }
+        } else
+#endif
         if (p.mode == 0) {
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) {
@@ -173,7 +206,7 @@ __global__ __launch_bounds__(64 * G1_NW) void G1_K(fwd)(const GmlG1Params p) {
 // writes g4; phase 2 (transposed forms: 64 KB, two workgroups per CU) gathers dc from g4 -- half the gathered bytes --, re-reads its
 // own row's blocks, writes q and forms dx.
 template <int FPL, int PH>
-__global__ __launch_bounds__(64 * G1_NW) void G1_K(bwd)(const GmlG1Params p) {
+__global__ __launch_bounds__(64 * G1_NW) void G1_K(bwd)(const G1_P p) {
     constexpr bool M3 = G1_M3;
     extern __shared__ __attribute__((aligned(16))) float wl[];
     using C = GmlG1Cfg<FPL>;
@@ -232,6 +265,20 @@ __global__ __launch_bounds__(64 * G1_NW) void G1_K(bwd)(const GmlG1Params p) {
                 f2 = g1_block<FPL>(wf, nb, lane, xr) + g1_bias4(p.b2, c0, p.n3);
                 f3 = g1_block<FPL>(wf, nb3 + nb, lane, xr) + g1_bias4(p.b3, c0, p.n3);
             }
+#if G1_M5
+            if (p.mode == 5) {                               // relu: a's and c's patterns from the recorded byte, f2 f3's recomputed
+                if (nb < nb1) {
+                    const f32x4 go = g1_load4(p.gout, p.ldgo, row, c0, p.n1, valid);
+                    const unsigned bits = valid ? p.pat[row * p.ldp + (c0 >> 2)] : 0u;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const float g = f2[u] * f3[u] > 0.f ? go[u] : 0.f;
+                        da[nb][u] = (bits >> u) & 1u ? go[u] : 0.f; dc[nb][u] = (bits >> (4 + u)) & 1u ? go[u] : 0.f;
+                        d2[nb][u] = g * f3[u]; d3[nb][u] = g * f2[u];
+                    }
+                }
+            } else
+#endif
             if (sum) {
                 if (nb < nb1) {
                     const f32x4 go = g1_load4(p.gout, p.ldgo, row, c0, p.n1, valid), oo = g1_load4(p.out, p.ldo, row, c0, p.n1, valid);
@@ -330,6 +377,7 @@ struct GmlG1DwParams {
     float* part; int64_t nflat; int32_t rows_per_wg;
 };
 
+#if !G1_M5                                                             // (mode 5 takes mode 1's pass from gml_gnnml1_dw: no third copy)
 __global__ __launch_bounds__(64 * G1_NW) void G1_K(dw)(const GmlG1DwParams p) {
     constexpr int NXB = G1_NXB;                                        // x blocks (16 features each) a wave holds accumulators for
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), c16 = lane & 15, k4 = lane >> 4;
@@ -440,6 +488,7 @@ __global__ __launch_bounds__(64 * G1_NW) void G1_K(dw)(const GmlG1DwParams p) {
         if (NXB <= G1_NW) break;                                       // (one x block per wave: a plain `if (wave < nfb)`)
     }
 }
+#endif
 
 
 // ------------------------------------------------------------------------------------------------------------ launch plumbing

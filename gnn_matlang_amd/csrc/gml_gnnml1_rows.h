@@ -1,4 +1,4 @@
-// The pieces every GNNML1 block kernel shares (gml_gnnml1_impl.h: modes 0 .. 3; gml_gnnml1_sum.hip: the sum-and-factors form): the
+// The pieces every GNNML1 block kernel shares (gml_gnnml1_impl.h: modes 0 .. 3 and 5; gml_gnnml1_sum.hip: the sum-and-factors form): the
 // kernel parameters, the activation, and 4-column accesses of a row that take a 16-byte path where stride and base allow it and a
 // scalar path otherwise.
 #pragma once

@@ -718,11 +718,14 @@ def xty(a, b):
     return out
 
 
-def gnnml1_block_supported(x, Fin, n1, n2, n3, mode):
+def gnnml1_block_supported(x, Fin, n1, n2, n3, mode, act=1):
     """the fused block (GNNML1BlockFunction) serves this input.  Modes 0..3: inputs up to 144 wide, parts up to 64; mode 4 (its own
-    kernel family): n1 = n2 <= 128, n3 <= 64, Fin <= 192"""
+    kernel family): n1 = n2 <= 128, n3 <= 64, Fin <= 192; mode 5: three equal parts up to 64, inputs up to 144, and act = 1 (relu)
+    only -- the one mode whose answer depends on the activation (tanh there runs on the composition)"""
     if not (x.is_cuda and x.dtype == torch.float32) or _os.environ.get('GML_NO_GNNML1_FUSED'):
         return False
+    if int(mode) == 5:
+        return bool(_lib.lib().gml_gnnml1_actsum_supported(int(Fin), int(n1), int(n2), int(n3), int(act)))
     if int(mode) == 4:
         return bool(_lib.lib().gml_gnnml1_sum_supported(int(Fin), int(n1), int(n2), int(n3)))
     return bool(_lib.lib().gml_gnnml1_supported(int(Fin), int(n1), int(n2), int(n3), int(mode)))
@@ -733,12 +736,16 @@ class GNNML1BlockFunction(torch.autograd.Function):
     backward = one launch (g4, q = A dc, dx only when x needs it) and one weight-gradient pass + fold.  a = fc_i1 x, c = conv_i1 x
     (SpectConv K = 1), f2 = fc_i2 x, f3 = fc_i3 x;
     mode 0: act(a + c + f2 f3); 1: [act a | act c | act(f2 f3)]; 2: [act a | act c | act f2 . act f3]; 3: [act a | act c | tanh f2 . tanh f3]
-    (ptc.py:311); 4: [act a + act c | act f2 . act f3] with n1 = n2; act 0 tanh / 1 relu.  Modes 0..3 (csrc/gml_gnnml1.hip): inputs up
+    (ptc.py:311); 4: [act a + act c | act f2 . act f3] with n1 = n2; 5: act a + act c + act(f2 f3) with n1 = n2 = n3 (filtering.py:246);
+    act 0 tanh / 1 relu.  Modes 0..3 (csrc/gml_gnnml1.hip): inputs up
     to 144 wide, parts up to 64; mode 4 (csrc/gml_gnnml1_sum.hip): inputs up to 192 wide, n1 <= 128, n3 <= 64
     (gnnml1_block_supported); rows of any stride.  Mode 4 differs in three places: its entry points, the pattern buffer and what is
     saved.  With relu its forward records the two activation patterns of the sum (one byte per 4 columns, saved for backward instead of
     `out`) and phase 1 reads them; tanh, or record=False: phase 1 recomputes a and c (the same bits).  record has no effect in modes
-    0..3.  val: per-edge values in TARGET order ([E] / [E, 1]) or None for ones (the scripts pass torch.ones); they carry no gradient
+    0..3.  Mode 5 (csrc/gml_gnnml1_act.hip; relu only, inputs up to 144 wide, parts up to 64) always records the patterns of a and c
+    in mode 4's byte layout, saves them instead of `out`, and its phase 1 forms g4 from gout, the bytes and the recomputed f2, f3; the g4
+    it writes is mode 1's, so the weight-gradient pass runs as mode 1.  tanh in mode 5 is not served (TypeError here; the module
+    composes it).  val: per-edge values in TARGET order ([E] / [E, 1]) or None for ones (the scripts pass torch.ones); they carry no gradient
     here (the module takes the unfused road when edge_attr requires one).  Exact fp32 products."""
 
     @staticmethod
@@ -748,7 +755,9 @@ class GNNML1BlockFunction(torch.autograd.Function):
         N, Fin = int(x.size(0)), int(x.size(1))
         n1, n2, n3 = int(w1.size(0)), int(wc.size(-1)), int(w2.size(0))
         w1, w2, w3, wc = _f32c(w1, 'fc1.weight'), _f32c(w2, 'fc2.weight'), _f32c(w3, 'fc3.weight'), _f32c(wc, 'conv.weight')
-        C = n1 if mode == 0 else (n1 + n3 if mode == 4 else n1 + n2 + n3)
+        C = n1 if mode in (0, 5) else (n1 + n3 if mode == 4 else n1 + n2 + n3)
+        if mode == 5 and act != 1:
+            raise TypeError('GNNML1 block mode 5 is fused for relu only (gnnml1_block_supported)')
         dev = x.device
         if val is not None:
             val = _f32c(val.reshape(-1), 'edge_attr')
@@ -762,13 +771,20 @@ class GNNML1BlockFunction(torch.autograd.Function):
                 pat = torch.empty(N, npat, dtype=torch.uint8, device=dev) if (act == 1 and record) else None
                 with _Timed('gnnml1_sum_fwd', nbytes, 0):
                     _lib.call('gml_gnnml1_sum_fwd', *head, act, _ptr(out), C, _ptr(pat), npat, _stream(dev))
+            elif mode == 5:
+                npat = (n1 + 15) // 16 * 4
+                pat = torch.empty(N, npat, dtype=torch.uint8, device=dev)
+                with _Timed('gnnml1_actsum_fwd', nbytes + N * npat if PROFILE is not None else 0, 0):
+                    _lib.call('gml_gnnml1_actsum_fwd', *head, act, _ptr(out), C, _ptr(pat), npat, _stream(dev))
+                _path('gnnml1_block', 'fused act_sum (Fin=%d n=%d)' % (Fin, n1))
             else:
                 with _Timed('gnnml1_fwd', nbytes, 0):
                     _lib.call('gml_gnnml1_fwd', *head, mode, act, _ptr(out), C, _stream(dev))
         ctx.csr, ctx.mode, ctx.act, ctx.dims = csr, mode, act, (N, Fin, n1, n2, n3, C)
         ctx.has_b = (b1 is not None, bc is not None, b2 is not None, b3 is not None)
-        # mode 4 recomputes a and c from the biases (or reads the pattern) and never reads `out`; modes 0..3 read `out`
-        ctx.save_for_backward(x, val, w1, wc, w2, b2, w3, b3, *((b1, bc, pat) if mode == 4 else (out,)))
+        # mode 4 recomputes a and c from the biases (or reads the pattern) and never reads `out`; mode 5 reads the pattern; modes 0..3
+        # read `out`
+        ctx.save_for_backward(x, val, w1, wc, w2, b2, w3, b3, *((b1, bc, pat) if mode == 4 else ((pat,) if mode == 5 else (out,))))
         return out
 
     @staticmethod
@@ -779,7 +795,8 @@ class GNNML1BlockFunction(torch.autograd.Function):
         dev = x.device
         gout = _f32rows(gout, 'grad_output')
         L = _lib.lib()
-        sfx, m = ('_sum', ()) if mode == 4 else ('', (mode,))          # the entry points of mode 4 take no mode argument
+        # the entry points of mode 4 take no mode argument; mode 5 writes mode 1's g4: the shared pass runs as mode 1
+        sfx, m = ('_sum', ()) if mode == 4 else ('', (1 if mode == 5 else mode,))
         ng4 = int(getattr(L, 'gml_gnnml1%s_g4_cols' % sfx)(n1, n2, n3, *m))
         p1, p2, p3 = (n1 + 15) // 16 * 16, (n2 + 15) // 16 * 16, (n3 + 15) // 16 * 16
         need_x = ctx.needs_input_grad[0]
@@ -795,13 +812,19 @@ class GNNML1BlockFunction(torch.autograd.Function):
                               _ptr(x), int(x.stride(0)), _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), _ptr(b1), n1, _ptr(wc), _ptr(bc), n2,
                               _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, act, _ptr(pat), p1 // 4, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p1,
                               _stream(dev))
+            elif mode == 5:
+                pat, = rest
+                with _Timed('gnnml1_actsum_bwd', 4 * (N * (Fin + C + (Fin if need_x else 0) + ng4 + p2) + csr.E + N) + N * p1 // 4 if PROFILE is not None else 0, 0):
+                    _lib.call('gml_gnnml1_actsum_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t), _ptr(x), int(x.stride(0)), _ptr(gout),
+                              int(gout.stride(0)), N, Fin, _ptr(w1), n1, _ptr(wc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3, act,
+                              _ptr(pat), p1 // 4, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p2, _stream(dev))
             else:
                 out, = rest
                 with _Timed('gnnml1_bwd', 4 * (N * (Fin + 2 * C + (Fin if need_x else 0) + ng4 + p2) + csr.E + N) if PROFILE is not None else 0, 0):
                     _lib.call('gml_gnnml1_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(val_t), _ptr(x), int(x.stride(0)), _ptr(out), C,
                               _ptr(gout), int(gout.stride(0)), N, Fin, _ptr(w1), n1, _ptr(wc), n2, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), n3,
                               mode, act, _ptr(dx), Fin, _ptr(g4), ng4, _ptr(q), p2, _stream(dev))
-            with _Timed('gnnml1%s_dw' % sfx):
+            with _Timed('gnnml1_actsum_dw' if mode == 5 else 'gnnml1%s_dw' % sfx):
                 nflat = int(getattr(L, 'gml_gnnml1%s_dw_floats' % sfx)(Fin, n1, n2, n3, *m))
                 nws = int(getattr(L, 'gml_gnnml1%s_dw_workspace_bytes' % sfx)(N, Fin, n1, n2, n3, *m))
                 flat = torch.empty(nflat, dtype=torch.float32, device=dev)

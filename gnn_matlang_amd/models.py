@@ -445,14 +445,16 @@ class DSSGCN(torch.nn.Module):
 
 def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
     """the block as one fused launch (functional.GNNML1BlockFunction) or None when the widths are outside the kernel (modes 0..3,
-    csrc/gml_gnnml1.hip: input > 144, a part > 64; mode 4, csrc/gml_gnnml1_sum.hip: input > 192, n1 = n2 > 128, n3 > 64) or the conv
-    is not the plain K = 1 form the scripts use.  Unit edge values (sr25.py:231, mutag.py:253: torch.ones).  No row-count gate in
-    mode 4: the fused road's 90th percentile is below the composition's 10th for both blocks at 1.7 k and at 500 k rows
-    (tools/bench_gnnml1_sum.py, profiles/gnnml1_sum.json, DESIGN s4.15)."""
+    csrc/gml_gnnml1.hip: input > 144, a part > 64; mode 4, csrc/gml_gnnml1_sum.hip: input > 192, n1 = n2 > 128, n3 > 64; mode 5,
+    csrc/gml_gnnml1_act.hip: input > 144, n > 64, or tanh) or the conv is not the plain K = 1 form the scripts use.  Unit edge values
+    (sr25.py:231, mutag.py:253: torch.ones).  No row-count gate in mode 4: the fused road's 90th percentile is below the
+    composition's 10th for both blocks at 1.7 k and at 500 k rows (tools/bench_gnnml1_sum.py, profiles/gnnml1_sum.json, DESIGN s4.15);
+    none in mode 5 for the same reason, at 900 and at 500 k rows (tools/bench_filtering_gnnml1.py, profiles/filtering_gnnml1.json:
+    0.33 against 0.79 - 0.85 ms, 0.46 - 0.62 against 4.92 - 5.06 ms; DESIGN s4.18)."""
     if conv.weight.size(0) != 1 or conv.selfconn or conv.depthwise:
         return None
     Fin, n1, n2, n3 = int(x.size(1)), int(fc1.weight.size(0)), int(conv.weight.size(2)), int(fc2.weight.size(0))
-    if not Fn.gnnml1_block_supported(x, Fin, n1, n2, n3, mode):
+    if not Fn.gnnml1_block_supported(x, Fin, n1, n2, n3, mode, act):
         return None
     return Fn.GNNML1BlockFunction.apply(x, csr, None, fc1.weight, fc1.bias, conv.weight, conv.bias, fc2.weight, fc2.bias,
                                         fc3.weight, fc3.bias, mode, act)
@@ -461,7 +463,7 @@ def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
 class GNNML1Blocks(torch.nn.Module):
     """The GNNML1 of every experiment script (mutag.py:214-266, sr25.py:192-246, graph8c.py:205-246, mnist75.py:262-326,
     exp_classify.py:209-262, Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343,
-    proteins.py:208-257, enzymes_contfeat.py:284-346) as one class: `nblocks` blocks
+    proteins.py:208-257, enzymes_contfeat.py:284-346, filtering.py:200-250, exp_iso.py:195-247) as one class: `nblocks` blocks
          form 'sum'         :  x <- act( fc_i1 x + conv_i1 x + fc_i2 x * fc_i3 x )                          (kernel mode 0, sr25.py:231-240;
                                n1 == n2 == n3, block output n1 wide)
          form 'product'     :  x <- cat[ act(fc_i1 x), act(conv_i1 x), act(fc_i2 x * fc_i3 x) ]              (mode 1)
@@ -469,31 +471,39 @@ class GNNML1Blocks(torch.nn.Module):
          form 'tanh_factors':  x <- cat[ act(fc_i1 x), act(conv_i1 x), tanh(fc_i2 x) * tanh(fc_i3 x) ]      (mode 3, ptc.py:311)
          form 'sum_factors' :  x <- cat[ act(fc_i1 x) + act(conv_i1 x), act(fc_i2 x) * act(fc_i3 x) ]       (mode 4, enzymes_contfeat.py:336;
                                n1 == n2, block output n1 + n3 wide)
+         form 'act_sum'     :  x <- act(fc_i1 x) + act(conv_i1 x) + act(fc_i2 x * fc_i3 x)                  (mode 5, filtering.py:246-248;
+                               n1 == n2 == n3, block output n1 wide; fused for relu, tanh runs on the composition)
     of widths = (n1, n2, n3) (fc_i1 -> n1, conv_i1 = SpectConv(K = 1, selfconn=False) over the raw adjacency with unit edge values
     -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (one fused launch) with the composition as the road of any other shape.
     bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn> are DECLARED (the scripts declare
     some they never call: the reference's checkpoints load with strict=True).  dropout > 0: F.dropout in front of every block in
-    training.  pool: a name or a tuple of names (_pool).  head:
+    training.  pool: a name or a tuple of names (_pool), or None together with head='node' (a node-level model: no pooling).  head:
          'mlp32'      : fc2(relu(fc1 x)), fc1: nin -> 32                       (Zinc12k.py:306-307, freqclass.py, mutag.py:264-266)
          'lin2'       : fc2(fc1 x), fc1: nin -> hidden, NO activation          (counting.py:332-333, exp_classify.py:240-241)
          'lin10'      : fc1 x, fc1: nin -> nclass, no fc2                      (sr25.py, graph8c.py)
          'bn_mlp'     : log_softmax(fc2(relu(fc1(bn1 x)))), fc1: nin -> 32, bn1 a plain torch BatchNorm of the pooled rows
                         (mnist75.py; the name bn1 is the head's: nbn == 0)
          'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)
+         'node'       : fc2 x on every node row, fc2: nin -> nclass, no fc1; needs pool=None        (filtering.py:231, 250)
     Same attribute names as the reference, so its state_dict loads.  A padded static batch hands _node_valid to the bnI in training:
     padding nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only."""
 
-    _MODES = dict(sum=0, product=1, factors=2, tanh_factors=3, sum_factors=4)
-    _HEADS = ('mlp32', 'lin2', 'lin10', 'bn_mlp', 'log_softmax')
+    _MODES = dict(sum=0, product=1, factors=2, tanh_factors=3, sum_factors=4)      # the kernel modes of the first five forms
+    _FORMS = dict(_MODES, act_sum=5)                                               # every form -> its kernel mode
+    _HEADS = ('mlp32', 'lin2', 'lin10', 'bn_mlp', 'log_softmax', 'node')
 
     def __init__(self, ninp, widths, nblocks, form='product', act='relu', bn_after=(), nbn=0, pool='add', head='mlp32', hidden=0,
                  nclass=1, dropout=0.0):
         super().__init__()
         n1, n2, n3 = (int(w) for w in widths)
-        if form not in self._MODES or act not in ('tanh', 'relu') or head not in self._HEADS:
-            raise ValueError('form: %s; act: tanh / relu; head: %s' % (' / '.join(self._MODES), ' / '.join(self._HEADS)))
+        if form not in self._FORMS or act not in ('tanh', 'relu') or head not in self._HEADS:
+            raise ValueError('form: %s; act: tanh / relu; head: %s' % (' / '.join(self._FORMS), ' / '.join(self._HEADS)))
         if form == 'sum' and not n1 == n2 == n3:
             raise ValueError("form='sum' adds fc_i1 x, conv_i1 x and fc_i2 x * fc_i3 x: three equal widths")
+        if form == 'act_sum' and not n1 == n2 == n3:
+            raise ValueError("form='act_sum' adds act(fc_i1 x), act(conv_i1 x) and act(fc_i2 x * fc_i3 x): three equal widths")
+        if (pool is None) != (head == 'node'):
+            raise ValueError("pool=None and head='node' go together: a node-level model has no pooling and reads out every row")
         if form == 'sum_factors' and n1 != n2:
             raise ValueError("form='sum_factors' adds act(fc_i1 x) and act(conv_i1 x): widths[0] == widths[1]")
         if any(not 1 <= int(b) <= min(nblocks, nbn) for b in bn_after):
@@ -504,7 +514,7 @@ class GNNML1Blocks(torch.nn.Module):
             raise ValueError("head='bn_mlp' names its BatchNorm bn1: no block BatchNorms (nbn == 0)")
         self.nblocks, self.form, self.act, self.pool, self.head = int(nblocks), form, act, pool, head
         self.bn_after = frozenset(int(b) for b in bn_after)
-        nin = {'sum': n1, 'sum_factors': n1 + n3}.get(form, n1 + n2 + n3)
+        nin = {'sum': n1, 'act_sum': n1, 'sum_factors': n1 + n3}.get(form, n1 + n2 + n3)
         for i in range(1, nbn + 1):
             setattr(self, 'bn%d' % i, BatchNorm1d(nin))
         for i, fin in enumerate([ninp] + [nin] * (nblocks - 1), start=1):
@@ -520,6 +530,8 @@ class GNNML1Blocks(torch.nn.Module):
                 self.bn1 = torch.nn.BatchNorm1d(nin)
             if head in ('mlp32', 'bn_mlp'):
                 hidden = 32
+            if head == 'node':
+                hidden = 0
             if hidden:
                 self.fc1 = torch.nn.Linear(nin, hidden)
             self.fc2 = torch.nn.Linear(hidden or nin, nclass)
@@ -527,7 +539,7 @@ class GNNML1Blocks(torch.nn.Module):
 
     def _block(self, i, x, csr, ones):
         g = lambda n: getattr(self, n % i)
-        mode, actid = self._MODES[self.form], 0 if self.act == 'tanh' else 1
+        mode, actid = self._FORMS[self.form], 0 if self.act == 'tanh' else 1
         y = _gnnml1_block(x, csr, g('fc%d1'), g('conv%d1'), g('fc%d2'), g('fc%d3'), mode, actid)
         if y is not None:
             return y
@@ -537,10 +549,13 @@ class GNNML1Blocks(torch.nn.Module):
             return A(a + c + f2 * f3)
         if mode == 4:
             return torch.cat([A(a) + A(c), A(f2) * A(f3)], 1)
+        if mode == 5:
+            return A(a) + A(c) + A(f2 * f3)
         h = A(f2 * f3) if mode == 1 else (A(f2) * A(f3) if mode == 2 else torch.tanh(f2) * torch.tanh(f3))
         return torch.cat([A(a), A(c), h], 1)
 
-    def forward(self, data, _features=False):
+    def forward(self, data, _features=False, _road=None):
+        """_road: accepted for models.filtering_step_loss, which hands it to every node-level model; there is one road here"""
         x = data.x
         padded = getattr(data, 'pad_graph', False)
         if self.head == 'bn_mlp' and self.training and padded:
@@ -558,9 +573,12 @@ class GNNML1Blocks(torch.nn.Module):
             if i in self.bn_after:
                 bn = getattr(self, 'bn%d' % i)
                 x = bn(x) if nvalid is None else bn(x, valid=nvalid)
-        x = _pool(self.pool, x, data)
+        if self.pool is not None:
+            x = _pool(self.pool, x, data)
         if _features:
             return x
+        if self.head == 'node':
+            return tall_linear(x, self.fc2)
         if self.head == 'lin10':
             return tall_linear(x, self.fc1)
         if self.head == 'lin2':
@@ -573,7 +591,8 @@ class GNNML1Blocks(torch.nn.Module):
         return x if self.head == 'mlp32' else F.log_softmax(x, dim=1)
 
     def features(self, data, pad_grad_zero=False):
-        """the pooled graph features the head is applied to: [num_graphs, nin] (pad_grad_zero: accepted for symmetry with
+        """the features the head is applied to: the pooled graph rows [num_graphs, nin], with head='node' the node rows [N, nin]
+        (pad_grad_zero: accepted for symmetry with
         GNNML3.features; the pool here masks the padding graph's gradient itself)."""
         return self.forward(data, _features=True)
 
@@ -643,6 +662,14 @@ def mnist75_gnnml1(ninp=3, dropout=0.0):   # mnist75.py:262-326 (relu, mean-pool
     return GNNML1Blocks(ninp, (64, 64, 64), 3, form='sum', act='relu', pool='mean', head='bn_mlp', nclass=10, dropout=dropout)
 
 
+def filtering_gnnml1(ninp=1, concat=False):
+    """filtering.py:200-250, the GNNML1 its model line offers beside GNNML3 (:287): three blocks 32 | 32 | 32 with relu, node-level
+    (no pooling, no fc1, fc2: nin -> 1 on every node).  concat=False, the script's setting: the sum of the three activated parts
+    (form 'act_sum', nin = 32); concat=True: their concatenation (form 'product', nin = 96; :241-243).  Loss and R^2:
+    filtering_step_loss / r2_from_stats, as for filtering_gnnml3."""
+    return GNNML1Blocks(ninp, (32, 32, 32), 3, form='product' if concat else 'act_sum', act='relu', pool=None, head='node', nclass=1)
+
+
 def filtering_gnnml3(ninp=1, ne=11):      # filtering.py:252-280 (node-level: three layers 32 + 16, fc2: 48 -> 1, no pooling, no fc1)
     return GNNML3(ninp, ne, 32, 16, 3, learnedge=False, pool=None, head='node', nclass=1)
 
@@ -661,6 +688,10 @@ def sr25_gnnml3(ninp=2, ne=6):             # sr25.py:252-262
 
 def graph8c_gnnml3(ninp=2, ne=6):          # graph8c.py:252-278 (the sr25 shapes: 32 + 16 outputs, 3 layers, add-pool, tanh(fc1) -> 10)
     return GNNML3(ninp, ne, 32, 16, 3, head='tanh10')
+
+
+def exp_gnnml1(ninp=2):                    # exp_iso.py:195-247 (sr25's shapes: nout = 64, sum form, tanh, add-pool, fc1 -> 10)
+    return GNNML1Blocks(ninp, (64, 64, 64), 3, form='sum', act='tanh', pool='add', head='lin10', nclass=10)
 
 
 def exp_gnnml3(ninp=2, ne=6):              # exp_iso.py:249-278 (the same shapes; ne = 6 supports of SpectralDesign(nfreq=5))

@@ -945,6 +945,31 @@ int gml_gnnml1_sum_dw(const float* x, int64_t ldx, const float* g4, int64_t ldg4
                       int32_t Fin, int32_t n1, int32_t n2, int32_t n3, float* out_flat, void* ws, size_t ws_bytes,
                       gml_stream_t stream);
 
+/* GNNML1 block as the sum of three activated parts (block mode 5; csrc/gml_gnnml1_act.hip) -- filtering.py:246-248 (concat = False):
+ *   out [N, n] = act(a) + act(c) + act(f2 * f3),   a, c, f2, f3 and the arguments as for gml_gnnml1_fwd,  n1 == n2 == n3 == n.
+ * One launch forward, the kernel of gml_gnnml1_fwd with another epilogue: exact fp32 products, aggregation in edge order, no atomics.
+ * act = 1 (relu), Fin <= 144, n <= 64 (gml_gnnml1_actsum_supported), else GML_E_UNSUPPORTED -- act = 0 (tanh) included: it needs the
+ * values of a and c in the backward, no script uses it in this form, and the caller composes it; unequal widths or an act outside
+ * 0 / 1: GML_E_BADARG.  Nothing is launched on any error.  Rows of any stride.
+ * pattern ([N, ldp >= 4 ceil(n / 16)] bytes; optional in the forward): where a and c are positive -- byte j of a row: bit u = a > 0,
+ * bit 4 + u = c > 0 of column 4 j + u (the layout of gml_gnnml1_sum_fwd) -- because the sum does not tell the relu patterns apart.
+ * Backward (source-keyed view rowptr_t / col_t / val_t; pattern required, NULL: GML_E_BADARG; no forward output is read):
+ *   g4 [N, ldg4 >= gml_gnnml1_g4_cols(n, n, n, 1)] = [da | dc | df2 | df3],  da = g [a > 0], dc = g [c > 0],
+ *                                                     df2 = g [f2 f3 > 0] f3, df3 = g [f2 f3 > 0] f2  (f2, f3 recomputed; relu'(0) = 0)
+ *   q  [N, ldq >= 16 ceil(n / 16)] = A dc;      dx (optional) = da W1 + q Wc^T + df2 W2 + df3 W3
+ * ldg4 and ldq multiples of 4; padding columns of g4 are zeros.  g4 is mode 1's layout: the weight and bias gradients come from
+ * gml_gnnml1_dw(..., mode = 1) (workspace: gml_gnnml1_dw_workspace_bytes(..., mode = 1)). */
+int gml_gnnml1_actsum_supported(int32_t Fin, int32_t n1, int32_t n2, int32_t n3, int32_t act);
+int gml_gnnml1_actsum_fwd(const int32_t* rowptr, const int32_t* col, const float* val, const float* x, int64_t ldx, int64_t num_rows,
+                          int32_t Fin, const float* w1, const float* b1, int32_t n1, const float* wc, const float* bc, int32_t n2,
+                          const float* w2, const float* b2, const float* w3, const float* b3, int32_t n3, int32_t act,
+                          float* out, int64_t ldo, uint8_t* pattern, int64_t ldp, gml_stream_t stream);
+int gml_gnnml1_actsum_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const float* x, int64_t ldx,
+                          const float* gout, int64_t ldgo, int64_t num_rows, int32_t Fin, const float* w1, int32_t n1,
+                          const float* wc, int32_t n2, const float* w2, const float* b2, const float* w3, const float* b3,
+                          int32_t n3, int32_t act, const uint8_t* pattern, int64_t ldp, float* dx, int64_t lddx,
+                          float* g4, int64_t ldg4, float* q, int64_t ldq, gml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
