@@ -118,13 +118,18 @@ __global__ __launch_bounds__(256) void gml_k_bn_bwd_apply(const float* __restric
 }
 
 static bool bn_shape_ok(const void* p, int64_t ld, int32_t C) { return C > 0 && C <= 64 && C % 4 == 0 && ld % 4 == 0 && ld >= C && (((uintptr_t)p) & 15) == 0; }
+// the per-column vectors a kernel reads as f32x4 (mean, rstd, weight, bias, sum_dy, sum_dyxhat) and the workspace, whose partials are
+// stored as f32x4: 16-byte aligned (NULL passes: an optional operand, or answered by the caller's own NULL check)
+static bool bn_al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e)) & 15) == 0;
+}
 
 extern "C" size_t gml_bn_workspace_bytes(int64_t num_rows) { return num_rows <= 0 ? 0 : (size_t)gml_cdiv(num_rows, GML_BN_ROWS) * 2 * 64 * sizeof(float); }
 
 extern "C" int gml_bn_stats(const float* x, int64_t ldx, int64_t num_rows, int32_t C, float eps, float* mean, float* var, float* rstd,
                             void* ws, size_t ws_bytes, gml_stream_t stream) {
     if (num_rows <= 0 || !x || !mean || !var || !rstd) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_al16(ws)) return GML_E_UNSUPPORTED;
     if (!ws || ws_bytes < gml_bn_workspace_bytes(num_rows)) return GML_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (int)gml_cdiv(num_rows, GML_BN_ROWS);
@@ -137,7 +142,7 @@ extern "C" int gml_bn_stats(const float* x, int64_t ldx, int64_t num_rows, int32
 extern "C" int gml_bn_apply(const float* x, int64_t ldx, int64_t num_rows, int32_t C, const float* mean, const float* rstd, const float* weight,
                             const float* bias, float* y, int64_t ldy, gml_stream_t stream) {
     if (num_rows <= 0 || !x || !mean || !rstd || !y) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(y, ldy, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(y, ldy, C) || !bn_al16(mean, rstd, weight, bias)) return GML_E_UNSUPPORTED;
     hipLaunchKernelGGL(gml_k_bn_apply, dim3((unsigned)gml_cdiv(num_rows * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, num_rows,
                        (int)C, mean, rstd, weight, bias, y, ldy);
     return gml_launch_status();
@@ -146,7 +151,7 @@ extern "C" int gml_bn_apply(const float* x, int64_t ldx, int64_t num_rows, int32
 extern "C" int gml_bn_bwd_sums(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t num_rows, int32_t C, const float* mean,
                                const float* rstd, float* sum_dy, float* sum_dyxhat, void* ws, size_t ws_bytes, gml_stream_t stream) {
     if (num_rows <= 0 || !dy || !x || !mean || !rstd || !sum_dy || !sum_dyxhat) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C) || !bn_al16(mean, rstd, ws)) return GML_E_UNSUPPORTED;
     if (!ws || ws_bytes < gml_bn_workspace_bytes(num_rows)) return GML_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (int)gml_cdiv(num_rows, GML_BN_ROWS);
@@ -160,7 +165,8 @@ extern "C" int gml_bn_bwd_apply(const float* dy, int64_t lddy, const float* x, i
                                 const float* rstd, const float* weight, const float* sum_dy, const float* sum_dyxhat, float* dx, int64_t lddx,
                                 gml_stream_t stream) {
     if (num_rows <= 0 || !dy || !x || !mean || !rstd || !sum_dy || !sum_dyxhat || !dx) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C) || !bn_shape_ok(dx, lddx, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C) || !bn_shape_ok(dx, lddx, C) || !bn_al16(mean, rstd, weight, sum_dy, sum_dyxhat))
+        return GML_E_UNSUPPORTED;
     hipLaunchKernelGGL(gml_k_bn_bwd_apply, dim3((unsigned)gml_cdiv(num_rows * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, dy, lddy, x, ldx,
                        num_rows, (int)C, mean, rstd, weight, sum_dy, sum_dyxhat, dx, lddx);
     return gml_launch_status();
@@ -321,7 +327,7 @@ extern "C" size_t gml_bn_masked_workspace_bytes(int64_t num_rows) {
 extern "C" int gml_bn_masked_stats(const float* x, int64_t ldx, const float* row_valid, int64_t num_rows, int32_t C, float eps, float* mean,
                                    float* var, float* rstd, float* count, void* ws, size_t ws_bytes, gml_stream_t stream) {
     if (num_rows <= 0 || !x || !row_valid || !mean || !var || !rstd || !count) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_al16(ws)) return GML_E_UNSUPPORTED;
     if (!ws || ws_bytes < gml_bn_masked_workspace_bytes(num_rows)) return GML_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (int)gml_cdiv(num_rows, GML_BN_ROWS);
@@ -337,7 +343,7 @@ extern "C" int gml_bn_masked_stats(const float* x, int64_t ldx, const float* row
 extern "C" int gml_bn_masked_apply(const float* x, int64_t ldx, const float* row_valid, int64_t num_rows, int32_t C, const float* mean,
                                    const float* rstd, const float* weight, const float* bias, float* y, int64_t ldy, gml_stream_t stream) {
     if (num_rows <= 0 || !x || !row_valid || !mean || !rstd || !y) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(y, ldy, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(y, ldy, C) || !bn_al16(mean, rstd, weight, bias)) return GML_E_UNSUPPORTED;
     hipLaunchKernelGGL(gml_k_bn_apply_masked, dim3((unsigned)gml_cdiv(num_rows * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, ldx,
                        row_valid, num_rows, (int)C, mean, rstd, weight, bias, y, ldy);
     return gml_launch_status();
@@ -347,7 +353,7 @@ extern "C" int gml_bn_masked_bwd_sums(const float* dy, int64_t lddy, const float
                                       int32_t C, const float* mean, const float* rstd, float* sum_dy, float* sum_dyxhat, void* ws,
                                       size_t ws_bytes, gml_stream_t stream) {
     if (num_rows <= 0 || !dy || !x || !row_valid || !mean || !rstd || !sum_dy || !sum_dyxhat) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C) || !bn_al16(mean, rstd, ws)) return GML_E_UNSUPPORTED;
     if (!ws || ws_bytes < gml_bn_masked_workspace_bytes(num_rows)) return GML_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (int)gml_cdiv(num_rows, GML_BN_ROWS);
@@ -362,7 +368,8 @@ extern "C" int gml_bn_masked_bwd_apply(const float* dy, int64_t lddy, const floa
                                        int32_t C, const float* mean, const float* rstd, const float* weight, const float* sum_dy,
                                        const float* sum_dyxhat, const float* count, float* dx, int64_t lddx, gml_stream_t stream) {
     if (num_rows <= 0 || !dy || !x || !row_valid || !mean || !rstd || !sum_dy || !sum_dyxhat || !count || !dx) return GML_E_BADARG;
-    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C) || !bn_shape_ok(dx, lddx, C)) return GML_E_UNSUPPORTED;
+    if (!bn_shape_ok(x, ldx, C) || !bn_shape_ok(dy, lddy, C) || !bn_shape_ok(dx, lddx, C) || !bn_al16(mean, rstd, weight, sum_dy, sum_dyxhat))
+        return GML_E_UNSUPPORTED;
     hipLaunchKernelGGL(gml_k_bn_bwd_apply_masked, dim3((unsigned)gml_cdiv(num_rows * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, dy, lddy,
                        x, ldx, row_valid, num_rows, (int)C, mean, rstd, weight, sum_dy, sum_dyxhat, count, dx, lddx);
     return gml_launch_status();

@@ -766,7 +766,11 @@ int gml_spectral_design(const int32_t* node_ptr, const int32_t* edge_ptr, const 
 /* torch.nn.BatchNorm1d in training mode over the rows of x [num_rows, C] (mutag.py:272-288: one between every two layers): batch
  * statistics (mean, BIASED variance, rstd = 1 / sqrt(var + eps)), y = (x - mean) rstd weight + bias, and the backward: sum_dy = d bias,
  * sum_dyxhat = d weight, dx = (dy - sum_dy / n - xhat sum_dyxhat / n) rstd weight.  C <= 64, C % 4 == 0, float4-addressable rows; other
- * shapes: GML_E_UNSUPPORTED.  weight / bias may be NULL (affine=False).  ws: gml_bn_workspace_bytes(num_rows). */
+ * shapes: GML_E_UNSUPPORTED.  weight / bias may be NULL (affine=False).  ws: gml_bn_workspace_bytes(num_rows).
+ * Alignment: x, y, dy, dx AND every per-column vector a launch READS -- mean, rstd, weight, bias, sum_dy, sum_dyxhat -- AND ws are
+ * accessed as 16-byte vectors and must be 16-byte aligned (a leading dimension that is a multiple of 4 keeps every row so), else
+ * GML_E_UNSUPPORTED, checked on the host before anything is launched.  The vectors a launch WRITES (mean, var, rstd of _stats, sum_dy,
+ * sum_dyxhat of _bwd_sums, count) need float alignment only.  The same holds for the masked entry points below. */
 size_t gml_bn_workspace_bytes(int64_t num_rows);
 int gml_bn_stats(const float* x, int64_t ldx, int64_t num_rows, int32_t C, float eps, float* mean, float* var, float* rstd,
                  void* ws, size_t ws_bytes, gml_stream_t stream);
@@ -815,7 +819,10 @@ int gml_xty_wide(const float* A, int64_t lda, const float* B, int64_t ldb, float
 /* Readout head + L1-sum loss of the ZINC GNNML3 in one launch each way (Zinc12k.py:343-345, :365) for the reference's regime, a
  * batch of 64 graphs, where head, loss and their backward were ~20 of the step's 70 launches (csrc/gml_head.hip):
  *   loss[0] = sum_{r < rows_loss} valid[r] |w2 . relu(W1 p[r] + b1) + b2 - y[r]|     p [rows, nin] pooled features, W1 [nh, nin]
- * rows >= rows_loss (the padding graph of a static batch) enter neither the loss nor any gradient.  pre (optional): logits of all
+ * rows >= rows_loss (the padding graph of a static batch) enter neither the loss nor any gradient.  `valid` is a WEIGHT, and the rows
+ * >= rows_loss are left out by a zero factor: those rows of p ARE read (and their logits written to pre), so a non-finite value in
+ * them is the caller's error -- unlike masked BatchNorm's invalid rows, which are never used.  This holds for all three heads
+ * (gml_head_l1_*, gml_head_l1_big_*, gml_head_bce_*).  pre (optional): logits of all
  * rows.  The backward recomputes from p and scales by gscale[0] (device scalar, NULL = 1): gp [rows, nin], dw1 [nh, nin], db1 [nh]
  * (NULL allowed), dw2 [nh], db2 [1] (NULL allowed).  One workgroup: rows <= 256, nin, nh <= 64 and everything in LDS, else
  * GML_E_UNSUPPORTED (large batches run the general path: library GEMMs + gml_xty). */
