@@ -1965,3 +1965,119 @@ class ML3LayerFunction(torch.autograd.Function):
             else:
                 g[1] = dea if need[1] else None
         return tuple(g)
+
+
+# ---------------------------------------------------------------------------- PPGN block (csrc/gml_ppgn.hip)
+PPGN_READOUTS = {'sum': 0, 'mean': 1, 'diag': 2}
+
+
+def ppgn_block_supported(x, nmax, Cin, C):
+    """the fused block (PPGNBlockFunction) serves this input: float32 [B, Cin, nmax, nmax] on the device with nmax <= 64, Cin <= 64
+    and C <= 64 (gml_ppgn_supported); any mix of node counts 1 <= n_g <= nmax.  A non-contiguous view is served through a contiguous
+    copy.  No shape class inside the range is gated onto the composition: one block forward + backward, fused 90th percentile against
+    the composition's 10th, ms (tools/bench_ppgn.py, profiles/ppgn.json, DESIGN s4.19): inner blocks (with dx) sr25 (15 graphs, n = 25) 0.37 against 0.90,
+    graph8c (11,117 graphs, n = 8) 2.02 against 12.53, EXP (1,200 graphs, nmax = 64) 6.56 against 10.10 (its first block, 3 -> 20
+    without dx: 5.05 against 7.57, the closest class), a ZINC-like batch of 64 at nmax = 37 0.37 against 0.82."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or _os.environ.get('GML_NO_PPGN_FUSED'):
+        return False
+    if int(x.size(1)) != int(Cin) or int(x.size(2)) != int(nmax) or int(x.size(3)) != int(nmax) or x.size(0) < 1:
+        return False
+    return bool(_lib.lib().gml_ppgn_supported(int(nmax), int(Cin), int(C)))
+
+
+def ppgn_block_torch(x, n, w1, b1, w2, b2, w3, b3, readout='sum'):
+    """The block composed from torch ops (the road of every shape outside ppgn_block_supported; about ten launches forward):
+    returns (y, r) like PPGNBlockFunction.  w*: [C, Cin] or Conv2d's [C, Cin, 1, 1]."""
+    nmax = x.size(-1)
+    ar = torch.arange(nmax, device=x.device)
+    inside = ar.view(1, -1) < n.view(-1, 1)                                        # [B, nmax]
+    m = (inside.unsqueeze(2) & inside.unsqueeze(1)).to(x.dtype).unsqueeze(1)       # [B, 1, nmax, nmax]
+    conv = lambda t, w, b: torch.nn.functional.conv2d(t, w.reshape(w.size(0), w.size(1), 1, 1), b)
+    a1 = torch.relu(conv(x, w1, b1) * m)
+    a2 = torch.relu(conv(x, w2, b2) * m)
+    p = torch.matmul(a1, a2) * m
+    y = torch.relu(conv(torch.cat([p, x], 1), w3, b3) * m)
+    eye = torch.eye(nmax, dtype=x.dtype, device=x.device)
+    m0, m1 = m * eye, m * (1 - eye)
+    r0, r1 = (y * m0).sum((2, 3)), (y * m1).sum((2, 3))
+    if readout == 'diag':
+        return y, r0
+    if readout == 'mean':
+        return y, torch.cat([r0 / m0.sum((2, 3)), r1 / m1.sum((2, 3))], 1)
+    if readout != 'sum':
+        raise ValueError("readout: 'sum', 'mean' or 'diag'")
+    return y, torch.cat([r0, r1], 1)
+
+
+class PPGNBlockFunction(torch.autograd.Function):
+    """One PPGN block (sr25.py:48-52) on x [B, Cin, nmax, nmax] with node counts n [B] (int32), mask m = [i < n_g and j < n_g]:
+        a1 = relu(m (W1 x + b1)),  a2 = relu(m (W2 x + b2)),  p_c = a1_c @ a2_c,  y = relu(m (W3 [p ; x] + b3))
+    returns (y, r): y [B, C, nmax, nmax], exactly 0 in the padding whatever x holds there, and the layer readout r out of the kernel
+    that writes y, r0_c = sum_i y_c[i, i], r1_c = sum_{i != j} y_c[i, j]:
+        'sum' : [r0 | r1] [B, 2C]  (sr25.py:52 sums rows, then columns: the same quantity)
+        'mean': [r0 / n | r1 / (n^2 - n)]  (exp_classify.py:60; at n = 1 the off-diagonal half is 0 / 0 = nan: the reference's
+                arithmetic, kept)
+        'diag': r0 [B, C]  (mutag.py:52)
+    Forward: three launches; backward: four, plus one for dx when x needs a gradient (the first block's input is data).  w1, w2
+    [C, Cin], w3 [C, C + Cin] (or Conv2d's 4-d weights), biases optional.  fp32 products and fp32 accumulation only, no bf16 pieces:
+    exact_products() changes nothing here.  Weight and bias gradients: per-workgroup partials, one ordered fold, no atomics --
+    bit-reproducible.  No host synchronisation: n is read on the device, forward + backward capture in a graph."""
+
+    @staticmethod
+    def forward(ctx, x, n, w1, b1, w2, b2, w3, b3, readout='sum'):
+        x = _f32c(x, 'x')
+        if x.dim() != 4 or x.size(2) != x.size(3):
+            raise ValueError('PPGN block: x must be [B, Cin, nmax, nmax], got %s' % (list(x.shape),))
+        B, Cin, nmax = int(x.size(0)), int(x.size(1)), int(x.size(2))
+        C = int(w1.size(0))
+        mode = PPGN_READOUTS[readout]
+        _require_cuda(n, 'n')
+        if n.dtype != torch.int32 or n.numel() != B:
+            raise TypeError('PPGN block: n must be int32 [B]')
+        n = n.contiguous()
+        ctx.wshapes = (w1.shape, w2.shape, w3.shape)
+        w1, w2, w3 = _f32c(w1.reshape(C, -1), 'w1'), _f32c(w2.reshape(C, -1), 'w2'), _f32c(w3.reshape(C, -1), 'w3')
+        if w1.size(1) != Cin or tuple(w2.shape) != (C, Cin) or tuple(w3.shape) != (C, C + Cin):
+            raise ValueError('PPGN block: weights [C, Cin], [C, Cin], [C, C + Cin] expected')
+        b1, b2, b3 = (None if b is None else _f32c(b, 'bias') for b in (b1, b2, b3))
+        dev = x.device
+        with torch.cuda.device(dev):
+            a12 = torch.empty(B, 2 * C, nmax, nmax, dtype=torch.float32, device=dev)
+            p = torch.empty(B, C, nmax, nmax, dtype=torch.float32, device=dev)
+            y = torch.empty(B, C, nmax, nmax, dtype=torch.float32, device=dev)
+            r = torch.empty(B, C if mode == 2 else 2 * C, dtype=torch.float32, device=dev)
+            with _Timed('ppgn_fwd'):
+                _lib.call('gml_ppgn_fwd', _ptr(x), _ptr(n), B, nmax, Cin, C, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3),
+                          mode, _ptr(a12), _ptr(p), _ptr(y), _ptr(r), _stream(dev))
+        ctx.dims, ctx.mode = (B, Cin, nmax, C), mode
+        ctx.has_b = (b1 is not None, b2 is not None, b3 is not None)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, n, w1, w2, w3, a12, p, y)
+        return y, r
+
+    @staticmethod
+    def backward(ctx, dy, dr):
+        x, n, w1, w2, w3, a12, p, y = ctx.saved_tensors
+        B, Cin, nmax, C = ctx.dims
+        dev = x.device
+        if dy is None and dr is None:
+            return (None,) * 9
+        dy = None if dy is None else _f32c(dy, 'grad of y')
+        dr = None if dr is None else _f32c(dr, 'grad of the readout')
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            flat = torch.empty(int(L.gml_ppgn_dw_floats(Cin, C)), dtype=torch.float32, device=dev)
+            nws = int(L.gml_ppgn_bwd_workspace_bytes(B, nmax, Cin, C))
+            ws = torch.empty(max(nws // 4, 1), dtype=torch.float32, device=dev)
+            with _Timed('ppgn_bwd'):
+                _lib.call('gml_ppgn_bwd', _ptr(x), _ptr(n), B, nmax, Cin, C, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(a12), _ptr(p), _ptr(y),
+                          _ptr(dy), _ptr(dr), ctx.mode, _ptr(dx), _ptr(flat), _ptr(ws), ws.numel() * 4, _stream(dev))
+        n3, n12 = C + Cin + 1, Cin + 1
+        d3 = flat[:C * n3].view(C, n3)
+        d12 = flat[C * n3:].view(2 * C, n12)
+        hb1, hb2, hb3 = ctx.has_b
+        s1, s2, s3 = ctx.wshapes                                     # (Conv2d's [C, Cin, 1, 1] get their gradient in that shape)
+        dw1, dw2, dw3 = d12[:C, :Cin].reshape(s1), d12[C:, :Cin].reshape(s2), d3[:, :C + Cin].reshape(s3)
+        return (dx, None, dw1, d12[:C, Cin] if hb1 else None, dw2, d12[C:, Cin] if hb2 else None, dw3, d3[:, C + Cin] if hb3 else None,
+                None)

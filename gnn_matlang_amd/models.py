@@ -735,6 +735,87 @@ def enzymes_contfeat_gnnml3(ninp=22, ne=4, dropout=0.1):  # enzymes_contfeats_gn
     return DSSGCN(ninp, ne, widths=(200, 200), pool=('mean', 'max'), dense=(100,), nclass=6, dropout=dropout)
 
 
+class PPGN(torch.nn.Module):
+    """The PPGN baseline of the experiment scripts (Maron et al.; sr25.py:20-72, exp_iso.py:22-74, exp_classify.py:24-83,
+    Zinc12k.py:25-95, counting.py:35-122, mutag.py:18-72) as one class: `nblocks` blocks on the dense tensors of ppgn.ppgn_inputs,
+        x1 = relu(m mlp{b}_1 x),  x2 = relu(m mlp{b}_2 x),  x <- relu(m mlp{b}_3 [x1 @ x2 ; x])     (1 x 1 convolutions, m: the n x n mask)
+    each through functional.PPGNBlockFunction (three launches forward, readout included) where functional.ppgn_block_supported says so
+    (nmax <= 64, widths <= 64), else through the torch-op composition functional.ppgn_block_torch.  The readouts of all blocks
+    ('sum': [diagonal sums | off-diagonal sums], 'mean': the two divided by n and n^2 - n -- at n = 1 the reference divides 0 by 0
+    and so does this, 'diag': the diagonal sums only) are concatenated and go through h1 (hidden wide; head_act 'tanh', 'relu' or
+    None) and, with nout, h2.  Parameters are torch.nn.Conv2d(., ., 1) modules mlp{b}_1, mlp{b}_2, mlp{b}_3 and Linear h1 (h2), created
+    in the reference's order: its state_dict loads with strict=True and torch.manual_seed(s) gives its weights.  forward(data) reads
+    data.X2 [B, ninp, nmax, nmax] and data.ppgn_n [B] (ppgn.attach); nmax is informative (the tensors carry it).  Device only."""
+
+    def __init__(self, ninp, nneuron=32, nblocks=3, bias=True, readout='sum', hidden=10, head_act='tanh', nout=None, nmax=0):
+        super().__init__()
+        if readout not in Fn.PPGN_READOUTS or head_act not in ('tanh', 'relu', None):
+            raise ValueError("readout: 'sum' / 'mean' / 'diag'; head_act: 'tanh' / 'relu' / None")
+        self.nmax, self.nneuron, self.nblocks, self.readout, self.head_act = int(nmax), int(nneuron), int(nblocks), readout, head_act
+        cin = int(ninp)
+        for b in range(1, self.nblocks + 1):
+            setattr(self, 'mlp%d_1' % b, torch.nn.Conv2d(cin, nneuron, 1, bias=bias))
+            setattr(self, 'mlp%d_2' % b, torch.nn.Conv2d(cin, nneuron, 1, bias=bias))
+            setattr(self, 'mlp%d_3' % b, torch.nn.Conv2d(nneuron + cin, nneuron, 1, bias=bias))
+            cin = int(nneuron)
+        self.h1 = torch.nn.Linear((1 if readout == 'diag' else 2) * self.nblocks * nneuron, hidden)
+        if nout:
+            self.h2 = torch.nn.Linear(hidden, nout)
+
+    def forward(self, data, _features=False, _road=None):
+        """_features: the concatenated block readouts (what h1 is applied to); _road: 'torch' forces the composition"""
+        x, n = data.X2, data.ppgn_n
+        Fn._require_cuda(x, 'data.X2')
+        Fn._require_cuda(n, 'data.ppgn_n')
+        outs = []
+        for b in range(1, self.nblocks + 1):
+            m1, m2, m3 = (getattr(self, 'mlp%d_%d' % (b, k)) for k in (1, 2, 3))
+            C = int(m1.weight.size(0))
+            if _road != 'torch' and Fn.ppgn_block_supported(x, x.size(-1), x.size(1), C):
+                x, r = Fn.PPGNBlockFunction.apply(x, n, m1.weight, m1.bias, m2.weight, m2.bias, m3.weight, m3.bias, self.readout)
+            else:
+                x, r = Fn.ppgn_block_torch(x, n, m1.weight, m1.bias, m2.weight, m2.bias, m3.weight, m3.bias, self.readout)
+            outs.append(r)
+        x = torch.cat(outs, 1)
+        if _features:
+            return x
+        x = tall_linear(x, self.h1)
+        if self.head_act is not None:
+            x = torch.tanh(x) if self.head_act == 'tanh' else F.relu(x)
+        return tall_linear(x, self.h2) if hasattr(self, 'h2') else x
+
+    def features(self, data):
+        return self.forward(data, _features=True)
+
+
+def sr25_ppgn(ninp=3):                     # sr25.py:20-72 (nmax 25; three blocks of 32 with biases, sum readout, tanh(h1: 192 -> 10))
+    return PPGN(ninp, 32, 3, bias=True, readout='sum', hidden=10, head_act='tanh', nmax=25)
+
+
+def graph8c_ppgn(ninp=3):                  # graph8c.py (the sr25 shapes at nmax 8)
+    return PPGN(ninp, 32, 3, bias=True, readout='sum', hidden=10, head_act='tanh', nmax=8)
+
+
+def exp_ppgn(ninp=3):                      # exp_iso.py:22-74 (nmax 64; three bias-free blocks of 20, sum readout, tanh(h1: 120 -> 10))
+    return PPGN(ninp, 20, 3, bias=False, readout='sum', hidden=10, head_act='tanh', nmax=64)
+
+
+def exp_classify_ppgn(ninp=3):             # exp_classify.py:24-83 (nmax 64; three bias-free blocks of 20, mean readout, relu(h1: 120 -> 10), h2: 10 -> 1)
+    return PPGN(ninp, 20, 3, bias=False, readout='mean', hidden=10, head_act='relu', nout=1, nmax=64)
+
+
+def zinc_ppgn(ninp=23):                    # Zinc12k.py:25-95 (nmax 37; four bias-free blocks of 32, sum readout, relu(h1: 256 -> 64), h2: 64 -> 1)
+    return PPGN(ninp, 32, 4, bias=False, readout='sum', hidden=64, head_act='relu', nout=1, nmax=37)
+
+
+def counting_ppgn(ninp=3):                 # counting.py:35-122 (nmax 30; five bias-free blocks of 40, sum readout, relu(h1: 400 -> 64), h2: 64 -> 1)
+    return PPGN(ninp, 40, 5, bias=False, readout='sum', hidden=64, head_act='relu', nout=1, nmax=30)
+
+
+def mutag_ppgn(ninp=9):                    # mutag.py:18-72 (nmax 28; three blocks of 32 with biases, diagonal readout, relu(h1: 96 -> 32), h2: 32 -> 1)
+    return PPGN(ninp, 32, 3, bias=True, readout='diag', hidden=32, head_act='relu', nout=1, nmax=28)
+
+
 def zinc_loss(pre, y):                     # Zinc12k.py:365
     return F.l1_loss(pre, y.unsqueeze(-1), reduction='sum')
 

@@ -9,7 +9,8 @@ identical to the reference so results agree to the last bits LAPACK gives:
   A, SP float32;  d, 1/sqrt(d), (A D)^T D float32;  nL, eigh(nL), Gaussian filters float64;
   eigh(A) float32 when laplacien=False;  M = (A+I) squared recfield-1 times (:566-573, i.e. a
   2^(recfield-1)-hop mask);  COO emitted in row-major order (:608-610).
-The PPGN baseline tensors (X2, M; :613-624) are not produced: ``nmax`` is accepted and ignored.
+The PPGN baseline tensors (X2, M; :613-624) are built on the device by ``ppgn.ppgn_inputs`` for a whole batch, not here:
+``nmax`` is accepted and unused.
 The GPU port of this step is the first "next" row.
 """
 import numpy as np

@@ -977,6 +977,43 @@ int gml_gnnml1_actsum_bwd(const int32_t* rowptr_t, const int32_t* col_t, const f
                           int32_t n3, int32_t act, const uint8_t* pattern, int64_t ldp, float* dx, int64_t lddx,
                           float* g4, int64_t ldg4, float* q, int64_t ldq, gml_stream_t stream);
 
+/* PPGN (the 3-WL baseline of every experiment script, e.g. sr25.py:20-72) on dense channel-major tensors [B, C, nmax, nmax]
+ * (csrc/gml_ppgn.hip).  n [B] int32: the node counts; pixel (i, j) of graph g is real where i < n_g and j < n_g (mask m).
+ *
+ * gml_ppgn_inputs: the tensors of libs/utils.py:613-624 for a batch, one launch, no host read.  X2 [B, nfeat + 2, nmax, nmax] and
+ * M [B, 2, nmax, nmax] must arrive ZERO FILLED; the kernel sets X2 channel 0 = adjacency (edge (s, d) -> pixel (s, d) of the graph of
+ * s), channel 1 = identity on the first n_g diagonal entries, channel 2 + f = diag(x[:, f]) for f < nfeat <= ldx; M channel 0 = the
+ * diagonal mask, channel 1 = the off-diagonal mask inside n_g x n_g; n [B] = ptr[g + 1] - ptr[g].  A graph with n_g > nmax gets no
+ * pixel at all (its n is still written: the caller's check).  edge_src / edge_dst: global node ids (int64), batch [N]: graph of a node.
+ *
+ * gml_ppgn_fwd: one block,
+ *   a1 = relu(m (W1 x + b1)),  a2 = relu(m (W2 x + b2)),  p_c = a1_c @ a2_c per channel,  y = relu(m (W3 [p ; x] + b3))
+ *   W1, W2 [C, Cin], W3 [C, C + Cin] row-major (first C columns on p), biases optional (NULL).  Three launches.
+ *   a12 [B, 2C, nmax, nmax] (a1 then a2) and p [B, C, nmax, nmax] are written on the real pixels only (the backward's inputs; the
+ *   padding is never read), y [B, C, nmax, nmax] everywhere (exactly 0 in the padding, whatever x holds there).
+ *   r: the layer readout out of the kernel that writes y.  r0_c = sum_i y_c[i, i], r1_c = sum_{i != j} y_c[i, j];
+ *   readout 0 ('sum'): r [B, 2C] = [r0 | r1];  1 ('mean'): [r0 / n | r1 / (n^2 - n)] (n = 1: 0 / 0, the reference's arithmetic);
+ *   2 ('diag'): r [B, C] = r0.
+ * gml_ppgn_bwd: dy [B, C, nmax, nmax] and / or dr (shape of r); either may be NULL, not both.  Four launches + one for dx (optional,
+ *   [B, Cin, nmax, nmax], exactly 0 in the padding).  Relu patterns from y > 0 and a > 0.  Weight and bias gradients: per-workgroup
+ *   partials over 32-pixel chunks on the f32-input matrix instruction, then one fold in ascending workgroup order (no atomics:
+ *   bit-reproducible).  dflat [gml_ppgn_dw_floats] = [D3 (C x (C + Cin + 1)) | D12 (2C x (Cin + 1))] row-major:
+ *   D3 = [dW3 | db3], D12 = [dW1 | db1 ; dW2 | db2] (the bias column is computed with or without biases).
+ * Range: 1 <= nmax <= 64, 1 <= Cin, C <= 64 (gml_ppgn_supported), else GML_E_UNSUPPORTED; nothing is launched on any error.
+ * Exact fp32 products and sums throughout.  No host synchronisation: capturable on one stream. */
+int gml_ppgn_supported(int32_t nmax, int32_t Cin, int32_t C);
+int gml_ppgn_inputs(const float* x, int64_t ldx, int32_t nfeat, const int64_t* edge_src, const int64_t* edge_dst, int64_t E,
+                    const int32_t* ptr, const int64_t* batch, int64_t N, int64_t B, int32_t nmax, float* X2, float* M, int32_t* n,
+                    gml_stream_t stream);
+int gml_ppgn_fwd(const float* x, const int32_t* n, int64_t B, int32_t nmax, int32_t Cin, int32_t C, const float* w1, const float* b1,
+                 const float* w2, const float* b2, const float* w3, const float* b3, int32_t readout, float* a12, float* p, float* y,
+                 float* r, gml_stream_t stream);
+int64_t gml_ppgn_dw_floats(int32_t Cin, int32_t C);
+size_t gml_ppgn_bwd_workspace_bytes(int64_t B, int32_t nmax, int32_t Cin, int32_t C);
+int gml_ppgn_bwd(const float* x, const int32_t* n, int64_t B, int32_t nmax, int32_t Cin, int32_t C, const float* w1, const float* w2,
+                 const float* w3, const float* a12, const float* p, const float* y, const float* dy, const float* dr, int32_t readout,
+                 float* dx, float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
