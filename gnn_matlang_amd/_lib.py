@@ -181,6 +181,12 @@ SIGNATURES = {
     'gml_ppgn_dw_floats': (_i64, [_i32, _i32]),
     'gml_ppgn_bwd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
     'gml_ppgn_bwd': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _sz, _p]),
+    'gml_gat_supported': (ctypes.c_int, [_i32, _i32]),
+    'gml_gat_logits': (ctypes.c_int, [_p, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
+    'gml_gat_fwd': (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _p]),
+    'gml_gat_bwd_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
+    'gml_gat_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i32, _i32, _i32,
+                                   _p, _i64, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -2081,3 +2081,131 @@ class PPGNBlockFunction(torch.autograd.Function):
         dw1, dw2, dw3 = d12[:C, :Cin].reshape(s1), d12[C:, :Cin].reshape(s2), d3[:, :C + Cin].reshape(s3)
         return (dx, None, dw1, d12[:C, Cin] if hb1 else None, dw2, d12[C:, Cin] if hb2 else None, dw3, d3[:, C + Cin] if hb3 else None,
                 None)
+
+
+# ---------------------------------------------------------------------------- GAT attention layer (csrc/gml_gat.hip)
+GAT_ACTS = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'elu': 3}
+GAT_SLOPE = 0.2
+
+
+def _gat_act_id(act):
+    if act not in GAT_ACTS:
+        raise ValueError("act: None, 'relu', 'tanh' or 'elu', got %r" % (act,))
+    return GAT_ACTS[act]
+
+
+def gat_conv_supported(x, heads, channels):
+    """the fused attention layer (GATConvFunction) serves this input: float32 [N >= 1, Fin] on the device, heads = 8 and channels in
+    {4, 8, 12, 16, 32} (gml_gat_supported) -- every GatNet of the experiment scripts (8 heads of 8, 12 or 16 channels).  Any number of
+    edges, any degree.  Everything else takes the composition gat_conv_torch.  No shape inside the range is gated onto the composition:
+    one layer forward + backward, fused 90th percentile against the composition's 10th, ms (tools/bench_gat.py, profiles/gat.json,
+    DESIGN s4.20): ZINC-like batch of 64 0.37 against 1.01 (25 -> 8 x 8) and 0.36 against 0.98 (96 -> 8 x 12), mutag batch 16 0.36 against
+    0.79, sr25 0.21 against 0.82, the 900-node grid 0.21 against 0.81, 500 k rows 2.11 against 7.05 and 2.66 against 8.38."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1):
+        return False
+    if _os.environ.get('GML_NO_GAT_FUSED'):
+        return False
+    return bool(_lib.lib().gml_gat_supported(int(heads), int(channels)))
+
+
+def gat_conv_torch(x, edge_index, weight, att_l, att_r, bias=None, act=None, negative_slope=GAT_SLOPE):
+    """GATConv (torch_geometric 1.6.1, concat=True, no attention dropout) composed from torch ops, on any device and dtype: the road
+    of every shape outside gat_conv_supported and the opponent of tools/bench_gat.py.  x [N, Fin], edge_index [2, E] = (source j,
+    target i), weight [H C, Fin], att_l / att_r [1, H, C] (or [H, C]), bias [H C] or None.  Edges with j == i are dropped (masked: no
+    host read), one self edge per node is added (evaluated per node, not as E + N gathered rows), repeated edges count once each.
+    Softmax per target and head with the row maximum subtracted and 1e-16 added to the denominator."""
+    N = x.size(0)
+    H, C = att_l.shape[-2], att_l.shape[-1]
+    src, dst = edge_index[0], edge_index[1]
+    xl = (x @ weight.t()).view(N, H, C)
+    al = (xl * att_l.reshape(1, H, C)).sum(-1)
+    ar = (xl * att_r.reshape(1, H, C)).sum(-1)
+    lrelu = lambda s: torch.where(s > 0, s, s * negative_slope)
+    keep = (src != dst).unsqueeze(1)
+    eself = lrelu(al + ar)                                                        # [N, H]
+    e = lrelu(al[src] + ar[dst])                                                  # [E, H]
+    e = torch.where(keep, e, torch.full_like(e, float('-inf')))
+    idx = dst.unsqueeze(1).expand(-1, H)
+    m = eself.detach().clone().scatter_reduce_(0, idx, e.detach(), 'amax', include_self=True)
+    pself = torch.exp(eself - m)
+    p = torch.exp(e - m[dst])                                                     # exactly 0 on the dropped edges
+    z = pself.clone().index_add_(0, dst, p) + 1e-16
+    out = (pself.unsqueeze(-1) * xl).index_add_(0, dst, p.unsqueeze(-1) * xl[src]) / z.unsqueeze(-1)
+    out = out.reshape(N, H * C)
+    if bias is not None:
+        out = out + bias
+    a = _gat_act_id(act)
+    if a == 1:
+        return torch.relu(out)
+    if a == 2:
+        return torch.tanh(out)
+    if a == 3:
+        return torch.nn.functional.elu(out)
+    return out
+
+
+def gat_edge_index(csr):
+    """int64 [2, E] = (source, target) of a GraphCSR in its target-sorted order (for gat_conv_torch)"""
+    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).to(torch.int64)
+    dst = torch.repeat_interleave(torch.arange(csr.N, device=csr.device), deg, output_size=csr.E)
+    return torch.stack([csr.col.to(torch.int64), dst])
+
+
+class GATConvFunction(torch.autograd.Function):
+    """y = act(GATConv(x) + bias) over a GraphCSR of the (source, target) edges: the projection xl = x W^T (torch.matmul, fp32), the head
+    logits (gml_gat_logits) and the edge softmax + weighted gather + bias + activation of every target row (gml_gat_fwd): three launches.
+    Backward: gml_gat_bwd (four launches: target view, source view, partial sums, fold) -> dxl, datt_l, datt_r, dbias, then dW =
+    dxl^T x and, when x needs one, dx = dxl W (torch.matmul): six.  The attention weights are recomputed in the backward from the
+    logits and the row maximum / sum the forward leaves ([N, H] each); no [E, H] alpha is stored.  No atomics, no host read:
+    bit-reproducible, capturable.  Plain fp32 (exact_products() changes nothing)."""
+
+    @staticmethod
+    def forward(ctx, x, csr, weight, att_l, att_r, bias, act=None):
+        x = _f32c(x, 'x')
+        weight = _f32c(weight, 'weight')
+        H, C = int(att_l.shape[-2]), int(att_l.shape[-1])
+        HC, N = H * C, int(x.size(0))
+        if x.dim() != 2 or weight.dim() != 2 or weight.size(1) != x.size(1) or weight.size(0) != HC or tuple(att_r.shape[-2:]) != (H, C):
+            raise ValueError('GAT layer: x [N, Fin], weight [H C, Fin], att_l / att_r [1, H, C] expected')
+        if csr.N != N:
+            raise ValueError('GraphCSR was built for %d nodes, x has %d rows' % (csr.N, N))
+        al_w, ar_w = _f32c(att_l.reshape(HC), 'att_l'), _f32c(att_r.reshape(HC), 'att_r')
+        b = None if bias is None else _f32c(bias, 'bias')
+        a = _gat_act_id(act)
+        dev = x.device
+        with torch.cuda.device(dev):
+            xl = torch.matmul(x, weight.t())
+            al = torch.empty(N, H, dtype=torch.float32, device=dev)
+            ar, m, z = torch.empty_like(al), torch.empty_like(al), torch.empty_like(al)
+            y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+            st = _stream(dev)
+            with _Timed('gat_fwd', q=4 * ((csr.E + N) * HC + N * HC)):
+                _lib.call('gml_gat_logits', _ptr(xl), HC, _ptr(al_w), _ptr(ar_w), N, H, C, _ptr(al), _ptr(ar), st)
+                _lib.call('gml_gat_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(xl), HC, _ptr(al), _ptr(ar), _ptr(b), N, csr.E, H, C, a,
+                          _ptr(y), HC, _ptr(m), _ptr(z), st)
+        ctx.csr, ctx.act, ctx.dims = csr, a, (N, H, C)
+        ctx.att_shapes = (att_l.shape, att_r.shape)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight, al_w, ar_w, xl, al, ar, m, z, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, al_w, ar_w, xl, al, ar, m, z, y = ctx.saved_tensors
+        csr, (N, H, C) = ctx.csr, ctx.dims
+        HC, dev = H * C, x.device
+        dy = _f32c(dy, 'grad of y')
+        with torch.cuda.device(dev):
+            dxl = torch.empty(N, HC, dtype=torch.float32, device=dev)
+            datt = torch.empty(3, HC, dtype=torch.float32, device=dev)
+            nws = int(_lib.lib().gml_gat_bwd_workspace_bytes(N, csr.E, H, C))
+            ws = torch.empty(max(nws // 4, 4), dtype=torch.float32, device=dev)
+            with _Timed('gat_bwd'):
+                _lib.call('gml_gat_bwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(csr.pos_t), _ptr(xl), HC,
+                          _ptr(al), _ptr(ar), _ptr(m), _ptr(z), _ptr(y), HC, _ptr(dy), HC, _ptr(al_w), _ptr(ar_w), N, csr.E, H, C, ctx.act,
+                          _ptr(dxl), HC, _ptr(datt[0]), _ptr(datt[1]), _ptr(datt[2]) if ctx.has_bias else None, _ptr(ws), ws.numel() * 4,
+                          _stream(dev))
+            dw = torch.matmul(dxl.t(), x) if ctx.needs_input_grad[2] else None
+            dx = torch.matmul(dxl, weight) if ctx.needs_input_grad[0] else None
+        sl, sr = ctx.att_shapes
+        return dx, None, dw, datt[0].reshape(sl), datt[1].reshape(sr), datt[2] if ctx.has_bias else None, None

@@ -816,6 +816,157 @@ def mutag_ppgn(ninp=9):                    # mutag.py:18-72 (nmax 28; three bloc
     return PPGN(ninp, 32, 3, bias=True, readout='diag', hidden=32, head_act='relu', nout=1, nmax=28)
 
 
+class GAT(torch.nn.Module):
+    """The GatNet of every PyG experiment script (Zinc12k.py:221-245, sr25.py:169-191, ...) as one class: conv1 .. convK =
+    gat.GATConv(., widths[i], heads=8, concat=True) over the raw adjacency, x <- act(conv_i x) with act 'elu', 'tanh' or 'relu' applied
+    inside the layer's launch, F.dropout in front of every layer in training (dropout > 0), bnI after the layers named in bn_after
+    (nbn of them declared: the scripts declare some they never call), the pools of _pool (or pool=None with head='node') and the head
+         'mlp'        : fc2(relu(fc1 x)), fc1: nin -> hidden                              (Zinc12k.py:244-245, counting.py:264-266)
+         'tanh'       : tanh(fc1 x), fc1: nin -> nclass, no fc2                           (sr25.py:189)
+         'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)   (ptc.py:270-271,
+                        enzymes.py:276)
+         'bn_mlp'     : log_softmax(fc2(relu(fc1(bn1 x)))), fc1: nin -> hidden, bn1 a plain torch BatchNorm of the pooled rows
+                        (mnist75.py:144-148; nbn == 0)
+         'node'       : fc2 x on every node row, no fc1; needs pool=None                  (filtering.py:198)
+    Same attribute names as the scripts, so their state_dicts load.  A padded static batch (batch_padded(..., adjacency=True)) works:
+    a padding node carries only its self loop, which is dropped and re-added like any other, so it sees itself alone; the pools skip
+    the padding graph and the bnI get the row validity.  Each layer takes the fused road where functional.gat_conv_supported allows,
+    else functional.gat_conv_torch; _road='torch' forces the composition."""
+
+    _HEADS = ('mlp', 'tanh', 'log_softmax', 'bn_mlp', 'node')
+
+    def __init__(self, ninp, widths, act='elu', pool='add', head='mlp', hidden=0, nclass=1, dropout=0.0, bn_after=(), nbn=0, heads=8):
+        super().__init__()
+        from .gat import GATConv
+        widths = [int(w) for w in widths]
+        if act not in ('elu', 'tanh', 'relu') or head not in self._HEADS:
+            raise ValueError('act: elu / tanh / relu; head: %s' % ' / '.join(self._HEADS))
+        if (pool is None) != (head == 'node'):
+            raise ValueError("pool=None and head='node' go together: a node-level model has no pooling and reads out every row")
+        if any(not 1 <= int(b) <= min(len(widths), nbn) for b in bn_after):
+            raise ValueError('bn_after names layers 1 .. K whose BatchNorm is declared (nbn)')
+        if head in ('mlp', 'bn_mlp') and not hidden > 0:
+            raise ValueError("head='%s' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)" % head)
+        if head == 'bn_mlp' and nbn:
+            raise ValueError("head='bn_mlp' names its BatchNorm bn1: no layer BatchNorms (nbn == 0)")
+        self.nlayers, self.act, self.pool, self.head = len(widths), act, pool, head
+        self.bn_after = frozenset(int(b) for b in bn_after)
+        fin = int(ninp)
+        for i, w in enumerate(widths, start=1):
+            setattr(self, 'conv%d' % i, GATConv(fin, w, heads=heads, concat=True, dropout=0.0))
+            fin = heads * w
+        for i in range(1, nbn + 1):
+            setattr(self, 'bn%d' % i, BatchNorm1d(fin))
+        nin = fin * (len(pool) if isinstance(pool, tuple) else 1)
+        if head == 'bn_mlp':
+            self.bn1 = torch.nn.BatchNorm1d(nin)
+        if head == 'tanh':
+            self.fc1 = torch.nn.Linear(nin, nclass)
+        else:
+            if head == 'node':
+                hidden = 0
+            if hidden:
+                self.fc1 = torch.nn.Linear(nin, hidden)
+            self.fc2 = torch.nn.Linear(hidden or nin, nclass)
+        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
+
+    def forward(self, data, _features=False, _road=None):
+        x = data.x
+        padded = getattr(data, 'pad_graph', False)
+        if self.head == 'bn_mlp' and self.training and padded:
+            raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
+                                      'graph and absent slots in the statistics of bn1')
+        graph = _adjacency(data)
+        nvalid = _node_valid(data) if padded and self.training and self.bn_after else None
+        drop = _dropout_pass(self)
+        for i in range(1, self.nlayers + 1):
+            if drop:
+                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
+            x = getattr(self, 'conv%d' % i)(x, graph, act=self.act, _road='torch' if _road == 'torch' else None)
+            if i in self.bn_after:
+                bn = getattr(self, 'bn%d' % i)
+                x = bn(x) if nvalid is None else bn(x, valid=nvalid)
+        if self.pool is not None:
+            x = _pool(self.pool, x, data)
+        if _features:
+            return x
+        if self.head == 'node':
+            return tall_linear(x, self.fc2)
+        if self.head == 'tanh':
+            return torch.tanh(tall_linear(x, self.fc1))
+        if self.head == 'bn_mlp':
+            x = self.bn1(x)
+        if hasattr(self, 'fc1'):
+            x = F.relu(tall_linear(x, self.fc1))
+        x = tall_linear(x, self.fc2)
+        return x if self.head == 'mlp' else F.log_softmax(x, dim=1)
+
+    def features(self, data, pad_grad_zero=False):
+        """the features the head is applied to: the pooled graph rows, with head='node' the node rows (pad_grad_zero: accepted for
+        symmetry with GNNML3.features; the pool masks the padding graph's gradient itself)"""
+        return self.forward(data, _features=True)
+
+
+def zinc_gat(ninp=25):                     # Zinc12k.py:221-245 (8 | 12 | 12 | 12 channels, elu, add-pool, relu(fc1: 96 -> 64), fc2: 64 -> 1)
+    return GAT(ninp, (8, 12, 12, 12), act='elu', pool='add', head='mlp', hidden=64)
+
+
+def mutag_gat(ninp=8):                     # mutag.py:186-212 (8 | 16 | 16, elu, mean-pool, relu(fc1: 128 -> 10), fc2: 10 -> 1)
+    return GAT(ninp, (8, 16, 16), act='elu', pool='mean', head='mlp', hidden=10)
+
+
+def enzymes_gat(ninp=4):                   # enzymes.py:245-276 (8 | 16 | 16 | 16, elu, (mean, max) pools, log_softmax(fc2: 256 -> 6), no fc1)
+    return GAT(ninp, (8, 16, 16, 16), act='elu', pool=('mean', 'max'), head='log_softmax', nclass=6)
+
+
+def freqclass_gat(ninp=1, dropout=0.2):    # freqclass.py:208-233 (8 | 16 | 16, elu, dropout 0.2, mean-pool, relu(fc1: 128 -> 32), fc2: 32 -> 1)
+    return GAT(ninp, (8, 16, 16), act='elu', pool='mean', head='mlp', hidden=32, dropout=dropout)
+
+
+def ptc_gat(ninp=20, dropout=0.1):         # ptc.py:233-271 (16 x 4, elu, dropout 0.1; bn1, bn2 declared, never called; (mean, max) pools, relu(fc1: 256 -> 100), log_softmax(fc2: 100 -> 2))
+    return GAT(ninp, (16, 16, 16, 16), act='elu', pool=('mean', 'max'), head='log_softmax', hidden=100, nclass=2, dropout=dropout, nbn=2)
+
+
+def proteins_gat(ninp=4, dropout=0.1):     # proteins.py:168-206 (16 | 16, elu, dropout 0.1; bn1, bn2 declared, never called; (mean, max) pools, relu(fc1: 256 -> 100), log_softmax(fc2: 100 -> 2))
+    return GAT(ninp, (16, 16), act='elu', pool=('mean', 'max'), head='log_softmax', hidden=100, nclass=2, dropout=dropout, nbn=2)
+
+
+def enzymes_contfeat_gat(ninp=22, dropout=0.1):
+    """enzymes_contfeat.py:244-282: 16 | 16, elu, dropout 0.1, bn1 / bn2 after the layers, (mean, max) pools, relu(fc1: 256 -> 100),
+    log_softmax(fc2: 100 -> 6).  bn1 / bn2 are 128 wide: beyond the masked BatchNorm kernel (C <= 64), so a padded static batch in
+    TRAINING raises BatchNorm1d's NotImplementedError, as enzymes_contfeat_gnnml1 does; plain batches and evaluation run."""
+    return GAT(ninp, (16, 16), act='elu', pool=('mean', 'max'), head='log_softmax', hidden=100, nclass=6, dropout=dropout,
+               bn_after=(1, 2), nbn=2)
+
+
+def sr25_gat(ninp=2):                      # sr25.py:169-191 (16 | 16 | 16, tanh, add-pool, tanh(fc1: 128 -> 10))
+    return GAT(ninp, (16, 16, 16), act='tanh', pool='add', head='tanh', nclass=10)
+
+
+def graph8c_gat(ninp=2):                   # graph8c.py:171-193 (the sr25 shapes)
+    return GAT(ninp, (16, 16, 16), act='tanh', pool='add', head='tanh', nclass=10)
+
+
+def exp_gat(ninp=2):                       # exp_iso.py:171-193 (the sr25 shapes)
+    return GAT(ninp, (16, 16, 16), act='tanh', pool='add', head='tanh', nclass=10)
+
+
+def exp_classify_gat(ninp=2):              # exp_classify.py:184-207 (16 | 16 | 16, relu, mean-pool, relu(fc1: 128 -> 10), fc2: 10 -> 1)
+    return GAT(ninp, (16, 16, 16), act='relu', pool='mean', head='mlp', hidden=10)
+
+
+def counting_gat(ninp=2):                  # counting.py:239-266 (16 x 5, relu, add-pool, relu(fc1: 128 -> 32), fc2: 32 -> 1)
+    return GAT(ninp, (16, 16, 16, 16, 16), act='relu', pool='add', head='mlp', hidden=32)
+
+
+def filtering_gat(ninp=1):                 # filtering.py:176-198 (16 | 16 | 16, elu, node-level: fc2: 128 -> 1 on every node, no pooling)
+    return GAT(ninp, (16, 16, 16), act='elu', pool=None, head='node', nclass=1)
+
+
+def mnist75_gat(ninp=3, dropout=0.1):      # mnist75.py:119-148 (8 | 16 | 16, elu, dropout 0.1, mean-pool, bn1 on the pooled rows, relu(fc1: 128 -> 32), log_softmax(fc2: 32 -> 10))
+    return GAT(ninp, (8, 16, 16), act='elu', pool='mean', head='bn_mlp', hidden=32, nclass=10, dropout=dropout)
+
+
 def zinc_loss(pre, y):                     # Zinc12k.py:365
     return F.l1_loss(pre, y.unsqueeze(-1), reduction='sum')
 

@@ -1014,6 +1014,46 @@ int gml_ppgn_bwd(const float* x, const int32_t* n, int64_t B, int32_t nmax, int3
                  const float* w3, const float* a12, const float* p, const float* y, const float* dy, const float* dr, int32_t readout,
                  float* dx, float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream);
 
+/* GAT (the attention baseline of every PyG experiment script, e.g. Zinc12k.py:221-245): the edge-softmax attention of GATConv
+ * (torch_geometric 1.6.1, concat=True, negative_slope 0.2, no attention dropout) behind the projection xl = x W^T, which the caller
+ * computes (csrc/gml_gat.hip).  xl [N, H C] in rows of ldxl, head h = columns [h C, (h + 1) C).  The graph is a GraphCSR's two views:
+ * (rowptr, col) lists the sources j of every target i, (rowptr_t, col_t) the targets i of every source j, pos_t[k] = the target-view
+ * position of source-view edge k.  Entries with col == row are skipped and ONE self edge per node is implicit; repeated edges count
+ * once per occurrence.
+ *
+ * gml_gat_logits: al[n, h] = sum_c xl[n, h, c] att_l[h, c] (the source term), ar likewise with att_r (the target term); al, ar [N, H]
+ *   contiguous, c ascending.  One launch.
+ * gml_gat_fwd: per target i and head h over its edges (j -> i), the self edge first, then the row in CSR order:
+ *   s = al[j, h] + ar[i, h],  e = s > 0 ? s : 0.2 s,  m = max e,  p = exp(e - m),  z = sum p,  out = (sum p xl[j, h, :]) / (z + 1e-16)
+ *   y[i] = act(out + bias), act 0 none / 1 relu / 2 tanh / 3 elu (alpha = 1); bias [H C] optional (NULL).  Two passes over the row (max,
+ *   then sums), so rows of any degree are served.  m, z [N, H] contiguous: the backward's inputs.  One launch.
+ * gml_gat_bwd: dy [N, H C] in rows of lddy -> dxl [N, H C] (rows of lddxl), datt_l, datt_r [H C], dbias [H C] (optional, NULL).
+ *   g = dy act'(y) (act' from y alone).  Four launches:
+ *   target view : g, d_e = <g[i, h], xl[j, h] - xl[i, h]> per edge and head (= dalpha_e - dalpha_self: the softmax gradient does not
+ *                 change under a shift of dalpha, and the differences keep their digits where neighbouring rows are alike) to the
+ *                 workspace in target-view order, S[i, h] = sum_e alpha_e d_e (= <g, out - xl[i]>), dar[i, h] = sum_e slope_e alpha_e
+ *                 (d_e - S) as sum slope alpha d - S sum slope alpha in the same pass, alpha recomputed from al, ar, m, z
+ *   source view : ds_e = slope_e alpha_e (d_e - S[i, h]) where it is used; dal[j, h] = sum over the edges out of j of ds_e;
+ *                 dxl[j, h, :] = sum_e alpha_e g[i, h, :] + dal[j, h] att_l[h, :] + dar[j, h] att_r[h, :]   (self edge first, then CSR order)
+ *   reduction   : per-workgroup partials of datt_l = sum_n dal[n, h] xl[n, h, c], datt_r (with dar) and dbias = sum_n g over
+ *                 contiguous row ranges, n ascending; then one fold in ascending workgroup order.
+ *   No atomics: every sum has a fixed order, two runs give the same bits.
+ * Range: H = 8, C in {4, 8, 12, 16, 32} (gml_gat_supported), any N >= 1, E >= 0 (below 2^31), any degree; rows must be float4
+ * addressable (pointers 16-byte aligned, leading dimensions multiples of 4), else GML_E_UNSUPPORTED.  Nothing is launched on any error.
+ * Plain fp32 fmaf / expf / tanhf.  No allocation, no host read: capturable on one stream. */
+int gml_gat_supported(int32_t H, int32_t C);
+int gml_gat_logits(const float* xl, int64_t ldxl, const float* att_l, const float* att_r, int64_t N, int32_t H, int32_t C, float* al,
+                   float* ar, gml_stream_t stream);
+int gml_gat_fwd(const int32_t* rowptr, const int32_t* col, const float* xl, int64_t ldxl, const float* al, const float* ar,
+                const float* bias, int64_t N, int64_t E, int32_t H, int32_t C, int32_t act, float* y, int64_t ldy, float* m, float* z,
+                gml_stream_t stream);
+size_t gml_gat_bwd_workspace_bytes(int64_t N, int64_t E, int32_t H, int32_t C);
+int gml_gat_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t, const int32_t* pos_t,
+                const float* xl, int64_t ldxl, const float* al, const float* ar, const float* m, const float* z, const float* y,
+                int64_t ldy, const float* dy, int64_t lddy, const float* att_l, const float* att_r, int64_t N, int64_t E, int32_t H,
+                int32_t C, int32_t act, float* dxl, int64_t lddxl, float* datt_l, float* datt_r, float* dbias, void* ws,
+                size_t ws_bytes, gml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
