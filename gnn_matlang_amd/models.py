@@ -6,6 +6,8 @@ configurable class each with the same attribute names, so ``state_dict`` keys ma
 ``forward`` takes a ``gnn_matlang_amd.Batch`` (PyG-compatible field names: x, edge_index,
 edge_index2, edge_attr2, batch, ptr, y).
 """
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
@@ -162,6 +164,68 @@ def _dropout_pass(model):
     return True
 
 
+# The heads of GNNML3, GNNML1Blocks and GAT, each described once: out(fc2(between(fc1(bn1 x)))) without the pieces it leaves out.
+#   bn1      a plain torch.nn.BatchNorm1d of the pooled rows in front (the name is the head's: no block / layer BatchNorms beside it)
+#   fc1      its width: a number, 'nclass', 'hidden' (the constructor's, required > 0), 'hidden?' (declared when hidden > 0) or None
+#   between  'relu' or None, on fc1's output
+#   fc2      whether there is one (its width: nclass)
+#   out      None, 'tanh' or 'log_softmax'
+# Each class maps the names it accepts to these rows (its _HEADS).
+_Head = namedtuple('_Head', 'bn1 fc1 between fc2 out')
+_MLP32 = _Head(False, 32, 'relu', True, None)                   # Zinc12k.py:306-307, freqclass.py:298-300, mutag.py:264-266
+_MLP = _Head(False, 'hidden', 'relu', True, None)               # exp_classify.py:280-281, Zinc12k.py:244-245, counting.py:264-266
+_LIN2 = _Head(False, 'hidden', None, True, None)                # counting.py:332-333, exp_classify.py:240-241: NO activation
+_TANH10 = _Head(False, 10, None, False, 'tanh')                 # sr25.py:248-278 (nclass is not read)
+_TANH = _Head(False, 'nclass', None, False, 'tanh')             # sr25.py:189
+_LIN10 = _Head(False, 'nclass', None, False, None)              # sr25.py, graph8c.py: fc1 x and nothing else
+_LOG_SOFTMAX = _Head(False, 'hidden?', 'relu', True, 'log_softmax')   # ptc.py:270-271, :323-363, enzymes.py:276, proteins.py:259-289
+_BN_MLP32 = _Head(True, 32, 'relu', True, 'log_softmax')        # mnist75.py:262-326
+_BN_MLP = _Head(True, 'hidden', 'relu', True, 'log_softmax')    # mnist75.py:144-148
+_NODE = _Head(False, None, None, True, None)                    # filtering.py:198, :231, :250: fc2 on every NODE row, with pool=None
+
+
+def _declare_head(model, nin, hidden, nclass):
+    """bn1, fc1, fc2 of model._HEADS[model.head] on the model, in that order and under those names (the reference's state_dict keys)"""
+    h = model._HEADS[model.head]
+    if h.fc1 == 'hidden' and not hidden > 0:
+        raise ValueError("head='%s' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)" % model.head)
+    width = {'hidden': hidden, 'hidden?': hidden, 'nclass': nclass}.get(h.fc1, h.fc1)
+    if h.bn1:
+        model.bn1 = torch.nn.BatchNorm1d(nin)
+    if width:
+        model.fc1 = torch.nn.Linear(nin, width)
+    if h.fc2:
+        model.fc2 = torch.nn.Linear(width or nin, nclass)
+
+
+def _apply_head(model, x, _capture=None):
+    """model._HEADS[model.head] on the rows x; _capture: a dict that receives fc1's pre-activation as 'head_pre'"""
+    h = model._HEADS[model.head]
+    if h.bn1:
+        x = model.bn1(x)
+    if hasattr(model, 'fc1'):
+        x = tall_linear(x, model.fc1)
+        if _capture is not None:
+            _capture['head_pre'] = x.detach()                  # (the parity checker takes the head's relu mask from here)
+        if h.between == 'relu':
+            x = F.relu(x)
+    if h.fc2:
+        x = tall_linear(x, model.fc2)
+    if h.out == 'tanh':
+        return torch.tanh(x)
+    return F.log_softmax(x, dim=1) if h.out == 'log_softmax' else x
+
+
+def _bn_valid(model, data, has_bn):
+    """what the bnI of a training forward get as valid=: the row validity of a padded static batch (real nodes only), None otherwise"""
+    return _node_valid(data) if getattr(data, 'pad_graph', False) and model.training and has_bn else None
+
+
+def _layer_bn(model, i, x, nvalid):
+    bn = getattr(model, 'bn%d' % i)
+    return bn(x) if nvalid is None else bn(x, valid=nvalid)
+
+
 # Road choice of a node-level GNNML3 on ONE large graph (GNNML3._dense_big): the dense road (dense_block.py on
 # csrc/gml_dense_big.hip) is taken from this mask fill E / N^2 upwards.  Measured (tools/bench_filtering.py,
 # profiles/filtering_twodgrid.json: one ML3 layer 48 -> 32 + 16 forward + backward on the 30 x 30 grid, S = 11, ms sparse / dense,
@@ -174,10 +238,10 @@ DENSE_BIG_MIN_FILL = 0.025
 
 
 class GNNML3(torch.nn.Module):
-    """head 'mlp32': fc2(relu(fc1 x)), fc1: nin->32, fc2: 32->nclass;  'tanh10': tanh(fc1 x), fc1: nin->10;
-    'mlp' (exp_classify.py:280-281, :294-295): fc2(relu(fc1 x)), fc1: nin->hidden (hidden > 0), fc2: hidden->nclass;
-    'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin->hidden (hidden > 0), else log_softmax(fc2 x), fc2: .->nclass;
-    'node' (with pool=None; filtering.py:252-280): no pooling, one output row per NODE: fc2 x, fc2: nin->nclass, no fc1."""
+    """head: a name of _HEADS (the table at _Head); 'node' goes with pool=None: no pooling, one output row per NODE."""
+
+    _HEADS = dict(mlp32=_MLP32, tanh10=_TANH10, mlp=_MLP, log_softmax=_LOG_SOFTMAX, node=_NODE)
+    _BCE_HEADS = ('mlp',)                  # the heads exp_classify_step_loss fuses (_exp_head)
 
     def __init__(self, ninp, ne, nout1, nout2, nlayers, learnedge=True, bn=False, pool='add', head='mlp32',
                  nclass=1, readout_bn=False, dense_n=0, chain=True, dropout=0.0, hidden=0, pool_bn=None):
@@ -188,6 +252,8 @@ class GNNML3(torch.nn.Module):
         # dropout > 0: F.dropout(x, p) in front of every layer in training (site = the layer index), masks from the device RNG state
         # `dropout_state` (functional.dropout)
         Fn.dropout_threshold(dropout)
+        if head not in self._HEADS:
+            raise ValueError('head: %s' % ' / '.join(self._HEADS))
         if pool_bn is not None and (bn or readout_bn or head != 'log_softmax'):
             raise ValueError("pool_bn goes with head='log_softmax' and neither bn nor readout_bn")
         # chain=False: do not declare the relu hand-over between stacked layers (ML3Layer.chain_after).  The hand-over is
@@ -226,23 +292,8 @@ class GNNML3(torch.nn.Module):
         self.pool_bn = pool_bn
         if pool_bn is not None:
             setattr(self, pool_bn, torch.nn.BatchNorm1d(nin))   # torch defaults (enzymes.py:362)
-        if head == 'node':
-            self.fc2 = torch.nn.Linear(nin, nclass)
-        elif head == 'mlp32':
-            self.fc1 = torch.nn.Linear(nin, 32)
-            self.fc2 = torch.nn.Linear(32, nclass)
-        elif head == 'mlp':
-            if not hidden > 0:
-                raise ValueError("head='mlp' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)")
-            self.fc1 = torch.nn.Linear(nin, hidden)
-            self.fc2 = torch.nn.Linear(hidden, nclass)
-        elif head == 'log_softmax':
-            if hidden:
-                self.fc1 = torch.nn.Linear(nin, hidden)
-            self.fc2 = torch.nn.Linear(hidden or nin, nclass)
-        else:
-            self.fc1 = torch.nn.Linear(nin, 10)
-        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
+        _declare_head(self, nin, hidden, nclass)
+        _init_dropout(self, dropout)          # (after the parameters: the seed draw does not shift their initialisation)
 
     def _declare_chain(self, on):
         for i in range(1, self.nlayers):
@@ -310,7 +361,7 @@ class GNNML3(torch.nn.Module):
         drop = _dropout_pass(self)
         if self._chain and self.dropout > 0:
             self._declare_chain(not drop)
-        nvalid = _node_valid(data) if padded and self.training and self.bn else None     # the bnN layers: real nodes only
+        nvalid = _bn_valid(self, data, self.bn)
         mid = self._dense_mid(data) and _road != 'sparse'        # a batch with an EqualSupports bank: the batched dense road
         if not mid and getattr(data, 'bank', None) is not None and getattr(data, 'edge_index2', None) is None:
             raise ValueError("the sparse road cannot serve this batch: it has no edge tensors (DeviceDataset.batch_dense: x, y and bank slots only); "
@@ -323,12 +374,9 @@ class GNNML3(torch.nn.Module):
             self._declare_chain(not mid and not big and not drop)   # withdrawn on the batched dense road too, back for the next sparse batch
             self._mid_withdrawn = mid
         if big:
-            x = self._forward_dense_big(data, x, drop)
-            return x if _features else tall_linear(x, self.fc2)
+            return self._readout(self._forward_dense_big(data, x, drop), data, False, _features, _capture)
         if mid:
             x = self._forward_dense_big(data, x, drop, bank=data.bank, gid=getattr(data, 'gid', None))
-            if self.head == 'node':
-                return x if _features else tall_linear(x, self.fc2)
             return self._readout(x, data, False, _features, _capture)
         if self.dense_n:
             from .dense_block import dense_supports, spectconv_dense, _library
@@ -361,34 +409,18 @@ class GNNML3(torch.nn.Module):
             else:
                 x = layer(x, csr, data.edge_attr2)
             if self.bn:
-                bn = getattr(self, 'bn%d' % (i + 1))
-                x = bn(x) if nvalid is None else bn(x, valid=nvalid)
-        if self.head == 'node':
-            return x if _features else tall_linear(x, self.fc2)
+                x = _layer_bn(self, i + 1, x, nvalid)
         return self._readout(x, data, pooled, _features, _capture)
 
     def _readout(self, x, data, pooled, _features, _capture):
-        """pool (unless the last layer pooled already), the readout normalisations and the head of a graph-level model"""
-        if not pooled:
+        """pool (unless the last layer pooled already, or the model is node-level), the readout normalisations and the head"""
+        if not pooled and self.pool is not None:
             x = _pool(self.pool, x, data)
         if self.readout_bn:
             x = self.bnr(x)
         if self.pool_bn is not None:
             x = getattr(self, self.pool_bn)(x)
-        if _features:
-            return x
-        if self.head == 'log_softmax':
-            if hasattr(self, 'fc1'):
-                x = F.relu(tall_linear(x, self.fc1))
-            return F.log_softmax(tall_linear(x, self.fc2), dim=1)
-        if self.head == 'mlp32':
-            z1 = tall_linear(x, self.fc1)
-            if _capture is not None:
-                _capture['head_pre'] = z1.detach()            # (the parity checker takes the head's relu mask from here)
-            return tall_linear(F.relu(z1), self.fc2)
-        if self.head == 'mlp':
-            return tall_linear(F.relu(tall_linear(x, self.fc1)), self.fc2)
-        return torch.tanh(tall_linear(x, self.fc1))
+        return x if _features else _apply_head(self, x, _capture)
 
     def features(self, data, pad_grad_zero=False):
         """the pooled (and, with readout_bn, normalised) graph features the head is applied to: [num_graphs, nin].
@@ -460,7 +492,58 @@ def _gnnml1_block(x, csr, fc1, conv, fc2, fc3, mode, act):
                                         fc3.weight, fc3.bias, mode, act)
 
 
-class GNNML1Blocks(torch.nn.Module):
+class _Stack(torch.nn.Module):
+    """What GNNML1Blocks and GAT share: nlayers layers over the raw adjacency, F.dropout in front of every layer in training
+    (dropout > 0), bnI after the layers named in bn_after (1-based; nbn: how many of bn1 .. bn<nbn> are DECLARED -- the scripts declare
+    some they never call, and their checkpoints load with strict=True), the pools of _pool (or pool=None together with head='node':
+    a node-level model) and a head of the class's _HEADS.  A padded static batch hands _node_valid to the bnI in training: padding
+    nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only.  A subclass declares its
+    layers and supplies _layers(x, graph, _road): the function (i, x) -> the output of layer i."""
+
+    def _init_stack(self, nlayers, bn_after, nbn, bn_width, pool, head):
+        """the checks and attributes of the shared arguments, and bn1 .. bn<nbn>"""
+        if (pool is None) != (head == 'node'):
+            raise ValueError("pool=None and head='node' go together: a node-level model has no pooling and reads out every row")
+        if any(not 1 <= int(b) <= min(nlayers, nbn) for b in bn_after):
+            raise ValueError('bn_after names layers 1 .. nlayers whose BatchNorm is declared (nbn)')
+        if self._HEADS[head].bn1 and nbn:
+            raise ValueError("head='%s' names its BatchNorm bn1: no layer BatchNorms (nbn == 0)" % head)
+        self.nlayers, self.pool, self.head, self.bn_after = int(nlayers), pool, head, frozenset(int(b) for b in bn_after)
+        for i in range(1, nbn + 1):
+            setattr(self, 'bn%d' % i, BatchNorm1d(bn_width))
+
+    def _init_head(self, nin, hidden, nclass, dropout):
+        """the head on nin features per pool, then the dropout state"""
+        _declare_head(self, nin * (len(self.pool) if isinstance(self.pool, tuple) else 1), hidden, nclass)
+        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
+
+    def forward(self, data, _features=False, _road=None):
+        x = data.x
+        if self._HEADS[self.head].bn1 and self.training and getattr(data, 'pad_graph', False):
+            # bn1 normalises the pooled rows: the padding graph's row and absent slots would enter its statistics
+            raise NotImplementedError("head '%s' takes plain batches in training: a padded static batch would count its padding "
+                                      'graph and absent slots in the statistics of bn1' % self.head)
+        graph = _adjacency(data)
+        nvalid = _bn_valid(self, data, self.bn_after)
+        layer = self._layers(x, graph, _road)
+        drop = _dropout_pass(self)
+        for i in range(1, self.nlayers + 1):
+            if drop:
+                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
+            x = layer(i, x)
+            if i in self.bn_after:
+                x = _layer_bn(self, i, x, nvalid)
+        if self.pool is not None:
+            x = _pool(self.pool, x, data)
+        return x if _features else _apply_head(self, x)
+
+    def features(self, data, pad_grad_zero=False):
+        """the features the head is applied to: the pooled graph rows [num_graphs, nin], with head='node' the node rows [N, nin]
+        (pad_grad_zero: accepted for symmetry with GNNML3.features; the pool here masks the padding graph's gradient itself)."""
+        return self.forward(data, _features=True)
+
+
+class GNNML1Blocks(_Stack):
     """The GNNML1 of every experiment script (mutag.py:214-266, sr25.py:192-246, graph8c.py:205-246, mnist75.py:262-326,
     exp_classify.py:209-262, Zinc12k.py:248-307, counting.py:268-333, freqclass.py:235-300, ptc.py:273-321, enzymes.py:278-343,
     proteins.py:208-257, enzymes_contfeat.py:284-346, filtering.py:200-250, exp_iso.py:195-247) as one class: `nblocks` blocks
@@ -475,22 +558,13 @@ class GNNML1Blocks(torch.nn.Module):
                                n1 == n2 == n3, block output n1 wide; fused for relu, tanh runs on the composition)
     of widths = (n1, n2, n3) (fc_i1 -> n1, conv_i1 = SpectConv(K = 1, selfconn=False) over the raw adjacency with unit edge values
     -> n2, fc_i2 / fc_i3 -> n3), each through _gnnml1_block (one fused launch) with the composition as the road of any other shape.
-    bn_after: the (1-based) blocks followed by their BatchNorm bnI; nbn: how many of bn1 .. bn<nbn> are DECLARED (the scripts declare
-    some they never call: the reference's checkpoints load with strict=True).  dropout > 0: F.dropout in front of every block in
-    training.  pool: a name or a tuple of names (_pool), or None together with head='node' (a node-level model: no pooling).  head:
-         'mlp32'      : fc2(relu(fc1 x)), fc1: nin -> 32                       (Zinc12k.py:306-307, freqclass.py, mutag.py:264-266)
-         'lin2'       : fc2(fc1 x), fc1: nin -> hidden, NO activation          (counting.py:332-333, exp_classify.py:240-241)
-         'lin10'      : fc1 x, fc1: nin -> nclass, no fc2                      (sr25.py, graph8c.py)
-         'bn_mlp'     : log_softmax(fc2(relu(fc1(bn1 x)))), fc1: nin -> 32, bn1 a plain torch BatchNorm of the pooled rows
-                        (mnist75.py; the name bn1 is the head's: nbn == 0)
-         'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)
-         'node'       : fc2 x on every node row, fc2: nin -> nclass, no fc1; needs pool=None        (filtering.py:231, 250)
-    Same attribute names as the reference, so its state_dict loads.  A padded static batch hands _node_valid to the bnI in training:
-    padding nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only."""
+    bn_after, nbn, dropout, pool: as _Stack has them (the layers are the blocks); head: a name of _HEADS (the table at _Head).
+    Same attribute names as the reference, so its state_dict loads."""
 
     _MODES = dict(sum=0, product=1, factors=2, tanh_factors=3, sum_factors=4)      # the kernel modes of the first five forms
     _FORMS = dict(_MODES, act_sum=5)                                               # every form -> its kernel mode
-    _HEADS = ('mlp32', 'lin2', 'lin10', 'bn_mlp', 'log_softmax', 'node')
+    _HEADS = dict(mlp32=_MLP32, lin2=_LIN2, lin10=_LIN10, bn_mlp=_BN_MLP32, log_softmax=_LOG_SOFTMAX, node=_NODE)
+    _BCE_HEADS = ('mlp32', 'lin2')                                                 # the heads exp_classify_step_loss fuses (_exp_head)
 
     def __init__(self, ninp, widths, nblocks, form='product', act='relu', bn_after=(), nbn=0, pool='add', head='mlp32', hidden=0,
                  nclass=1, dropout=0.0):
@@ -502,40 +576,22 @@ class GNNML1Blocks(torch.nn.Module):
             raise ValueError("form='sum' adds fc_i1 x, conv_i1 x and fc_i2 x * fc_i3 x: three equal widths")
         if form == 'act_sum' and not n1 == n2 == n3:
             raise ValueError("form='act_sum' adds act(fc_i1 x), act(conv_i1 x) and act(fc_i2 x * fc_i3 x): three equal widths")
-        if (pool is None) != (head == 'node'):
-            raise ValueError("pool=None and head='node' go together: a node-level model has no pooling and reads out every row")
         if form == 'sum_factors' and n1 != n2:
             raise ValueError("form='sum_factors' adds act(fc_i1 x) and act(conv_i1 x): widths[0] == widths[1]")
-        if any(not 1 <= int(b) <= min(nblocks, nbn) for b in bn_after):
-            raise ValueError('bn_after names blocks 1 .. nblocks whose BatchNorm is declared (nbn)')
-        if head == 'lin2' and not hidden > 0:
-            raise ValueError("head='lin2' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)")
-        if head == 'bn_mlp' and nbn:
-            raise ValueError("head='bn_mlp' names its BatchNorm bn1: no block BatchNorms (nbn == 0)")
-        self.nblocks, self.form, self.act, self.pool, self.head = int(nblocks), form, act, pool, head
-        self.bn_after = frozenset(int(b) for b in bn_after)
+        self.nblocks, self.form, self.act = int(nblocks), form, act
         nin = {'sum': n1, 'act_sum': n1, 'sum_factors': n1 + n3}.get(form, n1 + n2 + n3)
-        for i in range(1, nbn + 1):
-            setattr(self, 'bn%d' % i, BatchNorm1d(nin))
+        self._init_stack(nblocks, bn_after, nbn, nin, pool, head)
         for i, fin in enumerate([ninp] + [nin] * (nblocks - 1), start=1):
             setattr(self, 'conv%d1' % i, SpectConv(fin, n2, 1, selfconn=False))
             setattr(self, 'fc%d1' % i, torch.nn.Linear(fin, n1))
             setattr(self, 'fc%d2' % i, torch.nn.Linear(fin, n3))
             setattr(self, 'fc%d3' % i, torch.nn.Linear(fin, n3))
-        nin *= len(pool) if isinstance(pool, tuple) else 1
-        if head == 'lin10':
-            self.fc1 = torch.nn.Linear(nin, nclass)
-        else:
-            if head == 'bn_mlp':
-                self.bn1 = torch.nn.BatchNorm1d(nin)
-            if head in ('mlp32', 'bn_mlp'):
-                hidden = 32
-            if head == 'node':
-                hidden = 0
-            if hidden:
-                self.fc1 = torch.nn.Linear(nin, hidden)
-            self.fc2 = torch.nn.Linear(hidden or nin, nclass)
-        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
+        self._init_head(nin, hidden, nclass, dropout)
+
+    def _layers(self, x, csr, _road):
+        """_road: accepted for models.filtering_step_loss, which hands it to every node-level model; there is one road here"""
+        ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)
+        return lambda i, x: self._block(i, x, csr, ones)
 
     def _block(self, i, x, csr, ones):
         g = lambda n: getattr(self, n % i)
@@ -553,48 +609,6 @@ class GNNML1Blocks(torch.nn.Module):
             return A(a) + A(c) + A(f2 * f3)
         h = A(f2 * f3) if mode == 1 else (A(f2) * A(f3) if mode == 2 else torch.tanh(f2) * torch.tanh(f3))
         return torch.cat([A(a), A(c), h], 1)
-
-    def forward(self, data, _features=False, _road=None):
-        """_road: accepted for models.filtering_step_loss, which hands it to every node-level model; there is one road here"""
-        x = data.x
-        padded = getattr(data, 'pad_graph', False)
-        if self.head == 'bn_mlp' and self.training and padded:
-            # bn1 normalises the pooled rows: the padding graph's row and absent slots would enter its statistics
-            raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
-                                      'graph and absent slots in the statistics of bn1')
-        csr = _adjacency(data)
-        nvalid = _node_valid(data) if padded and self.training and self.bn_after else None
-        ones = torch.ones(csr.E, 1, dtype=x.dtype, device=x.device)
-        drop = _dropout_pass(self)
-        for i in range(1, self.nblocks + 1):
-            if drop:
-                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
-            x = self._block(i, x, csr, ones)
-            if i in self.bn_after:
-                bn = getattr(self, 'bn%d' % i)
-                x = bn(x) if nvalid is None else bn(x, valid=nvalid)
-        if self.pool is not None:
-            x = _pool(self.pool, x, data)
-        if _features:
-            return x
-        if self.head == 'node':
-            return tall_linear(x, self.fc2)
-        if self.head == 'lin10':
-            return tall_linear(x, self.fc1)
-        if self.head == 'lin2':
-            return tall_linear(tall_linear(x, self.fc1), self.fc2)
-        if self.head == 'bn_mlp':
-            x = self.bn1(x)
-        if hasattr(self, 'fc1'):
-            x = F.relu(tall_linear(x, self.fc1))
-        x = tall_linear(x, self.fc2)
-        return x if self.head == 'mlp32' else F.log_softmax(x, dim=1)
-
-    def features(self, data, pad_grad_zero=False):
-        """the features the head is applied to: the pooled graph rows [num_graphs, nin], with head='node' the node rows [N, nin]
-        (pad_grad_zero: accepted for symmetry with
-        GNNML3.features; the pool here masks the padding graph's gradient itself)."""
-        return self.forward(data, _features=True)
 
 
 def mutag_gnnml1(ninp=8):                  # mutag.py:214-266 (three blocks 16 | 32 | 16, factor form, relu, a BatchNorm after each, mean-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
@@ -816,24 +830,16 @@ def mutag_ppgn(ninp=9):                    # mutag.py:18-72 (nmax 28; three bloc
     return PPGN(ninp, 32, 3, bias=True, readout='diag', hidden=32, head_act='relu', nout=1, nmax=28)
 
 
-class GAT(torch.nn.Module):
+class GAT(_Stack):
     """The GatNet of every PyG experiment script (Zinc12k.py:221-245, sr25.py:169-191, ...) as one class: conv1 .. convK =
     gat.GATConv(., widths[i], heads=8, concat=True) over the raw adjacency, x <- act(conv_i x) with act 'elu', 'tanh' or 'relu' applied
-    inside the layer's launch, F.dropout in front of every layer in training (dropout > 0), bnI after the layers named in bn_after
-    (nbn of them declared: the scripts declare some they never call), the pools of _pool (or pool=None with head='node') and the head
-         'mlp'        : fc2(relu(fc1 x)), fc1: nin -> hidden                              (Zinc12k.py:244-245, counting.py:264-266)
-         'tanh'       : tanh(fc1 x), fc1: nin -> nclass, no fc2                           (sr25.py:189)
-         'log_softmax': log_softmax(fc2(relu(fc1 x))) with fc1: nin -> hidden (hidden > 0), else log_softmax(fc2 x)   (ptc.py:270-271,
-                        enzymes.py:276)
-         'bn_mlp'     : log_softmax(fc2(relu(fc1(bn1 x)))), fc1: nin -> hidden, bn1 a plain torch BatchNorm of the pooled rows
-                        (mnist75.py:144-148; nbn == 0)
-         'node'       : fc2 x on every node row, no fc1; needs pool=None                  (filtering.py:198)
+    inside the layer's launch; bn_after, nbn, dropout, pool: as _Stack has them; head: a name of _HEADS (the table at _Head).
     Same attribute names as the scripts, so their state_dicts load.  A padded static batch (batch_padded(..., adjacency=True)) works:
     a padding node carries only its self loop, which is dropped and re-added like any other, so it sees itself alone; the pools skip
     the padding graph and the bnI get the row validity.  Each layer takes the fused road where functional.gat_conv_supported allows,
     else functional.gat_conv_torch; _road='torch' forces the composition."""
 
-    _HEADS = ('mlp', 'tanh', 'log_softmax', 'bn_mlp', 'node')
+    _HEADS = dict(mlp=_MLP, tanh=_TANH, log_softmax=_LOG_SOFTMAX, bn_mlp=_BN_MLP, node=_NODE)
 
     def __init__(self, ninp, widths, act='elu', pool='add', head='mlp', hidden=0, nclass=1, dropout=0.0, bn_after=(), nbn=0, heads=8):
         super().__init__()
@@ -841,70 +847,17 @@ class GAT(torch.nn.Module):
         widths = [int(w) for w in widths]
         if act not in ('elu', 'tanh', 'relu') or head not in self._HEADS:
             raise ValueError('act: elu / tanh / relu; head: %s' % ' / '.join(self._HEADS))
-        if (pool is None) != (head == 'node'):
-            raise ValueError("pool=None and head='node' go together: a node-level model has no pooling and reads out every row")
-        if any(not 1 <= int(b) <= min(len(widths), nbn) for b in bn_after):
-            raise ValueError('bn_after names layers 1 .. K whose BatchNorm is declared (nbn)')
-        if head in ('mlp', 'bn_mlp') and not hidden > 0:
-            raise ValueError("head='%s' needs hidden > 0 (fc1: nin -> hidden, fc2: hidden -> nclass)" % head)
-        if head == 'bn_mlp' and nbn:
-            raise ValueError("head='bn_mlp' names its BatchNorm bn1: no layer BatchNorms (nbn == 0)")
-        self.nlayers, self.act, self.pool, self.head = len(widths), act, pool, head
-        self.bn_after = frozenset(int(b) for b in bn_after)
+        self.act = act
         fin = int(ninp)
         for i, w in enumerate(widths, start=1):
             setattr(self, 'conv%d' % i, GATConv(fin, w, heads=heads, concat=True, dropout=0.0))
             fin = heads * w
-        for i in range(1, nbn + 1):
-            setattr(self, 'bn%d' % i, BatchNorm1d(fin))
-        nin = fin * (len(pool) if isinstance(pool, tuple) else 1)
-        if head == 'bn_mlp':
-            self.bn1 = torch.nn.BatchNorm1d(nin)
-        if head == 'tanh':
-            self.fc1 = torch.nn.Linear(nin, nclass)
-        else:
-            if head == 'node':
-                hidden = 0
-            if hidden:
-                self.fc1 = torch.nn.Linear(nin, hidden)
-            self.fc2 = torch.nn.Linear(hidden or nin, nclass)
-        _init_dropout(self, dropout)           # (after the parameters: the seed draw does not shift their initialisation)
+        self._init_stack(len(widths), bn_after, nbn, fin, pool, head)
+        self._init_head(fin, hidden, nclass, dropout)
 
-    def forward(self, data, _features=False, _road=None):
-        x = data.x
-        padded = getattr(data, 'pad_graph', False)
-        if self.head == 'bn_mlp' and self.training and padded:
-            raise NotImplementedError("head 'bn_mlp' takes plain batches in training: a padded static batch would count its padding "
-                                      'graph and absent slots in the statistics of bn1')
-        graph = _adjacency(data)
-        nvalid = _node_valid(data) if padded and self.training and self.bn_after else None
-        drop = _dropout_pass(self)
-        for i in range(1, self.nlayers + 1):
-            if drop:
-                x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i - 1)
-            x = getattr(self, 'conv%d' % i)(x, graph, act=self.act, _road='torch' if _road == 'torch' else None)
-            if i in self.bn_after:
-                bn = getattr(self, 'bn%d' % i)
-                x = bn(x) if nvalid is None else bn(x, valid=nvalid)
-        if self.pool is not None:
-            x = _pool(self.pool, x, data)
-        if _features:
-            return x
-        if self.head == 'node':
-            return tall_linear(x, self.fc2)
-        if self.head == 'tanh':
-            return torch.tanh(tall_linear(x, self.fc1))
-        if self.head == 'bn_mlp':
-            x = self.bn1(x)
-        if hasattr(self, 'fc1'):
-            x = F.relu(tall_linear(x, self.fc1))
-        x = tall_linear(x, self.fc2)
-        return x if self.head == 'mlp' else F.log_softmax(x, dim=1)
-
-    def features(self, data, pad_grad_zero=False):
-        """the features the head is applied to: the pooled graph rows, with head='node' the node rows (pad_grad_zero: accepted for
-        symmetry with GNNML3.features; the pool masks the padding graph's gradient itself)"""
-        return self.forward(data, _features=True)
+    def _layers(self, x, graph, _road):
+        road = 'torch' if _road == 'torch' else None
+        return lambda i, x: getattr(self, 'conv%d' % i)(x, graph, act=self.act, _road=road)
 
 
 def zinc_gat(ninp=25):                     # Zinc12k.py:221-245 (8 | 12 | 12 | 12 channels, elu, add-pool, relu(fc1: 96 -> 64), fc2: 64 -> 1)
@@ -967,6 +920,22 @@ def mnist75_gat(ninp=3, dropout=0.1):      # mnist75.py:119-148 (8 | 16 | 16, el
     return GAT(ninp, (8, 16, 16), act='elu', pool='mean', head='bn_mlp', hidden=32, nclass=10, dropout=dropout)
 
 
+def _graph_valid(valid, data):
+    """valid, or the graph_valid [B] of a padded static batch, or None (a plain batch)"""
+    return valid if valid is not None else getattr(data, 'graph_valid', None)
+
+
+def _valid_sum(rowloss, pre, y, valid):
+    """the loss sum of a padded static batch: rowloss(pre[:B], y[:B]) [B] over its first B = valid.numel() rows, weighted by valid
+    (the padding graph's row and absent slots count zero)"""
+    nl = int(valid.numel())
+    return (rowloss(pre[:nl], y[:nl]) * valid).sum()
+
+
+def _bce_rows(pre, y):
+    return F.binary_cross_entropy(torch.sigmoid(pre[:, 0]), y.to(pre.dtype), reduction='none')
+
+
 def zinc_loss(pre, y):                     # Zinc12k.py:365
     return F.l1_loss(pre, y.unsqueeze(-1), reduction='sum')
 
@@ -975,9 +944,9 @@ def zinc_step_loss(model, data, valid=None, loss_sum=None):
     """zinc_loss(model(data), data.y) -- with the head and the loss as ONE launch each way where the batch is small enough for it
     (functional.HeadL1Function: the reference's batch 64; a static batch's padding graph and absent slots are masked through
     `valid` / data.graph_valid).  Same value and gradients up to summation order; large batches take the general path."""
-    from . import functional as Fn
-    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
-    if model.head == 'mlp32' and model.fc2.weight.size(0) == 1 and data.x.is_cuda:
+    valid = _graph_valid(valid, data)
+    # the fused roads serve fc2(relu(fc1 x)) with fc1: nin -> 32 (head 'mlp32' of GNNML3 and GNNML1Blocks), one output
+    if model._HEADS[model.head] == _MLP32 and model.fc2.weight.size(0) == 1 and data.x.is_cuda:
         nl = int(data.y.numel()) if valid is None else int(valid.numel())
         ng = int(data.num_graphs) if hasattr(data, 'num_graphs') else nl
         small = ng <= 256                                   # (the one-workgroup head: its rows beyond nl get a zero gradient)
@@ -991,12 +960,11 @@ def zinc_step_loss(model, data, valid=None, loss_sum=None):
             # any batch size: one pass + a fold each way (rows beyond nl -- a static batch's padding graph -- get a zero gradient)
             y = data.y[:nl].float().contiguous()
             return Fn.HeadL1BigFunction.apply(x, y, valid, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias, loss_sum)
-        pre = tall_linear(F.relu(tall_linear(x, model.fc1)), model.fc2)
+        pre = _apply_head(model, x)
     else:
         pre = model(data)
     if valid is not None:
-        nl = int(valid.numel())
-        l = ((pre[:nl, 0] - data.y[:nl]).abs() * valid).sum()
+        l = _valid_sum(lambda p, y: (p[:, 0] - y).abs(), pre, data.y, valid)
     else:
         l = zinc_loss(pre, data.y)
     if loss_sum is not None:
@@ -1038,19 +1006,18 @@ def exp_classify_loss(pre, y, valid=None):   # exp_classify.py:328-329
     padded static batch's graph_valid [B] -- the sum over the real graphs of its first B rows, as mutag_loss masks them."""
     if valid is None:
         return F.binary_cross_entropy(torch.sigmoid(pre), y.to(pre.dtype).unsqueeze(-1), reduction='sum')
-    nl = int(valid.numel())
-    l = F.binary_cross_entropy(torch.sigmoid(pre[:nl, 0]), y[:nl].to(pre.dtype), reduction='none')
-    return (l * valid).sum()
+    return _valid_sum(_bce_rows, pre, y, valid)
 
 
 def _exp_head(model):
-    """(fc1, fc2, act) of a model whose readout is fc2(act(fc1 x)): GNNML3 head 'mlp' (relu), GNNML1Blocks heads 'mlp32' (relu) /
-    'lin2' (identity)"""
-    if isinstance(model, GNNML3) and model.head == 'mlp':
-        return model.fc1, model.fc2, 1
-    if isinstance(model, GNNML1Blocks) and model.head in ('mlp32', 'lin2'):        # freqclass.py:298-300: relu(fc1: 96 -> 32), fc2
-        return model.fc1, model.fc2, 1 if model.head == 'mlp32' else 0
-    return None
+    """(fc1, fc2, act) of a model whose head is fc2(act(fc1 x)) and nothing else, act = 1 (relu) / 0 (identity).  Only for the heads a
+    class lists in _BCE_HEADS: the description alone would also admit GNNML3 'mlp32' and GAT 'mlp', which have never taken the
+    fused BCE road -- widening it is a change of behaviour, not of this function."""
+    if getattr(model, 'head', None) not in getattr(model, '_BCE_HEADS', ()):           # (PPGN, DSSGCN: no head name at all)
+        return None
+    h = model._HEADS[model.head]
+    assert h.fc1 and h.fc2 and not h.bn1 and h.out is None, h
+    return model.fc1, model.fc2, int(h.between == 'relu')
 
 
 def exp_classify_step_loss(model, data, valid=None, stats=None):
@@ -1059,8 +1026,7 @@ def exp_classify_step_loss(model, data, valid=None, stats=None):
     fc2(act(fc1 x)) with one output and at most 64 units a side; otherwise the torch-op road.  Plain and padded static batches
     (valid = data.graph_valid), training and evaluation under torch.no_grad() alike.  stats: optional float32 [3] on the device,
     ACCUMULATES {loss, correct predictions, graphs counted} (accuracy_from_stats); no host read."""
-    from . import functional as Fn
-    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
+    valid = _graph_valid(valid, data)
     nl = int(data.y.numel()) if valid is None else int(valid.numel())
     head = _exp_head(model)
     if head is not None and int(head[1].weight.size(0)) == 1:
@@ -1069,8 +1035,7 @@ def exp_classify_step_loss(model, data, valid=None, stats=None):
         if Fn.head_bce_supported(x, fc1.weight, fc2.weight) and nl <= x.size(0):
             return Fn.HeadBCEFunction.apply(x, data.y[:nl], valid, fc1.weight, fc1.bias, fc2.weight, fc2.bias, act, stats)
         Fn._path('head', 'torch ops (BCE head outside the fused kernel)')
-        h = tall_linear(x, fc1)
-        pre = tall_linear(F.relu(h) if act else h, fc2)
+        pre = _apply_head(model, x)
     else:
         Fn._path('head', 'torch ops (BCE on the model\'s own head)')
         pre = model(data)
@@ -1107,16 +1072,13 @@ def mutag_loss(pre, y, valid=None):        # mutag.py:345-348
     """valid: a padded static batch's graph_valid [B] -- the BCE sum over the real graphs of its first B rows (mutag.py:349-351)."""
     if valid is None:
         return F.binary_cross_entropy(torch.sigmoid(pre)[:, 0], y, reduction='sum')
-    nl = int(valid.numel())
-    l = F.binary_cross_entropy(torch.sigmoid(pre[:nl, 0]), y[:nl].to(pre.dtype), reduction='none')
-    return (l * valid).sum()
+    return _valid_sum(_bce_rows, pre, y, valid)
 
 
 def mutag_step_loss(model, data, valid=None):
     """mutag_loss(model(data), data.y) for plain and padded batches alike (a padded batch: valid = data.graph_valid) -- the
     ``loss_fn(model, data)`` of dist.TrainStep."""
-    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
-    return mutag_loss(model(data), data.y, valid)
+    return mutag_loss(model(data), data.y, _graph_valid(valid, data))
 
 
 def tu_loss(pre, y, valid=None):             # ptc.py:416, enzymes.py / proteins.py: F.nll_loss(pred, data.y, reduction='sum')
@@ -1124,15 +1086,12 @@ def tu_loss(pre, y, valid=None):             # ptc.py:416, enzymes.py / proteins
     row and absent slots count zero)."""
     if valid is None:
         return F.nll_loss(pre, y.long(), reduction='sum')
-    nl = int(valid.numel())
-    l = F.nll_loss(pre[:nl], y[:nl].long().clamp(0, int(pre.size(1)) - 1), reduction='none')
-    return (l * valid).sum()
+    return _valid_sum(lambda p, t: F.nll_loss(p, t.long().clamp(0, int(p.size(1)) - 1), reduction='none'), pre, y, valid)
 
 
 def tu_step_loss(model, data, valid=None):
     """tu_loss(model(data), data.y) for plain and padded batches alike -- the ``loss_fn(model, data)`` of dist.TrainStep."""
-    valid = valid if valid is not None else getattr(data, 'graph_valid', None)
-    return tu_loss(model(data), data.y, valid)
+    return tu_loss(model(data), data.y, _graph_valid(valid, data))
 
 
 def dssgcn_loss(model, logits, y, weight_decay=1e-4):   # libs/models_tf.py:286-301
