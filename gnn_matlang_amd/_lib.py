@@ -146,6 +146,7 @@ SIGNATURES = {
     'gml_pair_list_workspace_bytes': (_sz, [_i64, _i64]),
     'gml_pair_list_similar': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
     'gml_dense_pack': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p]),
+    'gml_dense_plan': (_i32, [_i32, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32]),
     'gml_dense_wimg_elems': (_sz, [_i32, _i32, _i32]),
     'gml_dense_pack_w': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p]),
     'gml_dense_wimgt_elems': (_sz, [_i32, _i32, _i32]),
@@ -219,6 +220,9 @@ GML_FWD_ONEWIN = 256
 GML_F16X3 = 1024                # gml_spectconv_fwd / gml_ml3_fwd, ring kernel: f16 (hi, lo) pieces under power-of-two scales
 GML_NO_FOLD = 512               # gml_spectconv_bwd*: leave the dW partials in ws (gml_fold_many)
 GML_FOLD_MAX_JOBS = 16
+# gml_dense_plan: entry points and the road bits it answers (include/gml.h)
+GML_DENSE_SUPPORT_MM, GML_DENSE_CONV_FWD, GML_DENSE_CONV_BWD_X, GML_DENSE_CONV_BWD_W = 0, 1, 2, 3
+GML_DENSE_VEC_IN, GML_DENSE_VEC_OUT, GML_DENSE_VEC_OUT2 = 1, 2, 4
 # gml_edge_mlp_plan: direction, flags and the kernel families it answers (include/gml.h)
 GML_EDGE_FWD, GML_EDGE_BWD = 0, 1
 GML_EDGE_TWO_PIECE, GML_EDGE_THREE_PIECE, GML_EDGE_EXACT, GML_EDGE_HAS_SPLIT, GML_EDGE_WANT_GIN, GML_EDGE_DUAL, GML_EDGE_UNIQUE = 0, 1, 2, 4, 8, 16, 32

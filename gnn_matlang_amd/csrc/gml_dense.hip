@@ -45,6 +45,54 @@ __device__ __forceinline__ bf16x8 dn_tr_frag(const unsigned char* p0, const unsi
 // then fall on distinct banks; a single tile needs no pad)
 __host__ __device__ constexpr int dn_pitch(int nft) { return 32 * nft + (nft == 1 ? 0 : 16); }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The plan: which template and which roads a call takes, decided HERE and nowhere else -- the entry points launch what these
+// functions answer, and gml_dense_plan (include/gml.h) returns the same answer on the host, without a launch.  An operand goes by
+// float4 when its width, its rows' pitch and the stride between its column slices are multiples of 4 floats AND it starts on a
+// 16-byte boundary; element by element otherwise.  (A float4 store at a 4-byte-aligned address gave the same bits in the one run that
+// tried it, DESIGN s4.7a: a wrong decision need not show in the values, so the ABI tests hold the decision itself through
+// gml_dense_plan.)
+// The plan word keeps NFT in bits 8 .. 15 and NOT in bits 16 .. 23.  The weight gradient's NOT is its number of 64-column
+// workgroups along Fout (gridDim.z), so it takes Fout up to DN_DW_MAX_FOUT = 255 * 64 and answers GML_E_UNSUPPORTED beyond.
+#define DN_DW_MAX_FOUT (255 * 64)
+static inline int dn_vec(int width, int64_t ld, int stride, const void* ptr) {
+    return (width % 4 == 0 && ld % 4 == 0 && stride % 4 == 0 && ((uintptr_t)ptr & 15) == 0) ? 1 : 0;
+}
+static inline int dn_nft(int F) { const int t = (F + 15) / 16; return t <= 1 ? 1 : (t <= 2 ? 2 : (t <= 4 ? 4 : 8)); }   // feature tiles of the template
+static inline int dn_not(int Fout) { return Fout <= 64 ? 4 : 8; }                                                     // output tiles of the template
+static inline int dn_plan_bits(int nft, int no, int vin, int vout, int vout2) {
+    return (vin ? GML_DENSE_VEC_IN : 0) | (vout ? GML_DENSE_VEC_OUT : 0) | (vout2 ? GML_DENSE_VEC_OUT2 : 0) | nft << 8 | no << 16;
+}
+static inline int dn_plan_nft(int plan) { return (plan >> 8) & 0xff; }
+static inline int dn_plan_not(int plan) { return (plan >> 16) & 0xff; }
+static int dn_plan_mm(const void* act, int64_t lda, int sa, const void* out, int64_t ldo, int so, int F) {
+    return dn_plan_bits(dn_nft(F), 0, dn_vec(F, lda, sa, act), dn_vec(F, ldo, so, out), 0);
+}
+static int dn_plan_conv(const void* x, int64_t ldx, const void* hcat, const void* out2, int64_t ldo2, int Fin, int Fout) {
+    // hcat is contiguous [B n, S Fin]: its pitch and its stride are multiples of Fin
+    return dn_plan_bits(dn_nft(Fin), dn_not(Fout), dn_vec(Fin, ldx, 0, x), hcat != nullptr ? dn_vec(Fin, 0, 0, hcat) : 0,
+                        dn_vec(Fout, ldo2, 0, out2));
+}
+static int dn_plan_bwdx(const void* dx, int64_t lddx, int Fin, int Fout) {         // (g is read element by element)
+    return dn_plan_bits(dn_nft(Fin), dn_not(Fout), 0, dn_vec(Fin, lddx, 0, dx), 0);
+}
+static int dn_plan_dw(const void* x, int64_t ldx, int Fin, int Fout) {             // NOT: workgroups along Fout, 64 columns each
+    return dn_plan_bits(dn_nft(Fin), (Fout + 63) / 64, dn_vec(Fin, ldx, 0, x), 0, 0);
+}
+
+extern "C" int32_t gml_dense_plan(int32_t entry, const void* in, int64_t ld_in, int32_t s_in, const void* out, int64_t ld_out,
+                                  int32_t s_out, const void* out2, int64_t ld_out2, int32_t F, int32_t Fout) {
+    if (entry < GML_DENSE_SUPPORT_MM || entry > GML_DENSE_CONV_BWD_W) return GML_E_BADARG;
+    if (F < 1 || F > 128) return GML_E_UNSUPPORTED;
+    if (entry != GML_DENSE_SUPPORT_MM && (Fout < 1 || Fout > (entry == GML_DENSE_CONV_BWD_W ? DN_DW_MAX_FOUT : 128))) return GML_E_UNSUPPORTED;
+    switch (entry) {
+        case GML_DENSE_SUPPORT_MM: return dn_plan_mm(in, ld_in, s_in, out, ld_out, s_out, F);
+        case GML_DENSE_CONV_FWD: return dn_plan_conv(in, ld_in, out, out2, ld_out2, F, Fout);
+        case GML_DENSE_CONV_BWD_X: return dn_plan_bwdx(out, ld_out, F, Fout);
+        default: return dn_plan_dw(in, ld_in, F, Fout);
+    }
+}
+
 template <int NFT, bool ACC>
 __global__ __launch_bounds__(384) void gml_k_dense_support_mm(GmlDenseParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dn_lds[];
@@ -181,7 +229,7 @@ __device__ __forceinline__ void dn_dma16(u32x4 rs, uint32_t lds_addr, int voff) 
 template <int NFT, int NOT, bool WRITE_H>
 __global__ __launch_bounds__(576) void gml_k_dense_conv_fwd(GmlDenseParams p, const uint16_t* __restrict__ wimg,
                                                             const float* __restrict__ bias, float* __restrict__ out2,
-                                                            int64_t ldo2, int Fout, int relu) {
+                                                            int64_t ldo2, int Fout, int relu, int vec_out2) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dn_lds[];
     using CH = DnChain<NFT>;
     constexpr int PA = dn_pitch(NFT);
@@ -351,7 +399,7 @@ __global__ __launch_bounds__(576) void gml_k_dense_conv_fwd(GmlDenseParams p, co
                 if (bias != nullptr && o0 + j < Fout) v[j] += bias[o0 + j];
                 if (relu) v[j] = fmaxf(v[j], 0.f);
             }
-            if (Fout % 4 == 0 && ldo2 % 4 == 0) *reinterpret_cast<f32x4*>(o + 16 * ot) = v;
+            if (vec_out2) *reinterpret_cast<f32x4*>(o + 16 * ot) = v;
             else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) if (o0 + j < Fout) o[16 * ot + j] = v[j];
@@ -555,9 +603,8 @@ __global__ __launch_bounds__(256) void gml_k_dense_pack_wT(const float* __restri
 }
 
 static void dn_bwd_shape(int Fin, int Fout, int& NFT, int& NOT) {
-    const int nft = (Fin + 15) / 16;
-    NFT = nft <= 1 ? 1 : (nft <= 2 ? 2 : (nft <= 4 ? 4 : 8));
-    NOT = Fout <= 64 ? 4 : 8;
+    NFT = dn_nft(Fin);
+    NOT = dn_not(Fout);
 }
 
 extern "C" size_t gml_dense_wimgt_elems(int32_t S, int32_t Fin, int32_t Fout) {
@@ -599,11 +646,11 @@ extern "C" int gml_dense_conv_bwd_x(const uint16_t* dimgT, const float* g, int64
     GmlDenseParams p;
     p.dimg = dimgT; p.act = g; p.out = dx; p.lda = ldg; p.ldo = lddx; p.sa = 0; p.so = 0;
     p.B = B; p.S = S; p.n = n; p.KP = KP; p.F = Fin;
+    const int plan = dn_plan_bwdx(dx, lddx, Fin, Fout);
     p.vec_in = 0;
-    p.vec_out = (Fin % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)dx & 15) == 0) ? 1 : 0;
+    p.vec_out = (plan & GML_DENSE_VEC_OUT) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    int NFT, NOT;
-    dn_bwd_shape(Fin, Fout, NFT, NOT);
+    const int NFT = dn_plan_nft(plan), NOT = dn_plan_not(plan);
 #define DN_BWDX(A) return NOT == 4 ? dn_launch_bwdx<A, 4>(p, wimgT, ldg, Fout, st) : dn_launch_bwdx<A, 8>(p, wimgT, ldg, Fout, st)
     if (NFT == 1) { DN_BWDX(1); }
     if (NFT == 2) { DN_BWDX(2); }
@@ -631,15 +678,16 @@ __global__ __launch_bounds__(256) void gml_k_dense_pack_w(const float* __restric
 }
 
 extern "C" size_t gml_dense_wimg_elems(int32_t S, int32_t Fin, int32_t Fout) {
-    const int KT = ((Fin + 15) / 16 + 1) / 2, NOT = Fout <= 64 ? 4 : 8;
+    // the tile count of the kernel template the launcher picks (1, 2, 4 or 8), as gml_dense_pack_w writes it: 5 or 6 feature tiles
+    // (Fin 65 .. 96) run the 8-tile template, whose four K steps are all packed
+    const int KT = (dn_nft(Fin) + 1) / 2, NOT = dn_not(Fout);
     return (size_t)S * KT * NOT * 2 * 64 * 8;
 }
 
 extern "C" int gml_dense_pack_w(const float* w, uint16_t* wimg, int32_t S, int32_t Fin, int32_t Fout, void* stream) {
     if (w == nullptr || wimg == nullptr) return GML_E_BADARG;
     if (S < 1 || Fin < 1 || Fin > 128 || Fout < 1 || Fout > 128) return GML_E_UNSUPPORTED;
-    const int nft = (Fin + 15) / 16, NFT = nft <= 1 ? 1 : (nft <= 2 ? 2 : (nft <= 4 ? 4 : 8));
-    const int KT = (NFT + 1) / 2, NOT = Fout <= 64 ? 4 : 8;
+    const int KT = (dn_nft(Fin) + 1) / 2, NOT = dn_not(Fout);
     const int64_t total = (int64_t)S * KT * NOT * 64 * 8;
     hipLaunchKernelGGL(gml_k_dense_pack_w, dim3((unsigned)gml_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, wimg, S, Fin,
                        Fout, KT, NOT);
@@ -648,7 +696,7 @@ extern "C" int gml_dense_pack_w(const float* w, uint16_t* wimg, int32_t S, int32
 
 template <int NFT, int NOT>
 static int dn_launch_conv(const GmlDenseParams& p, const uint16_t* wimg, const float* bias, float* out2, int64_t ldo2, int Fout,
-                          int relu, bool write_h, hipStream_t st) {
+                          int relu, int vec_out2, bool write_h, hipStream_t st) {
     const size_t lds = (size_t)2 * p.KP * dn_pitch(NFT) + (size_t)3 * DnChain<NFT>::ITEM_T * NOT * 2 * 64 * 16;
     {
         GML_ALLOW_BIG_LDS(rc1, (gml_k_dense_conv_fwd<NFT, NOT, true>), 160 * 1024);
@@ -657,8 +705,8 @@ static int dn_launch_conv(const GmlDenseParams& p, const uint16_t* wimg, const f
         if (rc0 != hipSuccess) return (int)rc0;
     }
     const int nwaves = (p.n + 15) / 16;
-    if (write_h) hipLaunchKernelGGL((gml_k_dense_conv_fwd<NFT, NOT, true>), dim3((unsigned)p.B), dim3(64 * (nwaves + DN_NLD)), lds, st, p, wimg, bias, out2, ldo2, Fout, relu);
-    else hipLaunchKernelGGL((gml_k_dense_conv_fwd<NFT, NOT, false>), dim3((unsigned)p.B), dim3(64 * (nwaves + DN_NLD)), lds, st, p, wimg, bias, out2, ldo2, Fout, relu);
+    if (write_h) hipLaunchKernelGGL((gml_k_dense_conv_fwd<NFT, NOT, true>), dim3((unsigned)p.B), dim3(64 * (nwaves + DN_NLD)), lds, st, p, wimg, bias, out2, ldo2, Fout, relu, vec_out2);
+    else hipLaunchKernelGGL((gml_k_dense_conv_fwd<NFT, NOT, false>), dim3((unsigned)p.B), dim3(64 * (nwaves + DN_NLD)), lds, st, p, wimg, bias, out2, ldo2, Fout, relu, vec_out2);
     return gml_launch_status();
 }
 
@@ -674,17 +722,20 @@ extern "C" int gml_dense_conv_fwd(const uint16_t* dimg, const float* x, int64_t 
     GmlDenseParams p;
     p.dimg = dimg; p.act = x; p.out = hcat; p.lda = ldx; p.ldo = (int64_t)S * Fin; p.sa = 0; p.so = Fin;
     p.B = B; p.S = S; p.n = n; p.KP = KP; p.F = Fin;
-    p.vec_in = (Fin % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
-    p.vec_out = (hcat != nullptr && Fin % 4 == 0 && ((uintptr_t)hcat & 15) == 0) ? 1 : 0;
+    // out2's float4 store is decided with every other road, by the plan (pointer alignment included), and handed to the kernel
+    const int plan = dn_plan_conv(x, ldx, hcat, out2, ldo2, Fin, Fout);
+    p.vec_in = (plan & GML_DENSE_VEC_IN) ? 1 : 0;
+    p.vec_out = (plan & GML_DENSE_VEC_OUT) ? 1 : 0;
+    const int vo2 = (plan & GML_DENSE_VEC_OUT2) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    const int nft = (Fin + 15) / 16;
+    const int nft = dn_plan_nft(plan);
     const bool wh = hcat != nullptr;
 #define DN_CONV(NFT)                                                                                             \
-    return Fout <= 64 ? dn_launch_conv<NFT, 4>(p, wimg, bias, out2, ldo2, Fout, relu, wh, st)                     \
-                      : dn_launch_conv<NFT, 8>(p, wimg, bias, out2, ldo2, Fout, relu, wh, st)
-    if (nft <= 1) { DN_CONV(1); }
-    if (nft <= 2) { DN_CONV(2); }
-    if (nft <= 4) { DN_CONV(4); }
+    return dn_plan_not(plan) == 4 ? dn_launch_conv<NFT, 4>(p, wimg, bias, out2, ldo2, Fout, relu, vo2, wh, st)    \
+                                  : dn_launch_conv<NFT, 8>(p, wimg, bias, out2, ldo2, Fout, relu, vo2, wh, st)
+    if (nft == 1) { DN_CONV(1); }
+    if (nft == 2) { DN_CONV(2); }
+    if (nft == 4) { DN_CONV(4); }
     DN_CONV(8);
 #undef DN_CONV
 }
@@ -734,21 +785,26 @@ static int dn_launch(const GmlDenseParams& p, hipStream_t st) {
 extern "C" int gml_dense_support_mm(const uint16_t* dimg, const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo,
                                     int32_t so, int32_t sum_s, int32_t B, int32_t S, int32_t n, int32_t KP, int32_t F,
                                     void* stream) {
-    if (dimg == nullptr || act == nullptr || out == nullptr || lda < F || ldo < F) return GML_E_BADARG;
+    if (dimg == nullptr || act == nullptr || out == nullptr || sa < 0 || so < 0) return GML_E_BADARG;
+    {   // the rows must hold every column the formula names: (S - 1) sa + F of act, and of out (S - 1) so + F unless summed over s
+        const int64_t smax = S > 1 ? S - 1 : 0;
+        if (lda < smax * sa + F || ldo < (sum_s ? 0 : smax * so) + F) return GML_E_BADARG;
+    }
     if (n < 1 || n > 96 || KP % 32 != 0 || KP < n || KP > 96 || F < 1 || F > 128 || S < 1 || B < 0) return GML_E_UNSUPPORTED;
     if (B == 0) return GML_OK;
     GmlDenseParams p;
     p.dimg = dimg; p.act = act; p.out = out; p.lda = lda; p.ldo = ldo; p.sa = sa; p.so = so;
     p.B = B; p.S = S; p.n = n; p.KP = KP; p.F = F;
-    p.vec_in = (F % 4 == 0 && lda % 4 == 0 && sa % 4 == 0 && ((uintptr_t)act & 15) == 0) ? 1 : 0;
-    p.vec_out = (F % 4 == 0 && ldo % 4 == 0 && so % 4 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+    const int plan = dn_plan_mm(act, lda, sa, out, ldo, so, F);
+    p.vec_in = (plan & GML_DENSE_VEC_IN) ? 1 : 0;
+    p.vec_out = (plan & GML_DENSE_VEC_OUT) ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    const int nft = (F + 15) / 16;
+    const int nft = dn_plan_nft(plan);
 #define DN_CASE(NFT)                                                              \
     return sum_s ? dn_launch<NFT, true>(p, st) : dn_launch<NFT, false>(p, st)
-    if (nft <= 1) { DN_CASE(1); }
-    if (nft <= 2) { DN_CASE(2); }
-    if (nft <= 4) { DN_CASE(4); }
+    if (nft == 1) { DN_CASE(1); }
+    if (nft == 2) { DN_CASE(2); }
+    if (nft == 4) { DN_CASE(4); }
     DN_CASE(8);
 #undef DN_CASE
 }
@@ -904,7 +960,7 @@ extern "C" size_t gml_dense_dw_workspace_bytes(int32_t B, int32_t S, int32_t Fin
 
 template <int NFT>
 static int dn_launch_dw(const uint16_t* dimg, const float* x, int64_t ldx, const float* g, int64_t ldg, float* partial, int B, int S, int n,
-                        int KP, int Fin, int Fout, hipStream_t st) {
+                        int KP, int Fin, int Fout, int plan, hipStream_t st) {
     constexpr int NOTB = 4;                                    // (2 at Fin = 128 -- a second workgroup per CU -- measured slower: twice the recomputed support products)
     const int slices = gml_dense_dw_slices(B), per = (B + slices - 1) / slices;
     const int nwaves = (n + 15) / 16;
@@ -914,8 +970,9 @@ static int dn_launch_dw(const uint16_t* dimg, const float* x, int64_t ldx, const
     if (lds > 160 * 1024) return GML_E_UNSUPPORTED;
     GML_ALLOW_BIG_LDS(rc, (gml_k_dense_dw<NFT, NOTB>), 160 * 1024);
     if (rc != hipSuccess) return (int)rc;
-    const int vec_in = (Fin % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
-    hipLaunchKernelGGL((gml_k_dense_dw<NFT, NOTB>), dim3((unsigned)slices, (unsigned)S, (unsigned)((Fout + 16 * NOTB - 1) / (16 * NOTB))),
+    const int vec_in = (plan & GML_DENSE_VEC_IN) ? 1 : 0;
+    static_assert(16 * NOTB == 64, "dn_plan_dw counts workgroups of 64 output columns");
+    hipLaunchKernelGGL((gml_k_dense_dw<NFT, NOTB>), dim3((unsigned)slices, (unsigned)S, (unsigned)dn_plan_not(plan)),
                        dim3(64 * nwaves), lds, st, dimg, x, ldx, g, ldg, partial, B, S, n, KP, Fin, Fout, per, vec_in);
     return gml_launch_status();
 }
@@ -926,17 +983,18 @@ extern "C" int gml_dense_conv_bwd_w(const uint16_t* dimg, const float* x, int64_
                                     int32_t B, int32_t S, int32_t n, int32_t KP, int32_t Fin, int32_t Fout, void* ws, size_t ws_bytes,
                                     void* stream) {
     if (!dimg || !x || !g || ldx < Fin || ldg < Fout) return GML_E_BADARG;
-    if (n < 1 || n > 96 || KP % 32 != 0 || KP < n || KP > 96 || Fin < 1 || Fin > 128 || Fout < 1 || S < 1 || B < 0) return GML_E_UNSUPPORTED;
+    if (n < 1 || n > 96 || KP % 32 != 0 || KP < n || KP > 96 || Fin < 1 || Fin > 128 || Fout < 1 || Fout > DN_DW_MAX_FOUT || S < 1 || B < 0)
+        return GML_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nw = (int64_t)S * Fin * Fout;
     if (B == 0) { if (dw) gml_zero_async(dw, sizeof(float) * nw, st); return gml_launch_status(); }
     if (!ws || ws_bytes < gml_dense_dw_workspace_bytes(B, S, Fin, Fout)) return GML_E_WORKSPACE;
-    const int nft = (Fin + 15) / 16;
+    const int plan = dn_plan_dw(x, ldx, Fin, Fout), nft = dn_plan_nft(plan);
     int rc;
-    if (nft <= 1) rc = dn_launch_dw<1>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, st);
-    else if (nft <= 2) rc = dn_launch_dw<2>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, st);
-    else if (nft <= 4) rc = dn_launch_dw<4>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, st);
-    else rc = dn_launch_dw<8>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, st);
+    if (nft == 1) rc = dn_launch_dw<1>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, plan, st);
+    else if (nft == 2) rc = dn_launch_dw<2>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, plan, st);
+    else if (nft == 4) rc = dn_launch_dw<4>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, plan, st);
+    else rc = dn_launch_dw<8>(dimg, x, ldx, g, ldg, (float*)ws, B, S, n, KP, Fin, Fout, plan, st);
     if (rc != GML_OK || !dw) return rc;
     gml_fold_job job = {};
     job.partial = (const float*)ws; job.nparts = gml_dense_dw_slices(B); job.n = nw; job.dst[0] = dw; job.ndst[0] = nw;

@@ -181,7 +181,8 @@ extern "C" int gml_xty_wide(const float* A, int64_t lda, const float* B, int64_t
     if (!out || lda < a || ldb < b) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { gml_zero_async(out, sizeof(float) * (size_t)a * b, st); return gml_launch_status(); }
-    if (!A || !B || !ws || ws_bytes < gml_xty_wide_workspace_bytes(n, a, b)) return GML_E_WORKSPACE;
+    if (!A || !B) return GML_E_BADARG;
+    if (!ws || ws_bytes < gml_xty_wide_workspace_bytes(n, a, b)) return GML_E_WORKSPACE;
     GmlXtyWideParams p;
     p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.part = (float*)ws; p.nrows = n; p.a = a; p.b = b;
     p.ntiles = (a + 127) / 128;

@@ -643,12 +643,44 @@ int gml_pair_list_similar(const uint64_t* bits, int64_t G, const int32_t* pairs,
  *   gml_dense_support_mm : out[(b n + r) ldo + s so + f]  =  sum_k D[b][s][r][k] . act[(b n + k) lda + s sa + f]   (f < F <= 128),
  *                          summed over s into out[(b n + r) ldo + f] when sum_s != 0.  Forward: D = the packed supports,
  *                          act = X (sa = 0), out = Hcat [B n, S Fin] (so = Fin); backward: D = the packed transposes,
- *                          act = d Hcat (sa = Fin), sum_s = 1 -> d X.  bf16x3 products, fp32 accumulate. */
+ *                          act = d Hcat (sa = Fin), sum_s = 1 -> d X.  bf16x3 products, fp32 accumulate.
+ *
+ * The contract of the family (these two and the chained entry points gml_dense_pack_w .. gml_dense_conv_bwd_w further down;
+ * tests/test_gpu_dense_abi.py holds every line of it):
+ *   Shapes.   1 <= n <= 96; KP any multiple of 32 with n <= KP <= 96 (columns n .. KP - 1 of an image are zero and inert: every KP
+ *             gives the same bits); 1 <= F, Fin <= 128; 1 <= Fout <= 128, except gml_dense_conv_bwd_w, which takes 1 <= Fout <= 16320
+ *             (64 output columns per workgroup, at most 255 of them along Fout); S >= 1; B, nblocks >= 0.  B = 0 / nblocks = 0 is GML_OK and touches nothing
+ *             (gml_dense_conv_bwd_w with B = 0 zero-fills dw and needs no workspace).
+ *   Read.     Of act / x / g exactly rows [0, B n) and the columns the formula names (s sa + f, f < F): padding columns and rows
+ *             behind row B n - 1 are never read, NaN there reaches nothing.  Images and weight images: exactly their size.
+ *   Written.  Exactly rows [0, B n) x the columns the formula names; columns between the supports' slices (so > F), padding
+ *             columns up to ldo and everything behind row B n - 1 keep their bytes.  gml_dense_pack writes exactly
+ *             nblocks * 2 * n * KP uint16; gml_dense_pack_w / _wt exactly gml_dense_wimg_elems / gml_dense_wimgt_elems int16.
+ *   Alignment. Images, weight images and workspaces: 16 bytes.  act / x / g / out / out2 / hcat / dx: 4 bytes; an operand whose
+ *             width, leading dimension and column stride (sa, so) are multiples of 4 floats and which starts on a 16-byte boundary
+ *             moves as float4, any other element by element -- same bits either way (gml_dense_plan answers which).
+ *   Errors, in this order, nothing written: GML_E_BADARG for a NULL required pointer (bias, hcat and dw may be NULL), a negative
+ *             sa / so, or a leading dimension below the columns the formula names (gml_dense_support_mm: (S - 1) sa + F of act,
+ *             (S - 1) so + F of out, F when sum_s; the others: Fin / Fout); GML_E_UNSUPPORTED outside the shapes above; GML_E_WORKSPACE (gml_dense_conv_bwd_w,
+ *             B > 0) for a NULL or short workspace.
+ *   Determinism. No atomics: two launches on the same inputs agree bit for bit. */
 int gml_dense_pack(const float* blocks, uint16_t* img, int64_t nblocks, int32_t n, int32_t KP, int32_t transpose,
                    gml_stream_t stream);
 int gml_dense_support_mm(const uint16_t* dimg, const float* act, int64_t lda, int32_t sa, float* out, int64_t ldo,
                          int32_t so, int32_t sum_s, int32_t B, int32_t S, int32_t n, int32_t KP, int32_t F,
                          gml_stream_t stream);
+/* Which kernel template and which roads a call of the family takes (csrc/gml_dense.hip: the one place that decides them; the entry
+ * points launch what this answers; answered on the host, no launch, pointers are not dereferenced).  Arguments as the entry point
+ * names them: SUPPORT_MM (in = act, ld_in = lda, s_in = sa, out, ld_out = ldo, s_out = so, F); CONV_FWD (in = x, ld_in = ldx,
+ * out = hcat or NULL, out2, ld_out2 = ldo2, F = Fin, Fout); CONV_BWD_X (out = dx, ld_out = lddx, F = Fin, Fout); CONV_BWD_W
+ * (in = x, ld_in = ldx, F = Fin, Fout); the others are ignored.  Returns the GML_DENSE_VEC_* bits of the operands that move as
+ * float4, | NFT << 8 (feature tiles of the template: 1, 2, 4, 8) | NOT << 16 (output tiles: 4 up to Fout = 64, else 8; CONV_BWD_W:
+ * its workgroups along Fout, at most 255; SUPPORT_MM: 0); GML_E_BADARG for an unknown entry, GML_E_UNSUPPORTED outside the widths
+ * above (CONV_BWD_W: Fout > 16320). */
+enum { GML_DENSE_SUPPORT_MM = 0, GML_DENSE_CONV_FWD = 1, GML_DENSE_CONV_BWD_X = 2, GML_DENSE_CONV_BWD_W = 3 };
+enum { GML_DENSE_VEC_IN = 1, GML_DENSE_VEC_OUT = 2 /* out / hcat / dx */, GML_DENSE_VEC_OUT2 = 4 };
+int32_t gml_dense_plan(int32_t entry, const void* in, int64_t ld_in, int32_t s_in, const void* out, int64_t ld_out, int32_t s_out,
+                       const void* out2, int64_t ld_out2, int32_t F, int32_t Fout);
 /* The same product for ONE large graph: 96 < n <= 1024 nodes, F <= 64, any S >= 1 (the 30 x 30 grid of filtering.py: n = 900, a
  * 40 % full mask, S = 11).  Images in the format above with nblocks = S (gml_dense_big_pack; KP = 32 ceil(n / 32)).
  *   gml_dense_big_support_mm : out[r ldo + s so + f]  =  sum_k D[s][r][k] . act[k lda + s sa + f], summed over s into out[r ldo + f]
@@ -724,7 +756,10 @@ int gml_node_head_bwd(const float* g, const float* x, int64_t ldx, const float* 
  * product's accumulators are the projection's operand, Hcat never goes through a library GEMM.
  *   gml_dense_pack_w   : weight [S][Fin][Fout] fp32 -> bf16 (hi, lo) projection fragments (gml_dense_wimg_elems int16 elements)
  *   gml_dense_conv_fwd : out2[(b n + r) ldo2 + o] = act?( sum_s sum_f (sum_k D[b][s][r][k] x[(b n + k) ldx + f]) W[s][f][o] + bias[o] );
- *                        hcat (optional, [B n, S Fin] contiguous) receives D_s X for the caller's weight gradient. Fin, Fout <= 128. */
+ *                        hcat (optional, [B n, S Fin] contiguous) receives D_s X for the caller's weight gradient, bit for bit what
+ *                        gml_dense_support_mm(sum_s = 0, so = Fin) writes; out2 has the same bits with and without it.  relu != 0:
+ *                        max(., 0), a deselected element is +0.0.  bias may be NULL.  Fin, Fout <= 128.  Contract: see the
+ *                        dense-block paragraph above. */
 size_t gml_dense_wimg_elems(int32_t S, int32_t Fin, int32_t Fout);
 int gml_dense_pack_w(const float* w, uint16_t* wimg, int32_t S, int32_t Fin, int32_t Fout, void* stream);
 int gml_dense_conv_fwd(const uint16_t* dimg, const float* x, int64_t ldx, const uint16_t* wimg, const float* bias,
@@ -740,7 +775,11 @@ int gml_dense_conv_bwd_x(const uint16_t* dimgT, const float* g, int64_t ldg, con
 /* the layer's weight gradient WITHOUT Hcat and without a library GEMM: dW[s][f][o] = sum_b sum_j (D[b][s] X[b])[j][f] g[b n + j][o] -- the
  * support product recomputed per graph on the matrix cores and contracted with g over the graph's rows (K = 16 MFMAs on the
  * untransposed product), per-slice partial sums in ws ([gml_dense_dw_slices(B)][S][Fin][Fout]) folded in slice order into dw
- * (dw == NULL: the partials stay for gml_fold_many).  dimg: the forward images (gml_dense_pack(transpose = 0)); Fin <= 128. */
+ * (dw == NULL: the partials stay for gml_fold_many).  dimg: the forward images (gml_dense_pack(transpose = 0)); Fin <= 128,
+ * 1 <= Fout <= 16320 (255 workgroups of 64 columns; GML_E_UNSUPPORTED beyond).  Slices: gml_dense_dw_slices(B) = min(max(B, 1), 64); slice i owns the graphs [i per, min((i + 1) per, B)) with
+ * per = ceil(B / slices) and writes its whole [S][Fin][Fout] partial -- zeros (+0.0) when it owns no graph (B = 65: slices 33 .. 63),
+ * so the fold never reads an unwritten float.  ws: gml_dense_dw_workspace_bytes(B, S, Fin, Fout) = slices S Fin Fout floats, 16-byte
+ * aligned, all of it written and nothing behind it; 0 for B <= 0.  NULL or short: GML_E_WORKSPACE. */
 int32_t gml_dense_dw_slices(int32_t B);
 size_t gml_dense_dw_workspace_bytes(int32_t B, int32_t S, int32_t Fin, int32_t Fout);
 int gml_dense_conv_bwd_w(const uint16_t* dimg, const float* x, int64_t ldx, const float* g, int64_t ldg, float* dw,
@@ -810,7 +849,11 @@ int gml_xty(const float* A, int64_t lda, const float* B, int64_t ldb, float* out
 
 /* out[i, j] = sum_r A[r, i] * B[r, j] for a wide A (a <= 4096 columns) and b <= 128: the dense-block layer's weight gradient
  * dW = Hcat^T g (libs/layers_tf.py:231-236, its autograd: a = S Fin, b = Fout) on the bf16 matrix cores (bf16x3 split products, fp32
- * accumulate), rows along K through transposing LDS reads; per-row-range partials folded in order.  ws: gml_xty_wide_workspace_bytes. */
+ * accumulate), rows along K through transposing LDS reads; per-row-range partials folded in order.  ws: gml_xty_wide_workspace_bytes
+ * (16-byte aligned; all of it is written, nothing behind it).  Rows behind row n - 1 and columns beyond a / b are never read.
+ * Answers, in this order, nothing written: GML_E_UNSUPPORTED unless n >= 0, 1 <= a <= 4096, 1 <= b <= 128 (gml_xty_wide_supported);
+ * GML_E_BADARG for out == NULL, lda < a or ldb < b; n == 0 zero-fills out (A, B and ws may be NULL) and is GML_OK; GML_E_BADARG for
+ * A == NULL or B == NULL; GML_E_WORKSPACE for a NULL or short ws. */
 int gml_xty_wide_supported(int64_t n, int32_t a, int32_t b);
 size_t gml_xty_wide_workspace_bytes(int64_t n, int32_t a, int32_t b);
 int gml_xty_wide(const float* A, int64_t lda, const float* B, int64_t ldb, float* out, int64_t n, int32_t a, int32_t b,
