@@ -663,7 +663,7 @@ def ml3_split_bwd(gy, y, nout1, x=None, w11=None, b11=None, w12=None, b12=None, 
     if nbytes == 0 and N > 0:
         return None
     ld = (nout1 + 3) // 4 * 4                                # zero padded: float4-readable rows
-    premasked = bool(premasked and gy_seg is None and gy.stride(0) % 4 == 0 and gy.stride(0) >= ld and gy.data_ptr() % 16 == 0)
+    assert not premasked or (gy_seg is None and _rows4_ok(*_rows_of(gy), nout1)), 'a pre-masked gradient is handed on as G: float4-readable rows'
     G = gy if premasked else torch.empty(N, ld, dtype=torch.float32, device=dev)
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
     dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if (need_dx and F2 and not dz_out) else None
@@ -1427,10 +1427,17 @@ def dropout(x, p, training, state, site=0):
     return DropoutFunction.apply(x, float(p), state, int(site))
 
 
-def _bwd_plan(csr, S, Fin, Fout):
-    """(flags, ginfo, (max_edges, max_window), workspace bytes) of the fused backward for this shape, or None."""
+# one fused conv-backward launch as the library plans it: kernel flags, group records and their maxima, dW workspace, rows per group
+ConvBwdPlan = _collections.namedtuple('ConvBwdPlan', 'flags ginfo max_edges max_window ws_bytes rows')
+# which road a conv backward takes: kind 'one128' / 'one64' (one launch of the 128- / 64-row kernel), 'split48' (two launches over the
+# feature slices [0, 32) and [32, Fin)) or 'unfused'; plan: the whole shape's plan or None; halves: the two slices' plans (split48)
+ConvBwdRoad = _collections.namedtuple('ConvBwdRoad', 'kind plan halves')
+
+
+def _bwd_plan(csr, S, Fin, Fout, exact=None):
+    """ConvBwdPlan of the fused backward for this shape (exact: on exact f32 products; None = as this thread runs), or None."""
     L = _lib.lib()
-    for flags in ((_lib.GML_F32_MFMA,) if exact_mode() else (0, _lib.GML_F32_MFMA)):
+    for flags in ((_lib.GML_F32_MFMA,) if (exact_mode() if exact is None else exact) else (0, _lib.GML_F32_MFMA)):
         rows = int(L.gml_spectconv_bwd_group_rows(int(S), int(Fin), int(Fout), flags))
         if rows == 0:
             continue
@@ -1440,38 +1447,73 @@ def _bwd_plan(csr, S, Fin, Fout):
             ginfo, gmax = csr.ginfo_t, csr.gmax_t
         nbytes = int(L.gml_spectconv_bwd_workspace_bytes(csr.N, int(S), int(Fin), int(Fout), gmax[0], gmax[1], flags))
         if nbytes > 0:
-            return flags, ginfo, gmax, nbytes, rows
+            return ConvBwdPlan(flags, ginfo, gmax[0], gmax[1], nbytes, rows)
     return None
+
+
+# 48-wide layers (sr25.py:252-262, mutag.py:272-288: hidden width 32 + 16 / 24 + 24) run as ONE launch of the 8-wave bf16x3 kernel where
+# the library has that shape (round 5: S = 4, 6; GML_BWD_WIDE48=0 turns it off), else as two launches over the feature slices: dX and dW
+# split by input feature; dval is linear in x, so the second launch adds its share (GML_DVAL_ACCUM).  The edge loop runs twice -- still
+# ~2 x faster than the 64-row f32-MFMA kernel these layers ran on (tools/bench_configs.py).
+def _conv_bwd_road(csr, S, Fin, Fout, exact, x_rows4=True, wants_handover=False):
+    """ConvBwdRoad of this shape; the slices need float4-readable x rows (x_rows4) and carry no hand-over (mix / relu_cols / had)."""
+    bf16x3 = lambda p: p is not None and p.rows == 128 and not p.flags & _lib.GML_F32_MFMA
+    plan = _bwd_plan(csr, S, Fin, Fout, exact)
+    if (32 < Fin <= 48 and not exact and not bf16x3(plan) and not wants_handover and x_rows4 and (Fin - 32) % 4 == 0
+            and not (S == 8 and Fout > 16)):                  # (S = 8, 32 columns: no dval += in that kernel)
+        halves = _bwd_plan(csr, S, 32, Fout, exact), _bwd_plan(csr, S, Fin - 32, Fout, exact)
+        if bf16x3(halves[0]) and bf16x3(halves[1]):
+            return ConvBwdRoad('split48', plan, halves)
+    return ConvBwdRoad('unfused' if plan is None else 'one%d' % plan.rows, plan, None)
 
 
 def fused_bwd_available(csr, S, Fin, Fout):
     return _bwd_plan(csr, S, Fin, Fout) is not None
 
 
+def _plan_takes_dz(plan, S, Fin, Fout, nmix):
+    return plan is not None and 1 <= nmix <= 4 and bool(_lib.lib().gml_spectconv_bwd_mix_supported(int(S), int(Fin), int(Fout), int(nmix), plan.flags))
+
+
 def conv_bwd_takes_dz(csr, S, Fin, Fout, nmix):
     """True when the fused backward of this shape can form  dx = conv part + dz wmix  itself (gml_spectconv_bwd_mix)."""
-    if _os.environ.get('GML_NO_DZ') or not (1 <= nmix <= 4):
-        return False
-    plan = _bwd_plan(csr, S, Fin, Fout)
-    return plan is not None and bool(_lib.lib().gml_spectconv_bwd_mix_supported(int(S), int(Fin), int(Fout), int(nmix), plan[0]))
+    return _plan_takes_dz(_bwd_plan(csr, S, Fin, Fout), S, Fin, Fout, nmix)
 
 
 BWD_DMA = _os.environ.get('GML_BWD_DMA') == '1'     # fused backward on the LDS-DMA ring kernel (bwd4) where it applies; A/B switch
 BWD_HAD = _os.environ.get('GML_BWD_HAD', '1') != '0'  # ML3Layer output stage inside the conv backward (gml_spectconv_bwd_had); A/B switch
 
 
-def conv_bwd_had_parts(csr, S, Fin, Fout, F2, want_dx=True):
-    """Partial rows of gml_spectconv_bwd_had for this shape (0: the shape / the build has no fused output stage)."""
-    if not BWD_HAD or BWD_DMA or exact_mode():
-        return 0
-    plan = _bwd_plan(csr, S, Fin, Fout)
-    if plan is None or plan[4] != 128:
-        return 0
-    return int(_lib.lib().gml_spectconv_bwd_had_parts(csr.N, int(S), int(Fin), int(Fout), int(F2), 1 if want_dx else 0, plan[2][0], plan[2][1],
-                                                      plan[0]))
+# rows a kernel may read as float4: leading dimension a multiple of 4 floats that holds `cols`, base aligned to 16 bytes; _rows_of:
+# (row stride, pointer % 16) of a [n, c] tensor -- a column stride other than 1 never passes
+def _rows4_ok(stride, ptr16, cols):
+    return stride % 4 == 0 and stride >= (cols + 3) // 4 * 4 and ptr16 == 0
 
 
-def fused_conv_bwd(csr, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into=None, mix=None, relu_cols=0, had=None):
+def _rows_of(t):
+    return (int(t.stride(0)), t.data_ptr() % 16) if t.stride(1) == 1 else (0, 1)
+
+
+def _g_rows4(G, N, Fout):
+    """G as the 8-wave kernel reads its window (float4): itself, or a copy with rows padded (with zeros) to a multiple of 4 floats"""
+    if _rows4_ok(*_rows_of(G), Fout):
+        return G
+    Gp = torch.zeros(N, (Fout + 3) // 4 * 4, dtype=torch.float32, device=G.device)
+    Gp[:, :Fout] = G
+    return Gp[:, :Fout]
+
+
+def _conv_bwd_call(entry, csr, plan, flags, val_t, x, G, weight, dx, dval_t, dw, ws, own=(), f2=(), own_ws=(), col0=0, lddx=None):
+    """one gml_spectconv_bwd* launch: the arguments every entry point shares, around the entry's `own` ones (f2 / own_ws: the had
+    form's F2 and partial rows).  col0: first of the weight's input features inside the rows of x and dx (leading dimension lddx)."""
+    S, Fin, Fout = weight.shape
+    _lib.call(entry, _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(plan.ginfo), _ptr(val_t), _off(x, col0), int(x.stride(0)), _ptr(G),
+              int(G.stride(0)), _ptr(weight), _off(dx, col0) if dx is not None else _ptr(None), lddx or Fin, _ptr(dval_t), _ptr(dw), *own,
+              csr.N, S, Fin, Fout, *f2, plan.max_edges, plan.max_window, flags, _ptr(ws), ws.numel() if ws is not None else 0, *own_ws,
+              _stream(x.device))
+
+
+def fused_conv_bwd(csr, plan, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into=None, mix=None, relu_cols=0, had=None):
     """one launch: dX, dval (source order), dW.  val_t: supports in source order.  mix = (dz [N, 4], wmix [nmix, Fin]):
     dX = conv part + dz wmix (instead of accumulating into a dx another kernel wrote).  relu_cols (with mix): dX[:, f] for
     f < relu_cols is written multiplied by (x[:, f] > 0) (gml_spectconv_bwd_mix_relu: the relu of the ML3Layer below).
@@ -1480,15 +1522,9 @@ def fused_conv_bwd(csr, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_
     (dcb, dw11, db11, dw12, db12)."""
     S, Fin, Fout = weight.shape
     dev = x.device
-    flags, ginfo, gmax, nbytes, _ = _bwd_plan(csr, S, Fin, Fout)
-    if BWD_DMA:
-        flags |= _lib.GML_DMA_RING
-    ld4 = (Fout + 3) // 4 * 4
-    if G.stride(0) % 4 != 0 or G.stride(0) < ld4 or G.data_ptr() % 16 != 0:
-        # the 8-wave kernel reads the g window as float4: rows padded (with zeros) to a multiple of 4 floats
-        Gp = torch.zeros(csr.N, ld4, dtype=torch.float32, device=dev)
-        Gp[:, :Fout] = G
-        G = Gp[:, :Fout]
+    assert plan.rows == 128 or (mix is None and relu_cols == 0 and had is None), 'the hand-overs ride on the one-launch 128-row backward'
+    flags, nbytes = plan.flags | (_lib.GML_DMA_RING if BWD_DMA else 0), plan.ws_bytes
+    G = _g_rows4(G, csr.N, Fout)
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev) if need_w else None
     if need_x and dx_accum_into is not None:                 # dx already holds another branch's contribution
         dx, flags = dx_accum_into, flags | _lib.GML_ACCUM
@@ -1523,78 +1559,48 @@ def fused_conv_bwd(csr, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_
             kd = (dcb, dw11, db11, dw12, db12)
         had['out'] = (dcb, dw11, db11, dw12, db12)
         with _Timed('spectconv_bwd', q + 8 * csr.N, f):        # (+ the own rows' two Hadamard columns; the rest it reads anyway)
-            _lib.call('gml_spectconv_bwd_had', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t),
-                      _ptr(x), int(x.stride(0)), _ptr(G), int(G.stride(0)), _ptr(weight), _ptr(dx), Fin, _ptr(dval_t),
-                      _ptr(dw), _ptr(w11), _ptr(b11), _ptr(w12), _ptr(b12), int(relu_cols), _ptr(kd[0]), _ptr(kd[1]), _ptr(kd[2]),
-                      _ptr(kd[3]), _ptr(kd[4]), csr.N, S, Fin, Fout, 2, gmax[0], gmax[1], flags, _ptr(ws),
-                      ws.numel() if ws is not None else 0, _ptr(hws), hws.numel() * 4, _stream(dev))
-        if fq is not None:
-            dw = flat.view(S, Fin, Fout)
-        return dx, dval_t, dw
-    with _Timed('spectconv_bwd', q, f):
-        if mix is not None:
-            dz, wmix = mix
+            _conv_bwd_call('gml_spectconv_bwd_had', csr, plan, flags, val_t, x, G, weight, dx, dval_t, dw, ws,
+                           (_ptr(w11), _ptr(b11), _ptr(w12), _ptr(b12), int(relu_cols)) + tuple(_ptr(t) for t in kd), (2,),
+                           (_ptr(hws), hws.numel() * 4))
+    elif mix is not None:
+        dz, wmix = mix
+        with _Timed('spectconv_bwd', q, f):
             if isinstance(wmix, tuple):                      # (fc11.weight, fc12.weight) as they are stored: no concatenation launch
                 wa, wb = wmix
-                _lib.call('gml_spectconv_bwd_mix_relu2', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t),
-                          _ptr(x), int(x.stride(0)), _ptr(G), int(G.stride(0)), _ptr(weight), _ptr(dx), Fin, _ptr(dval_t),
-                          _ptr(dw), _ptr(dz), _ptr(wa), int(wa.size(0)), _ptr(wb), int(wb.size(0)), int(relu_cols), csr.N, S, Fin, Fout,
-                          gmax[0], gmax[1], flags, _ptr(ws), ws.numel() if ws is not None else 0, _stream(dev))
+                _conv_bwd_call('gml_spectconv_bwd_mix_relu2', csr, plan, flags, val_t, x, G, weight, dx, dval_t, dw, ws,
+                               (_ptr(dz), _ptr(wa), int(wa.size(0)), _ptr(wb), int(wb.size(0)), int(relu_cols)))
             else:
-                _lib.call('gml_spectconv_bwd_mix_relu', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t),
-                          _ptr(x), int(x.stride(0)), _ptr(G), int(G.stride(0)), _ptr(weight), _ptr(dx), Fin, _ptr(dval_t),
-                          _ptr(dw), _ptr(dz), _ptr(wmix), int(wmix.size(0)), int(relu_cols), csr.N, S, Fin, Fout, gmax[0], gmax[1], flags,
-                          _ptr(ws), ws.numel() if ws is not None else 0, _stream(dev))
-        else:
-            assert relu_cols == 0, 'the relu hand-over rides on the dz form of the backward'
-            _lib.call('gml_spectconv_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t),
-                      _ptr(x), int(x.stride(0)), _ptr(G), int(G.stride(0)), _ptr(weight), _ptr(dx), Fin, _ptr(dval_t),
-                      _ptr(dw), csr.N, S, Fin, Fout, gmax[0], gmax[1], flags, _ptr(ws),
-                      ws.numel() if ws is not None else 0, _stream(dev))
+                _conv_bwd_call('gml_spectconv_bwd_mix_relu', csr, plan, flags, val_t, x, G, weight, dx, dval_t, dw, ws,
+                               (_ptr(dz), _ptr(wmix), int(wmix.size(0)), int(relu_cols)))
+    else:
+        assert relu_cols == 0, 'the relu hand-over rides on the dz form of the backward'
+        with _Timed('spectconv_bwd', q, f):
+            _conv_bwd_call('gml_spectconv_bwd', csr, plan, flags, val_t, x, G, weight, dx, dval_t, dw, ws)
     if fq is not None:
         dw = flat.view(S, Fin, Fout)
     return dx, dval_t, dw
 
 
-def split48_plan(csr, S, Fin, Fout):
-    """48-wide layers (sr25.py:252-262, mutag.py:272-288: hidden width 32 + 16 / 24 + 24) on the 8-wave bf16x3 backward, which is
-    compiled for Fin <= 32: two launches over the feature slices [0, 32) and [32, Fin).  dX and dW split by input feature; dval is
-    linear in x, so the second launch adds its share (GML_DVAL_ACCUM).  The edge loop runs twice -- still ~2 x faster than the
-    64-row f32-MFMA kernel these layers ran on (tools/bench_configs.py).  Returns the two plans or None."""
-    if exact_mode() or _os.environ.get('GML_NO_SPLIT48') or not (32 < Fin <= 48) or (Fin - 32) % 4 != 0 or (S == 8 and Fout > 16):   # (S = 8, 32 columns: no dval += in that kernel)
-        return None
-    pa, pb = _bwd_plan(csr, S, 32, Fout), _bwd_plan(csr, S, Fin - 32, Fout)
-    if pa is None or pb is None or pa[4] != 128 or pb[4] != 128 or (pa[0] | pb[0]) & _lib.GML_F32_MFMA:
-        return None
-    return pa, pb
-
-
-def fused_conv_bwd_split48(csr, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into, plans):
+def fused_conv_bwd_split48(csr, plans, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into=None):
+    """two launches of the 8-wave kernel over the feature slices [0, 32) and [32, Fin) (_conv_bwd_road); plans: one per slice"""
     S, Fin, Fout = weight.shape
     dev = x.device
-    ld4 = (Fout + 3) // 4 * 4
-    if G.stride(0) % 4 != 0 or G.stride(0) < ld4 or G.data_ptr() % 16 != 0:
-        Gp = torch.zeros(csr.N, ld4, dtype=torch.float32, device=dev)
-        Gp[:, :Fout] = G
-        G = Gp[:, :Fout]
+    G = _g_rows4(G, csr.N, Fout)
     dx = dx_accum_into if (need_x and dx_accum_into is not None) else (torch.empty(csr.N, Fin, dtype=torch.float32, device=dev) if need_x else None)
     dval_t = torch.empty(csr.E, S, dtype=torch.float32, device=dev) if need_val else None
     dws = []
     q, f = conv_cost_bwd(csr.N, csr.E, S, Fin, Fout, need_x, need_val) if PROFILE is not None else (0, 0)
     with _Timed('spectconv_bwd', q, f):
         for part, (f0, f1) in enumerate(((0, 32), (32, Fin))):
-            flags, ginfo, gmax, nbytes, _ = plans[part]
+            flags = plans[part].flags
             if need_x and dx_accum_into is not None:
                 flags |= _lib.GML_ACCUM
             if part == 1 and need_val:
                 flags |= _lib.GML_DVAL_ACCUM
             w_p = weight[:, f0:f1, :].contiguous()
             dw_p = torch.empty(S, f1 - f0, Fout, dtype=torch.float32, device=dev) if need_w else None
-            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev) if need_w else None
-            _lib.call('gml_spectconv_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t),
-                      _off(x, f0), int(x.stride(0)), _ptr(G), int(G.stride(0)), _ptr(w_p), _off(dx, f0) if dx is not None else _ptr(None), Fin,
-                      _ptr(dval_t), _ptr(dw_p), csr.N, S, f1 - f0, Fout, gmax[0], gmax[1], flags, _ptr(ws),
-                      ws.numel() if ws is not None else 0, _stream(dev))
+            ws = torch.empty(max(plans[part].ws_bytes, 4), dtype=torch.uint8, device=dev) if need_w else None
+            _conv_bwd_call('gml_spectconv_bwd', csr, plans[part], flags, val_t, x, G, w_p, dx, dval_t, dw_p, ws, col0=f0, lddx=Fin)
             dws.append(dw_p)
     dw = torch.cat(dws, 1) if need_w else None
     return dx, dval_t, dw
@@ -1602,33 +1608,30 @@ def fused_conv_bwd_split48(csr, val_t, x, G, weight, need_x, need_val, need_w, d
 
 # ---------------------------------------------------------------------------- shared backward pieces
 def _conv_backward(csr, x, val, weight, G, need_x, need_val, need_w, val_t=None, want_source_order=False,
-                   dx_accum_into=None, mix=None, relu_cols=0, had=None):
+                   dx_accum_into=None, mix=None, relu_cols=0, had=None, road=None):
     """G [N,Fout] contiguous = gradient at the (pre-activation) conv output.
     Returns dx, dval, dw; dval is in source order when want_source_order (and the fused kernel ran).
-    dx_accum_into: [N,Fin] buffer that already holds a partial dx; the conv contribution is added to it."""
+    dx_accum_into: [N,Fin] buffer that already holds a partial dx; the conv contribution is added to it.
+    road: the caller's _conv_bwd_road of this shape (decided here otherwise); mix / relu_cols / had: see fused_conv_bwd."""
     S, Fin, Fout = weight.shape
     N = csr.N
     dx = dval = dw = None
     if G.stride(1) != 1:
         G = G.contiguous()
-    # 33 .. 48 input features: ONE launch of the 8-wave kernel where the library has that shape (round 5: S = 4, 6; GML_BWD_WIDE48=0
-    # turns it off), else two launches over the feature slices
-    one48 = None
-    if 32 < Fin <= 48 and not exact_mode():
-        one48 = _bwd_plan(csr, S, Fin, Fout)
-        if one48 is not None and (one48[4] != 128 or (one48[0] & _lib.GML_F32_MFMA)):
-            one48 = None
-    sp48 = split48_plan(csr, S, Fin, Fout) if (one48 is None and mix is None and relu_cols == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) else None
-    if sp48 is not None or fused_bwd_available(csr, S, Fin, Fout):
+    handover = mix is not None or relu_cols != 0 or had is not None
+    if road is None:
+        road = _conv_bwd_road(csr, S, Fin, Fout, exact_mode(), _rows4_ok(*_rows_of(x), Fin), handover)
+    assert road.kind == 'one128' or not handover, 'the dz, relu and output-stage hand-overs ride on the one-launch 128-row backward'
+    if road.kind != 'unfused':
         if val_t is None:
             with _Timed('val_to_source_order'):
                 val_t = csr.to_source_order(val)
-        if sp48 is not None:
+        if road.kind == 'split48':
             _path('conv_bwd', 'fused (group kind 128), two launches over the feature slices [0, 32) and [32, %d)' % Fin, S, Fin, Fout)
-            dx, dval_t, dw = fused_conv_bwd_split48(csr, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into, sp48)
+            dx, dval_t, dw = fused_conv_bwd_split48(csr, road.halves, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into)
         else:
-            _path('conv_bwd', 'fused (group kind %d)' % _bwd_plan(csr, S, Fin, Fout)[4], S, Fin, Fout)
-            dx, dval_t, dw = fused_conv_bwd(csr, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into, mix, relu_cols, had)
+            _path('conv_bwd', 'fused (group kind %d)' % road.plan.rows, S, Fin, Fout)
+            dx, dval_t, dw = fused_conv_bwd(csr, road.plan, val_t, x, G, weight, need_x, need_val, need_w, dx_accum_into, mix, relu_cols, had)
         if need_val and not want_source_order:
             with _Timed('dval_from_source_order'):
                 dval_t = csr.from_source_order(dval_t)
@@ -1721,6 +1724,101 @@ class ChainToken(object):
 
 
 CHAIN = not _os.environ.get('GML_NO_CHAIN')      # A/B switch for the relu hand-over between stacked ML3Layers
+
+
+# ZINC's 30 + 2 top layer: the pool also leaves the relu pattern of every row (4 bytes) and the backward expands the pool's gradient with
+# it -- the layer then runs pre-masked like the ones below it, output stage inside the conv backward, instead of reading its saved output.
+def _pool_relu_pattern(bwd_had, mixk, nout1, nout2, exact, wanted, gy_rows4=True, conv_takes=True):
+    """ONE predicate for both sides: the forward asks with what it knows (wanted: any gradient at all; inference pools plainly), the
+    backward adds the gradients the had form writes, the pooled gradient's rows and what the conv plan takes."""
+    return bool(bwd_had and mixk and nout1 == 30 and nout2 == 2 and not exact and wanted and gy_rows4 and conv_takes)
+
+
+# How one ML3Layer backward runs (decided once, by _ml3_bwd_road; DESIGN s4.4 has the table):
+#   pool_grad   None (no pool) / 'expanded' (segment_bcast) / 'per_segment' (gy_seg: never expanded) / 'masked' (segment_bcast_mask)
+#   stage       'had' (inside the conv backward: parts, want_dx) / 'one_pass' (ml3_split_bwd: premasked, dz_out, mixk = it carries the
+#               Hadamard branch) / 'separate' (relu_bwd + gml_node_mix_bwd)
+#   lib_hadamard  the wide Hadamard branch runs as library GEMMs;  use_dz / relu_cols: the dz and relu hand-overs of the conv backward;
+#   conv_accum  the conv backward adds to the dx the output stage wrote;  conv: its ConvBwdRoad
+ML3BwdRoad = _collections.namedtuple('ML3BwdRoad', 'pool_grad stage parts want_dx premasked dz_out mixk lib_hadamard use_dz relu_cols '
+                                                   'conv_accum need_val want_cw want_cb learnedge conv')
+
+
+def _ml3_bwd_road(S, Fin, nout1, nout2, N, need, learnedge, has_cb, conv, exact, bwd_had, bwd_dma, chain, pool, pool_mask,
+                  chain_out_premasked, chain_in_cols, gy_rows, x_rows4):
+    """ML3BwdRoad from plain values only (no tensor, no launch).  Every hand-over (dz, relu_cols, had) rides on the one-launch 128-row
+    conv backward: without that plan none is chosen."""
+    # need: needs_input_grad of ML3LayerFunction; conv: _conv_bwd_road of (S, Fin, nout1); pool / pool_mask: the layer is pooled / its
+    # forward left the relu pattern; chain_out_premasked: the consumer applied this layer's relu to gy; chain_in_cols: relu columns of x's
+    # producer (None: no hand-over); gy_rows: (row stride, pointer % 16) of the incoming gradient; x_rows4: x has float4-readable rows
+    L = _lib.lib()
+    C = nout1 + nout2
+    mixk = nout2 > 0 and node_mix_native(Fin, nout2)
+    plan = conv.plan if conv.kind == 'one128' else None
+    want_dx, want_w3 = bool(need[0]), bool(need[6] and need[8] and need[10])
+    stage_ws = int(L.gml_ml3_split_bwd_workspace_bytes(int(N), Fin if mixk else 0, int(nout1), int(nout2) if mixk else 0))
+    # 2 nout2 <= 4 (Zinc12k.py's 30+2 layers): the Hadamard branch hands its share of dx to the conv backward as 4 numbers per row (dz)
+    # instead of writing a [N, Fin] array the conv kernel reads back
+    use_dz = bool(mixk and want_dx and not _os.environ.get('GML_NO_DZ') and _plan_takes_dz(plan, S, Fin, nout1, 2 * nout2))
+    # partial rows of gml_spectconv_bwd_had (0: the shape / the build has no fused output stage)
+    parts = 0 if (not bwd_had or bwd_dma or exact or plan is None) else int(L.gml_spectconv_bwd_had_parts(
+        int(N), int(S), int(Fin), int(nout1), int(nout2), int(want_dx), plan.max_edges, plan.max_window, plan.flags))
+    pool_grad, pre = None, bool(chain and chain_out_premasked)
+    if pool:
+        fuse = stage_ws > 0 and (mixk or nout2 == 0) and not _os.environ.get('GML_NO_POOL_FUSE')
+        pre = bool(fuse and pool_mask and _pool_relu_pattern(bwd_had, mixk, nout1, nout2, exact, want_dx and want_w3,
+                                                             _rows4_ok(*gy_rows, 0), use_dz and parts > 0))
+        pool_grad = 'masked' if pre else 'per_segment' if fuse else 'expanded'
+        if pool_grad != 'per_segment':
+            gy_rows = (C, 0)          # (the expanded gradient is a fresh [N, C] array)
+    # ZINC's 30 + 2 layers with a pre-masked gradient: the output stage runs INSIDE the conv backward (one launch, no dz array, no second
+    # pass over gy and x)
+    had = bool(parts > 0 and (use_dz or (mixk and not want_dx and x_rows4)) and pre and nout2 == 2 and want_w3 and _rows4_ok(*gy_rows, C))
+    stage = 'had' if had else 'one_pass' if (stage_ws > 0 or N == 0) else 'separate'
+    use_dz = use_dz and stage == 'one_pass'
+    # x is the lower ML3Layer's output and only this layer consumes it: its relu mask goes back inside dx
+    relu_cols = chain_in_cols if (((had and want_dx) or use_dz) and chain and chain_in_cols is not None and not bwd_dma) else 0
+    return ML3BwdRoad(pool_grad, stage, parts if had else 0, want_dx, stage == 'one_pass' and pre and _rows4_ok(*gy_rows, nout1), use_dz,
+                      mixk, nout2 > 0 and not mixk, use_dz, relu_cols, bool(stage == 'one_pass' and mixk and want_dx and not use_dz),
+                      bool(need[1] or (learnedge and any(need[2:6]))), bool(need[6]), bool(has_cb and need[7]), bool(learnedge), conv)
+
+
+# The three output-stage forms of the ML3Layer backward: each fills g[7 .. 11] (conv1.bias, fc11 / fc12 weight and bias gradients) and
+# returns what its _conv_backward call returns.  fc = (w11, b11, w12, b12).
+def _ml3_stage_had(road, csr, g, gy, gy_seg, out, x, ea, ea_t, cw, fc):
+    had = {'w': fc, 'parts': road.parts}
+    r = _conv_backward(csr, x, ea, cw, gy[:, :cw.size(2)], road.want_dx, road.need_val, True, val_t=ea_t,
+                       want_source_order=road.learnedge, relu_cols=road.relu_cols, had=had, road=road.conv)
+    dcb, g[8], g[9], g[10], g[11] = had['out']
+    g[7] = dcb if road.want_cb else None
+    return r
+
+
+def _ml3_stage_one_pass(road, csr, g, gy, gy_seg, out, x, ea, ea_t, cw, fc):
+    # one pass: relu mask, conv1.bias gradient, Hadamard branch (its dx or dz written; the conv adds to the dx / takes the dz)
+    G, dx0, g[7], g[8], g[9], g[10], g[11] = ml3_split_bwd(gy, out, cw.size(2), *((x,) + fc if road.mixk else ()), need_dx=road.want_dx,
+                                                           need_dcb=road.want_cb, dz_out=road.dz_out, gy_seg=gy_seg, premasked=road.premasked)
+    mix = (dx0, (fc[0].detach().contiguous(), fc[2].detach().contiguous())) if road.use_dz else None    # (rows of wmix from both arrays)
+    return _conv_backward(csr, x, ea, cw, G, road.want_dx, road.need_val, road.want_cw, val_t=ea_t, want_source_order=road.learnedge,
+                          dx_accum_into=dx0 if road.conv_accum else None, mix=mix, relu_cols=road.relu_cols, road=road.conv)
+
+
+def _ml3_stage_separate(road, csr, g, gy, gy_seg, out, x, ea, ea_t, cw, fc):
+    assert gy_seg is None, 'pooled gradient without the one-pass output-stage kernel'
+    N, (S, Fin, nout1), C = csr.N, cw.shape, int(gy.size(1))
+    G = relu_bwd(gy, 0, C, out, C, N, nout1)
+    r = _conv_backward(csr, x, ea, cw, G, road.want_dx, road.need_val, road.want_cw, val_t=ea_t, want_source_order=road.learnedge, road=road.conv)
+    if road.want_cb:
+        g[7] = G.sum(0)
+    if road.mixk:
+        w11, b11, w12, b12 = fc
+        ws = torch.empty(int(_lib.lib().gml_node_mix_bwd_workspace_bytes(N, Fin, C - nout1)), dtype=torch.uint8, device=x.device)
+        g[8], g[9], g[10], g[11] = torch.empty_like(w11), torch.empty_like(b11), torch.empty_like(w12), torch.empty_like(b12)
+        with _Timed('node_mix_bwd'):
+            _lib.call('gml_node_mix_bwd', _ptr(x), int(x.stride(0)), _ptr(w11), _ptr(b11), _ptr(w12), _ptr(b12), _off(gy, nout1), C,
+                      _ptr(r[0]) if road.want_dx else _ptr(None), Fin, _ptr(g[8]), _ptr(g[9]), _ptr(g[10]), _ptr(g[11]), N, Fin,
+                      C - nout1, _ptr(ws), ws.numel(), _stream(x.device))
+    return r
 
 
 class ML3LayerFunction(torch.autograd.Function):
@@ -1822,10 +1920,7 @@ class ML3LayerFunction(torch.autograd.Function):
         ctx.save_for_backward(x, val, (ea if learnedge and epos is None else None), w1, w2, w3, w4, cw, w11, b11, w12, b12, out, ea_t)
         ctx.pool_mask = None
         if ctx.pool is not None:
-            # ZINC's 30 + 2 top layer: the pool also leaves the relu pattern of every row (4 bytes) -- the backward then takes the
-            # pre-masked road with the output stage inside the conv backward instead of reading the saved output
-            if (BWD_HAD and mixk and nout1 == 30 and nout2 == 2 and out.stride(0) == 32 and not exact_mode()
-                    and any(ctx.needs_input_grad)):              # (inference: the plain pool)
+            if _pool_relu_pattern(BWD_HAD, mixk, nout1, nout2, exact_mode(), any(ctx.needs_input_grad)):
                 pooled, ctx.pool_mask = segment_sum_mask(out, pool_ptr, int(pool_mean) & 3)
             else:
                 pooled = segment_sum(out, pool_ptr, int(pool_mean) & 3)
@@ -1844,105 +1939,46 @@ class ML3LayerFunction(torch.autograd.Function):
         x, val, ea, w1, w2, w3, w4, cw, w11, b11, w12, b12, out, ea_t = ctx.saved_tensors
         csr, learnedge, nout2 = ctx.csr, ctx.learnedge, ctx.nout2
         S, Fin, nout1 = cw.shape
-        N, C = csr.N, nout1 + nout2
+        N = csr.N
         need = ctx.needs_input_grad
         gy = _f32c(gy, 'grad_out')
         if not learnedge:
             ea = val
-        g = [None] * 23
-        gy_seg = None
-        pre_top = False
-        if ctx.pool is not None:                               # gy is the POOLED gradient [B, C]
-            pptr, pseg, pmean = ctx.pool
+        if ctx.pool is not None and (ctx.pool[2] & 2) and not (ctx.pool[2] & 4):
             # GML_POOL_SKIP_LAST: the padding graph's pooled row was written, not computed -- its gradient must not reach the nodes.
             # Bit 2 (4): the caller vouches that the loss gives that row a ZERO gradient already (models.zinc_step_loss: the fused
             # head + loss ignore rows beyond the labelled ones) -- the masking launch is skipped
-            if (pmean & 2) and not (pmean & 4):
-                gy = gy * skip_last_mask(gy)
-            pmean &= 1
-            mixk_ = nout2 > 0 and node_mix_native(Fin, nout2)
-            nb_ = int(_lib.lib().gml_ml3_split_bwd_workspace_bytes(int(N), Fin if mixk_ else 0, int(nout1), int(nout2) if mixk_ else 0))
-            if nb_ > 0 and (mixk_ or nout2 == 0) and not _os.environ.get('GML_NO_POOL_FUSE'):
-                if pmean:
-                    cnt = (pptr[1:] - pptr[:-1]).clamp(min=1).to(gy.dtype).unsqueeze(1)
-                    gy = gy / cnt
-                gy_seg = pseg
-                if (ctx.pool_mask is not None and BWD_HAD and mixk_ and nout2 == 2 and need[0] and need[6] and need[8] and need[10]
-                        and gy.stride(1) == 1 and gy.stride(0) % 4 == 0 and gy.data_ptr() % 16 == 0
-                        and conv_bwd_takes_dz(csr, S, Fin, nout1, 4) and conv_bwd_had_parts(csr, S, Fin, nout1, nout2) > 0):
-                    # the pool's gradient per row with the relu pattern applied (4 + 4 bytes read, 128 written per row): the layer
-                    # then runs like the ones below it -- pre-masked, output stage inside the conv backward
-                    gy = segment_bcast_mask(gy, pseg, ctx.pool_mask, nout1)
-                    gy_seg, pre_top = None, True
-            else:
+            gy = gy * skip_last_mask(gy)
+        exact, x4 = exact_mode(), _rows4_ok(*_rows_of(x), Fin)
+        road = _ml3_bwd_road(S, Fin, nout1, nout2, N, need, learnedge, ctx.has_cb, _conv_bwd_road(csr, S, Fin, nout1, exact, x4), exact,
+                             BWD_HAD, BWD_DMA, CHAIN, ctx.pool is not None, ctx.pool_mask is not None,
+                             ctx.chain_out is not None and ctx.chain_out.premasked,
+                             ctx.chain_in.cols if ctx.chain_in is not None else None, _rows_of(gy), x4)
+        if VERBOSE:
+            _path('ml3_bwd', ' '.join('%s=%s' % (k, v.kind if k == 'conv' else int(v) if isinstance(v, bool) else v)
+                                      for k, v in zip(road._fields, road)), S, Fin, nout1)
+        # the hand-over tokens are read once: this layer's is cleared, the lower layer's set when dx leaves with its relu applied
+        if ctx.chain_out is not None:
+            ctx.chain_out.premasked = False
+        if road.relu_cols:
+            ctx.chain_in.premasked = True
+        gy_seg = ctx.pool[1] if road.pool_grad == 'per_segment' else None      # (the stage then reads gy[gy_seg[row]]: never expanded)
+        if road.pool_grad is not None:                         # gy is the POOLED gradient [B, C]
+            pptr, pseg, pmean = ctx.pool[0], ctx.pool[1], ctx.pool[2] & 1
+            if road.pool_grad == 'expanded':
                 gy = segment_bcast(gy, pptr, N, pmean)
+            elif pmean:
+                gy = gy / (pptr[1:] - pptr[:-1]).clamp(min=1).to(gy.dtype).unsqueeze(1)
+            if road.pool_grad == 'masked':
+                # the pool's gradient per row with the relu pattern applied (4 + 4 bytes read, 128 written per row)
+                gy = segment_bcast_mask(gy, pseg, ctx.pool_mask, nout1)
+        g = [None] * 23
         with torch.cuda.device(x.device):
-            need_val = need[1] or (learnedge and any(need[2:6]))
-            if not learnedge and fused_bwd_available(csr, S, Fin, nout1):
+            if not learnedge and road.conv.plan is not None:
                 ea_t = csr.to_source_order(val, cache=not val.requires_grad)   # raw supports: per-batch data (trained ones change)
-            want_cb = ctx.has_cb and need[7]
-            mixk = nout2 > 0 and node_mix_native(Fin, nout2)
-            # 2 nout2 <= 4 (Zinc12k.py's 30+2 layers): the Hadamard branch hands its share of dx to the conv backward as 4 numbers
-            # per row (dz) instead of writing a [N, Fin] array the conv kernel reads back
-            use_dz = bool(mixk and need[0] and conv_bwd_takes_dz(csr, S, Fin, nout1, 2 * nout2))
-            # the consumer of this layer's output already applied the relu mask to gy (ChainToken); read once, then cleared
-            pre = (ctx.chain_out is not None and ctx.chain_out.premasked and gy_seg is None) or pre_top
-            if ctx.chain_out is not None:
-                ctx.chain_out.premasked = False
-            # ZINC's 30 + 2 layers with a pre-masked gradient: the output stage runs INSIDE the conv backward (one launch, no dz array,
-            # no second pass over gy and x)
-            hparts = 0
-            x4 = x.stride(0) % 4 == 0 and x.stride(0) >= (Fin + 3) // 4 * 4 and x.data_ptr() % 16 == 0     # float4-readable x rows
-            if ((use_dz or (mixk and not need[0] and x4)) and pre and nout2 == 2 and need[6] and need[8] and need[10] and gy.stride(1) == 1
-                    and gy.stride(0) % 4 == 0 and gy.stride(0) >= C and gy.data_ptr() % 16 == 0):
-                hparts = conv_bwd_had_parts(csr, S, Fin, nout1, nout2, want_dx=need[0])
-            if hparts > 0:
-                had = {'w': (w11, b11, w12, b12), 'parts': hparts}
-                rc = ctx.chain_in.cols if (need[0] and ctx.chain_in is not None and not BWD_DMA) else 0
-                dx, dea, dcw, dea_src = _conv_backward(csr, x, ea, cw, gy[:, :nout1], need[0], need_val, True, val_t=ea_t,
-                                                       want_source_order=learnedge, relu_cols=rc, had=had)
-                if rc:
-                    ctx.chain_in.premasked = True
-                g[6] = dcw
-                dcb_, g[8], g[9], g[10], g[11] = had['out']
-                g[7] = dcb_ if want_cb else None
-                r = False                                    # (done: neither branch below)
-            else:
-                r = ml3_split_bwd(gy, out, nout1, x, w11, b11, w12, b12, need_dx=need[0], need_dcb=want_cb, dz_out=use_dz, gy_seg=gy_seg,
-                                  premasked=pre) \
-                    if mixk else ml3_split_bwd(gy, out, nout1, need_dcb=want_cb, gy_seg=gy_seg, premasked=pre)
-            if r is False:
-                pass
-            elif r is not None:
-                # one pass: relu mask, conv1.bias gradient, Hadamard branch (its dx written, conv adds to it)
-                G, dx0, g[7], g[8], g[9], g[10], g[11] = r
-                mix = (dx0, (w11.detach().contiguous(), w12.detach().contiguous())) if use_dz else None    # (rows of wmix from both arrays)
-                # x is the lower ML3Layer's output and only this layer consumes it: hand its relu mask back inside dx
-                rc = ctx.chain_in.cols if (use_dz and ctx.chain_in is not None and not BWD_DMA) else 0
-                dx, dea, dcw, dea_src = _conv_backward(csr, x, ea, cw, G, need[0], need_val, need[6], val_t=ea_t,
-                                                       want_source_order=learnedge,
-                                                       dx_accum_into=None if use_dz else dx0, mix=mix, relu_cols=rc)
-                if rc:
-                    ctx.chain_in.premasked = True
-                g[6] = dcw
-            else:
-                assert gy_seg is None, 'pooled gradient without the one-pass output-stage kernel'
-                G = relu_bwd(gy, 0, C, out, C, N, nout1)
-                dx, dea, dcw, dea_src = _conv_backward(csr, x, ea, cw, G, need[0], need_val, need[6], val_t=ea_t,
-                                                       want_source_order=learnedge)
-                g[6] = dcw
-                if want_cb:
-                    g[7] = G.sum(0)
-                if mixk:
-                    nbytes = int(_lib.lib().gml_node_mix_bwd_workspace_bytes(N, Fin, nout2))
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-                    g[8], g[9], g[10], g[11] = (torch.empty_like(w11), torch.empty_like(b11), torch.empty_like(w12),
-                                                torch.empty_like(b12))
-                    with _Timed('node_mix_bwd'):
-                        _lib.call('gml_node_mix_bwd', _ptr(x), int(x.stride(0)), _ptr(w11), _ptr(b11), _ptr(w12), _ptr(b12),
-                                  _off(gy, nout1), C, _ptr(dx) if need[0] else _ptr(None), Fin, _ptr(g[8]), _ptr(g[9]),
-                                  _ptr(g[10]), _ptr(g[11]), N, Fin, nout2, _ptr(ws), ws.numel(), _stream(x.device))
-            if nout2 > 0 and not mixk:                              # wide Hadamard branch: library GEMMs (see forward)
+            stage = {'had': _ml3_stage_had, 'one_pass': _ml3_stage_one_pass, 'separate': _ml3_stage_separate}[road.stage]
+            dx, dea, g[6], dea_src = stage(road, csr, g, gy, gy_seg, out, x, ea, ea_t, cw, (w11, b11, w12, b12))
+            if road.lib_hadamard:                                   # wide Hadamard branch: library GEMMs (see forward)
                 ta, tb = torch.tanh(_linear(x, w11, b11)), torch.tanh(_linear(x, w12, b12))
                 g2 = gy[:, nout1:]
                 ga, gb = g2 * tb * (1 - ta * ta), g2 * ta * (1 - tb * tb)
@@ -1953,7 +1989,7 @@ class ML3LayerFunction(torch.autograd.Function):
                     dx = dx.addmm_(ga, w11).addmm_(gb, w12)
             g[0] = dx
             if learnedge:
-                if need_val:
+                if road.need_val:
                     # the edge MLP is per-edge, so it can run in whichever order dea arrived in
                     val_in = val if ctx.val_is_source else (csr.to_source_order(val, cache=not val.requires_grad) if dea_src else val)
                     with _Timed('edge_mlp_bwd', 4 * val.numel() * 2, 60 * val.size(0) * val.size(1) ** 2):

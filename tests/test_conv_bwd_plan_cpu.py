@@ -1,8 +1,8 @@
 """The host-only queries of the fused conv backward -- gml_spectconv_bwd_group_rows / _workspace_bytes / _mix_supported / _had_parts and
 the two staging queries _stage_edges / _stage_window -- against a table written from include/gml.h and DESIGN.md s4.2 / s4.2a, not
-from the dispatch code.  functional._bwd_plan, split48_plan, conv_bwd_takes_dz and conv_bwd_had_parts choose group records, flags and
-fallbacks from these answers, so a change of the plan that moves one shows up here, without a GPU: the library loads and answers on
-the host."""
+from the dispatch code.  functional._bwd_plan, _conv_bwd_road, conv_bwd_takes_dz and _ml3_bwd_road choose group records, flags and
+fallbacks from these answers (their own table: tests/test_ml3_bwd_road_cpu.py), so a change of the plan that moves one shows up here,
+without a GPU: the library loads and answers on the host."""
 import itertools
 import os
 

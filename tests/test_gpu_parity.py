@@ -2411,6 +2411,64 @@ def test_model_step_with_the_output_stage_inside_the_conv_backward(dev):
             close(res[True][1][n], res[False][1][n], tol=2e-5, what='fused vs split output stage ' + n)
 
 
+def test_ml3_backward_runs_the_road_its_record_names(dev, monkeypatch):
+    """Four chained ZINC layers (8 supports, 32 -> 30 + 2), the top one pooled, one training step: the road records of the four
+    backward calls (functional._ml3_bwd_road, under VERBOSE one `ml3_bwd` key each) name the output stage inside the conv backward for
+    all four -- masked pool gradient on the top layer, no dx on the bottom one -- and with GML_BWD_HAD off four one-pass stages, three of
+    them pre-masked; the launches that ran are the ones the records name, and every gradient of the two settings agrees within 2e-5 of
+    its scale (the bar of test_model_step_with_the_output_stage_inside_the_conv_backward)."""
+    from gnn_matlang_amd import ML3Layer, functional as Fn
+    rng = np.random.default_rng(61)
+    torch.manual_seed(61)
+    N, S, B = 300, 8, 12
+    ei = _random_graph(rng, N, 6)
+    ei = ei[:, np.lexsort((ei[1], ei[0]))]                   # source-sorted, as SpectralDesign emits
+    eit = T(ei).to(dev)
+    layers = [ML3Layer(True, S, S, 32, 30, 2).to(dev) for _ in range(4)]
+    for lo, up in zip(layers, layers[1:]):
+        up.chain_after(lo)
+    x0, ea = torch.randn(N, 32, device=dev), torch.randn(ei.shape[1], S, device=dev)
+    ptr = torch.arange(0, N + 1, N // B, dtype=torch.int32, device=dev)
+    batch = torch.arange(N, device=dev, dtype=torch.int32) // (N // B)
+    gout = torch.randn(B, 32, device=dev)
+    ran = []
+    spy = lambda name, what: monkeypatch.setattr(Fn, name, (lambda real: lambda *a, **k: (ran.append(what(a, k)), real(*a, **k))[1])(getattr(Fn, name)))
+    spy('ml3_split_bwd', lambda a, k: ('stage', bool(k['premasked']), bool(k['dz_out']), k['gy_seg'] is not None))
+    spy('fused_conv_bwd', lambda a, k: ('conv', a[1].rows, a[6], a[10] is not None, a[11], a[12] is not None))   # rows, need_x, mix, relu_cols, had
+    spy('segment_bcast_mask', lambda a, k: ('masked pool',))
+    monkeypatch.setattr(Fn, 'VERBOSE', True)
+    res = {}
+    for on in (True, False):
+        monkeypatch.setattr(Fn, 'BWD_HAD', on)
+        for l in layers:
+            l.zero_grad()
+        Fn.PATHS.clear()
+        del ran[:]
+        h = x0
+        for l in layers[:-1]:
+            h = l(h, eit, ea)
+        (layers[-1].forward_pooled(h, eit, ea, ptr, batch) * gout).sum().backward()
+        torch.cuda.synchronize()
+        keys = sorted((k, n) for k, n in Fn.PATHS.items() if k.startswith('ml3_bwd:'))
+        res[on] = ([p.grad.clone() for l in layers for p in l.parameters()], keys, list(ran))
+    field = lambda keys, text: sum(n for k, n in keys if text + ' ' in k)
+    _, keys, launches = res[True]
+    assert sum(n for _, n in keys) == 4 and field(keys, 'stage=had') == 4 and field(keys, 'parts=3') == 4, keys
+    assert [(n, 'want_dx=1' in k, 'relu_cols=30' in k) for k, n in keys if 'pool_grad=masked ' in k] == [(1, True, True)], keys
+    assert [(n, 'relu_cols=0 ' in k, 'pool_grad=None' in k) for k, n in keys if 'want_dx=0 ' in k] == [(1, True, True)], keys
+    assert field(keys, 'conv=one128') == 4 and field(keys, 'use_dz=0') == 4
+    assert launches == [('masked pool',), ('conv', 128, True, False, 30, True), ('conv', 128, True, False, 30, True),
+                        ('conv', 128, True, False, 30, True), ('conv', 128, False, False, 0, True)], launches
+    _, keys, launches = res[False]
+    assert sum(n for _, n in keys) == 4 and field(keys, 'stage=one_pass') == 4 and field(keys, 'premasked=1') == 3, keys
+    assert [(n, 'premasked=0 ' in k, 'dz_out=1 ' in k) for k, n in keys if 'pool_grad=per_segment ' in k] == [(1, True, True)], keys
+    assert field(keys, 'relu_cols=30') == 3 and field(keys, 'use_dz=1') == 3 and field(keys, 'conv_accum=0') == 4
+    assert launches == [('stage', False, True, True), ('conv', 128, True, True, 30, False), ('stage', True, True, False), ('conv', 128, True, True, 30, False),
+                        ('stage', True, True, False), ('conv', 128, True, True, 30, False), ('stage', True, False, False), ('conv', 128, False, False, 0, False)], launches
+    for i, (a, b) in enumerate(zip(res[True][0], res[False][0])):
+        close(a, b, tol=2e-5, what='output stage inside the conv backward vs one-pass stage, parameter %d' % i)
+
+
 def test_edge_sym_pairing_with_repeated_and_one_sided_edges(dev):
     """multigraph input (an edge repeated, on one side or on both) and one-sided edges (no mirror at all): such edges are evaluated
     alone; every row of the output is still written exactly once and equals the plain kernels' bit for bit."""

@@ -39,13 +39,13 @@ def main():
     G[:, :Fout] = torch.randn(N, Fout, generator=g).to(dev)
     Gv = G[:, :Fout]
 
-    def one_launch():
-        return Fn.fused_conv_bwd(csr, val_t, x, Gv, w, True, True, True, None, None, 0)
-
     def plan(fo):
         p = Fn._bwd_plan(csr, S, Fin, fo)
-        assert p is not None and p[4] == 128, p
+        assert p is not None and p.rows == 128, p
         return p
+
+    def one_launch():
+        return Fn.fused_conv_bwd(csr, plan(Fout), val_t, x, Gv, w, True, True, True)
     halves = ((0, 16), (16, Fout))
     plans = [plan(o1 - o0) for o0, o1 in halves]
     wp = [w[:, :, o0:o1].contiguous() for o0, o1 in halves]
@@ -55,14 +55,14 @@ def main():
         dval = torch.empty(E, S, device=dev)
         dws = []
         for part, (o0, o1) in enumerate(halves):
-            flags, ginfo, gmax, nbytes, _ = plans[part]
+            p, flags = plans[part], plans[part].flags
             if part == 1:
                 flags |= _lib.GML_ACCUM | _lib.GML_DVAL_ACCUM
             dw_p = torch.empty(S, Fin, o1 - o0, device=dev)
-            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
-            _lib.call('gml_spectconv_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t), _ptr(x), int(x.stride(0)),
+            ws = torch.empty(max(p.ws_bytes, 4), dtype=torch.uint8, device=dev)
+            _lib.call('gml_spectconv_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(p.ginfo), _ptr(val_t), _ptr(x), int(x.stride(0)),
                       _off(G, o0), int(G.stride(0)), _ptr(wp[part]), _ptr(dx), Fin, _ptr(dval), _ptr(dw_p), N, S, Fin, o1 - o0,
-                      gmax[0], gmax[1], flags, _ptr(ws), ws.numel(), _stream(dev))
+                      p.max_edges, p.max_window, flags, _ptr(ws), ws.numel(), _stream(dev))
             dws.append(dw_p)
         return dx, dval, torch.cat(dws, 2)
 
@@ -82,12 +82,12 @@ def main():
     t1, t2 = time_ms(one_launch), time_ms(two_launches)
     # one NOB = 1 launch alone (the first half), for the per-pass cost
     def first_half():
-        flags, ginfo, gmax, nbytes, _ = plans[0]
+        p, flags = plans[0], plans[0].flags
         dx = torch.empty(N, Fin, device=dev); dval = torch.empty(E, S, device=dev); dw_p = torch.empty(S, Fin, 16, device=dev)
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
-        _lib.call('gml_spectconv_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(ginfo), _ptr(val_t), _ptr(x), int(x.stride(0)),
+        ws = torch.empty(max(p.ws_bytes, 4), dtype=torch.uint8, device=dev)
+        _lib.call('gml_spectconv_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(p.ginfo), _ptr(val_t), _ptr(x), int(x.stride(0)),
                   _ptr(G), int(G.stride(0)), _ptr(wp[0]), _ptr(dx), Fin, _ptr(dval), _ptr(dw_p), N, S, Fin, 16,
-                  gmax[0], gmax[1], flags, _ptr(ws), ws.numel(), _stream(dev))
+                  p.max_edges, p.max_window, flags, _ptr(ws), ws.numel(), _stream(dev))
     th = time_ms(first_half)
     q, _ = Fn.conv_cost_bwd(N, E, S, Fin, Fout, True, True)
     print('ZINC layer backward, %d graphs: N = %d rows, E = %d support edges, S = 8, Fin = 32, Fout = 30 (dX + dval + dW)' % (data.num_graphs, N, E))

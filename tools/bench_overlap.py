@@ -45,7 +45,7 @@ def edge_bwd():
 
 
 def conv_bwd():
-    return Fn.fused_conv_bwd(csr, ea_t, x, G, cw, True, True, True)
+    return Fn.fused_conv_bwd(csr, Fn._bwd_plan(csr, S, Fin, Fout), ea_t, x, G, cw, True, True, True)
 
 
 def timeit(fn, n=10):
