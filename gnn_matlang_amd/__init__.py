@@ -10,8 +10,9 @@ include/gml.h), loaded lazily with ctypes on the first forward.  No CPU fallback
 from .spect_conv import SpectConv, SpectConCatConv, ML3Layer, glorot, zeros
 from .spectral_design import SpectralDesign
 from .gat import GATConv
+from .gin import GINConv
 from .graph import GraphCSR, Batch, collate, csr_for, shard_graphs, shard_graphs_balanced
 from .dataset import DeviceDataset
 
 __all__ = ['SpectConv', 'SpectConCatConv', 'ML3Layer', 'SpectralDesign', 'GraphCSR', 'Batch', 'collate',
-           'csr_for', 'shard_graphs', 'shard_graphs_balanced', 'DeviceDataset', 'glorot', 'zeros', 'GATConv']
+           'csr_for', 'shard_graphs', 'shard_graphs_balanced', 'DeviceDataset', 'glorot', 'zeros', 'GATConv', 'GINConv']

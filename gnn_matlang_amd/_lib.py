@@ -188,6 +188,13 @@ SIGNATURES = {
     'gml_gat_bwd_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
     'gml_gat_bwd': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i32, _i32, _i32,
                                    _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    'gml_gin_supported': (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    'gml_gin_fwd': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i64,
+                                   _p]),
+    'gml_gin_dflat_floats': (_i64, [_i32, _i32, _i32, _i32]),
+    'gml_gin_bwd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    'gml_gin_bwd': (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _i32, _p, _i32, _i32, _i32,
+                                   _p, _i64, _p, _p, _sz, _p]),
 }
 
 

@@ -2245,3 +2245,134 @@ class GATConvFunction(torch.autograd.Function):
             dx = torch.matmul(dxl, weight) if ctx.needs_input_grad[0] else None
         sl, sr = ctx.att_shapes
         return dx, None, dw, datt[0].reshape(sl), datt[1].reshape(sr), datt[2] if ctx.has_bias else None, None
+
+
+# ---------------------------------------------------------------------------- GIN layer (csrc/gml_gin.hip)
+GIN_ACTS = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2}
+
+
+def _gin_act_id(act):
+    if act not in GIN_ACTS:
+        raise ValueError("act: None, 'relu' or 'tanh', got %r" % (act,))
+    return GIN_ACTS[act]
+
+
+def gin_nn_linears(nn):
+    """the Linears of a GINConv's nn when it is torch.nn.Sequential(Linear) or Sequential(Linear, ReLU, Linear) -- the two forms of the
+    experiment scripts, which the fused layer serves --, else None"""
+    if not isinstance(nn, torch.nn.Sequential) or len(nn) not in (1, 3):
+        return None
+    mods = list(nn)
+    if type(mods[0]) is not torch.nn.Linear:
+        return None
+    if len(mods) == 1:
+        return [mods[0]]
+    if type(mods[1]) is not torch.nn.ReLU or type(mods[2]) is not torch.nn.Linear or mods[2].in_features != mods[0].out_features:
+        return None
+    return [mods[0], mods[2]]
+
+
+def gin_conv_supported(x, Fh, Fout=None):
+    """the fused GIN layer (GINConvFunction) serves this input: float32 [N >= 1, Fin] on the device, nn = Linear(Fin, Fh) (Fout None)
+    or Linear(Fin, Fh) - ReLU - Linear(Fh, Fout), every width in 1 .. 64 (gml_gin_supported) -- every 64-wide GinNet of the experiment
+    scripts.  Any number of edges, any degree.  Everything else (the 200-wide GinNets of ptc / proteins / enzymes_contfeat among it)
+    takes the composition gin_conv_torch.  GML_NO_GIN_FUSED=1 sends every shape there.  No shape inside the range is gated onto the
+    composition: one layer forward + backward, fused 90th percentile against the composition's 10th, ms (tools/bench_gin.py,
+    profiles/gin.json, DESIGN s4.21): ZINC-like batch of 64 0.30 against 0.50 (25 -> 64 -> 64) and 0.30 against 0.50 (64 -> 64 -> 64),
+    mutag batch 16 0.30 against 0.49 and 0.29 against 0.49, sr25 at depth 1 0.28 against 0.39 and 0.27 against 0.38, the 900-node grid
+    0.28 against 0.38 (1 -> 64 -> 64) and 0.15 against 0.38, 500 k rows 1.65 against 3.44 and 2.01 against 4.27."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1):
+        return False
+    if _os.environ.get('GML_NO_GIN_FUSED'):
+        return False
+    depth = 1 if Fout is None else 2
+    return bool(_lib.lib().gml_gin_supported(int(x.size(1)), int(Fh), int(Fout or 0), depth))
+
+
+def gin_conv_torch(x, edge_index, eps, linears, act=None):
+    """GINConv (torch_geometric 1.6.1) composed from torch ops, on any device and dtype: the road of every shape outside
+    gin_conv_supported and the opponent of tools/bench_gin.py.  x [N, Fin], edge_index [2, E] = (source j, target i), eps a tensor of
+    one element, linears = [(weight, bias or None)] or [(w1, b1), (w2, b2)] with a relu between the two.
+        h = index_add over the targets of x[source], then + (1 + eps) x;  out = act(nn(h))
+    Every edge occurrence counts, self loops included."""
+    src, dst = edge_index[0], edge_index[1]
+    h = torch.zeros_like(x).index_add_(0, dst, x[src]) + (1 + eps) * x
+    if len(linears) not in (1, 2):
+        raise ValueError('linears: one or two (weight, bias) pairs')
+    out = _linear(h, linears[0][0], linears[0][1])
+    if len(linears) == 2:
+        out = _linear(torch.relu(out), linears[1][0], linears[1][1])
+    a = _gin_act_id(act)
+    return torch.relu(out) if a == 1 else (torch.tanh(out) if a == 2 else out)
+
+
+class GINConvFunction(torch.autograd.Function):
+    """y = act(nn((1 + eps) x + sum of the neighbours)) over a GraphCSR of the (source, target) edges, nn = Linear (w2 None) or
+    Linear - ReLU - Linear: ONE launch (gml_gin_fwd); the aggregate h [N, Fin] and the hidden t [N, Fh] are kept for the backward.
+    Backward: gml_gin_bwd, three launches (row pass, source-view aggregation, fold), two when x needs no gradient (dx = NULL: the
+    first layer of most models) -> dx, deps, dW1, db1, dW2, db2.  eps is read from device memory inside the kernels.  No atomics, no
+    host read: bit-reproducible, capturable.  Plain fp32 (exact_products() changes nothing)."""
+
+    @staticmethod
+    def forward(ctx, x, csr, eps, w1, b1, w2, b2, act=None):
+        x, w1 = _f32c(x, 'x'), _f32c(w1, 'w1')
+        eps = _f32c(eps, 'eps')
+        depth = 1 if w2 is None else 2
+        if depth == 1 and b2 is not None:
+            raise ValueError('GIN layer: b2 without w2')
+        if x.dim() != 2 or w1.dim() != 2 or w1.size(1) != x.size(1) or eps.numel() != 1:
+            raise ValueError('GIN layer: x [N, Fin], eps [1], w1 [Fh, Fin] expected')
+        N, Fin, Fh = int(x.size(0)), int(x.size(1)), int(w1.size(0))
+        Fout = 0
+        if depth == 2:
+            w2 = _f32c(w2, 'w2')
+            if w2.dim() != 2 or w2.size(1) != Fh:
+                raise ValueError('GIN layer: w2 [Fout, Fh] expected')
+            Fout = int(w2.size(0))
+        if csr.N != N:
+            raise ValueError('GraphCSR was built for %d nodes, x has %d rows' % (csr.N, N))
+        b1 = None if b1 is None else _f32c(b1, 'b1')
+        b2 = None if b2 is None else _f32c(b2, 'b2')
+        a = _gin_act_id(act)
+        dev = x.device
+        Fo = Fout if depth == 2 else Fh
+        with torch.cuda.device(dev):
+            h = torch.empty(N, Fin, dtype=torch.float32, device=dev)
+            t = torch.empty(N, Fh, dtype=torch.float32, device=dev) if depth == 2 else None
+            y = torch.empty(N, Fo, dtype=torch.float32, device=dev)
+            flops = 2 * N * (Fin * Fh + Fh * Fout)
+            with _Timed('gin_fwd', q=4 * ((csr.E + N) * Fin + N * (Fin + (Fh if depth == 2 else 0) + Fo)), f=flops):
+                _lib.call('gml_gin_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(x), Fin, N, csr.E, Fin, _ptr(eps), _ptr(w1), _ptr(b1), Fh,
+                          _ptr(w2), _ptr(b2), Fout, depth, a, _ptr(h), Fin, _ptr(t), Fh, _ptr(y), Fo, _stream(dev))
+        ctx.csr, ctx.act, ctx.dims = csr, a, (N, Fin, Fh, Fout, depth)
+        ctx.has_b = (b1 is not None, b2 is not None)
+        ctx.eps_shape = eps.shape
+        ctx.save_for_backward(x, eps, w1, w2, h, t, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, eps, w1, w2, h, t, y = ctx.saved_tensors
+        csr, (N, Fin, Fh, Fout, depth) = ctx.csr, ctx.dims
+        dev = x.device
+        dy = _f32c(dy, 'grad of y')
+        Fo = Fout if depth == 2 else Fh
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+            flat = torch.empty(int(L.gml_gin_dflat_floats(Fin, Fh, Fout, depth)), dtype=torch.float32, device=dev)
+            nws = int(L.gml_gin_bwd_workspace_bytes(N, Fin, Fh, Fout, depth))
+            ws = torch.empty(max(nws // 4, 4), dtype=torch.float32, device=dev)
+            with _Timed('gin_bwd'):
+                _lib.call('gml_gin_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(x), Fin, _ptr(h), Fin, _ptr(t), Fh, _ptr(y), Fo, _ptr(dy),
+                          Fo, N, csr.E, Fin, _ptr(eps), _ptr(w1), Fh, _ptr(w2), Fout, depth, ctx.act, _ptr(dx), Fin, _ptr(flat), _ptr(ws),
+                          ws.numel() * 4, _stream(dev))
+        o1 = Fh * Fin
+        o2 = o1 + Fh
+        dw1, db1 = flat[:o1].view(Fh, Fin), flat[o1:o2]
+        dw2 = db2 = None
+        if depth == 2:
+            o3 = o2 + Fout * Fh
+            dw2, db2 = flat[o2:o3].view(Fout, Fh), flat[o3:o3 + Fout]
+        hb1, hb2 = ctx.has_b
+        return dx, None, flat[-1:].reshape(ctx.eps_shape), dw1, db1 if hb1 else None, dw2, db2 if hb2 else None, None

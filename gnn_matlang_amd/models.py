@@ -920,6 +920,113 @@ def mnist75_gat(ninp=3, dropout=0.1):      # mnist75.py:119-148 (8 | 16 | 16, el
     return GAT(ninp, (8, 16, 16), act='elu', pool='mean', head='bn_mlp', hidden=32, nclass=10, dropout=dropout)
 
 
+class GIN(_Stack):
+    """The GinNet of the PyG experiment scripts (Zinc12k.py:97-143, sr25.py:74-105, ...) as one class: conv1 .. convK =
+    gin.GINConv(nn_i, eps, train_eps=True) over the raw adjacency with nn_i = Sequential(Linear(., width)) (depth 1) or
+    Sequential(Linear(., width), ReLU(), Linear(width, width)) (depth 2), x <- act(conv_i x) with act 'relu' or 'tanh' applied inside
+    the layer's launch; bn_after, nbn, dropout, pool: as _Stack has them; head: a name of _HEADS (the table at _Head).
+    eps: a number (every layer starts from it), or 'uniform': one np.random.uniform() per layer, all drawn BEFORE the first Linear is
+    built, as the expressivity scripts do (sr25.py:78-80).  share_nn = {4: 3}: conv4 is built on conv3's nn (enzymes.py:116-117 hands
+    nn3 to conv4; nn4 is never attached), so a state_dict carries conv3.nn.* and conv4.nn.* for the same tensors.
+    Same attribute names as the scripts, so their state_dicts load.  A padded static batch (batch_padded(..., adjacency=True)) works:
+    a padding node carries only self loops, which count like any edge, so it reaches itself alone; the pools skip the padding graph and
+    the bnI get the row validity.  Each layer takes the fused road where functional.gin_conv_supported allows (widths up to 64), else
+    functional.gin_conv_torch; _road='torch' forces the composition."""
+
+    _HEADS = dict(mlp=_MLP, tanh=_TANH, log_softmax=_LOG_SOFTMAX, node=_NODE)
+
+    def __init__(self, ninp, width, nlayers, depth=2, act='relu', eps=0.0, share_nn=None, bn_after=(), nbn=0, dropout=0.0, pool='add',
+                 head='mlp', hidden=0, nclass=1):
+        super().__init__()
+        from .gin import GINConv
+        width, nlayers, share_nn = int(width), int(nlayers), dict(share_nn or {})
+        if act not in ('tanh', 'relu') or head not in self._HEADS or depth not in (1, 2):
+            raise ValueError('act: tanh / relu; depth: 1 / 2; head: %s' % ' / '.join(self._HEADS))
+        if any(not 1 <= int(src) < int(i) <= nlayers for i, src in share_nn.items()):
+            raise ValueError('share_nn = {layer: an earlier layer whose nn it is built on}')
+        if eps == 'uniform':
+            import numpy as np
+            eps0 = [float(np.random.uniform()) for _ in range(nlayers)]       # (r1, r2, r3 first: sr25.py:78-80)
+        else:
+            eps0 = [float(eps)] * nlayers
+        self.act, self.width, self.depth, self.share_nn = act, width, int(depth), {int(i): int(s) for i, s in share_nn.items()}
+        self._init_stack(nlayers, bn_after, nbn, width, pool, head)
+        fin = int(ninp)
+        for i in range(1, nlayers + 1):
+            if i in share_nn:
+                nn = getattr(self, 'conv%d' % share_nn[i]).nn
+            elif depth == 1:
+                nn = torch.nn.Sequential(torch.nn.Linear(fin, width))
+            else:
+                nn = torch.nn.Sequential(torch.nn.Linear(fin, width), torch.nn.ReLU(), torch.nn.Linear(width, width))
+            setattr(self, 'conv%d' % i, GINConv(nn, eps=eps0[i - 1], train_eps=True))
+            if i <= nbn:                                   # (the scripts declare convI, then bnI: the same state_dict key order)
+                self._modules['bn%d' % i] = self._modules.pop('bn%d' % i)
+            fin = width
+        self._init_head(width, hidden, nclass, dropout)
+
+    def _layers(self, x, graph, _road):
+        road = 'torch' if _road == 'torch' else None
+        return lambda i, x: getattr(self, 'conv%d' % i)(x, graph, act=self.act, _road=road)
+
+
+def sr25_gin(ninp=2):                      # sr25.py:74-105 (3 x Linear 64, eps from np.random.uniform(), tanh, add-pool, tanh(fc1: 64 -> 10))
+    return GIN(ninp, 64, 3, depth=1, act='tanh', eps='uniform', pool='add', head='tanh', nclass=10)
+
+
+def graph8c_gin(ninp=2):                   # graph8c.py:74-105 (the sr25 shapes)
+    return GIN(ninp, 64, 3, depth=1, act='tanh', eps='uniform', pool='add', head='tanh', nclass=10)
+
+
+def exp_gin(ninp=2):                       # exp_iso.py:76-107 (the sr25 shapes)
+    return GIN(ninp, 64, 3, depth=1, act='tanh', eps='uniform', pool='add', head='tanh', nclass=10)
+
+
+def exp_classify_gin(ninp=2):              # exp_classify.py:85-117 (3 x Linear 64, eps from np.random.uniform(), relu, mean-pool, relu(fc1: 64 -> 10), fc2: 10 -> 1)
+    return GIN(ninp, 64, 3, depth=1, act='relu', eps='uniform', pool='mean', head='mlp', hidden=10)
+
+
+def zinc_gin(ninp=25):                     # Zinc12k.py:97-143 (4 x L-ReLU-L 64, relu, bn1-4 after the layers, add-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
+    return GIN(ninp, 64, 4, bn_after=(1, 2, 3, 4), nbn=4, pool='add', head='mlp', hidden=32)
+
+
+def counting_gin(ninp=2):                  # counting.py:124-159 (5 x L-ReLU-L 64, relu, add-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
+    return GIN(ninp, 64, 5, pool='add', head='mlp', hidden=32)
+
+
+def mutag_gin(ninp=8):                     # mutag.py:74-111 (3 x L-ReLU-L 64, relu, bn1-3, mean-pool, relu(fc1: 64 -> 10), fc2: 10 -> 1)
+    return GIN(ninp, 64, 3, bn_after=(1, 2, 3), nbn=3, pool='mean', head='mlp', hidden=10)
+
+
+def freqclass_gin(ninp=1, dropout=0.2):    # freqclass.py:90-129 (3 x L-ReLU-L 64, relu, dropout 0.2, bn1-3, mean-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
+    return GIN(ninp, 64, 3, bn_after=(1, 2, 3), nbn=3, dropout=dropout, pool='mean', head='mlp', hidden=32)
+
+
+def filtering_gin(ninp=1):                 # filtering.py:86-111 (3 x L-ReLU-L 64, relu, node-level: fc2: 64 -> 1 on every node, no pooling)
+    return GIN(ninp, 64, 3, pool=None, head='node', nclass=1)
+
+
+def enzymes_gin(ninp=4, dropout=0.1):
+    """enzymes.py:100-148: 4 x L-ReLU-L 64 with conv4 built on nn3 (:116-117; nn4 is never attached), relu, dropout 0.1, bn1-4,
+    (mean, max) pools, log_softmax(fc2: 128 -> 6), no fc1"""
+    return GIN(ninp, 64, 4, share_nn={4: 3}, bn_after=(1, 2, 3, 4), nbn=4, dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=6)
+
+
+def ptc_gin(ninp=20, dropout=0.2):
+    """ptc.py:95-126: 2 x L-ReLU-L 200, relu, dropout 0.2, bn1-2, (add, max) pools, log_softmax(fc2: 400 -> 2).  200 wide: beyond the
+    fused layer (widths up to 64), so both layers run on functional.gin_conv_torch; bn1 / bn2 are beyond the masked BatchNorm kernel, so
+    a padded static batch in TRAINING raises BatchNorm1d's NotImplementedError; plain batches and evaluation run."""
+    return GIN(ninp, 200, 2, bn_after=(1, 2), nbn=2, dropout=dropout, pool=('add', 'max'), head='log_softmax', nclass=2)
+
+
+def proteins_gin(ninp=4, dropout=0.2):     # proteins.py:31-63 (the ptc shapes and roads)
+    return GIN(ninp, 200, 2, bn_after=(1, 2), nbn=2, dropout=dropout, pool=('add', 'max'), head='log_softmax', nclass=2)
+
+
+def enzymes_contfeat_gin(ninp=22, dropout=0.2):    # enzymes_contfeat.py:104-137 (the ptc shapes and roads with (mean, max) pools, fc2: 400 -> 6)
+    return GIN(ninp, 200, 2, bn_after=(1, 2), nbn=2, dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=6)
+
+
 def _graph_valid(valid, data):
     """valid, or the graph_valid [B] of a padded static batch, or None (a plain batch)"""
     return valid if valid is not None else getattr(data, 'graph_valid', None)

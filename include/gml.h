@@ -1097,6 +1097,41 @@ int gml_gat_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* rowptr
                 int32_t C, int32_t act, float* dxl, int64_t lddxl, float* datt_l, float* datt_r, float* dbias, void* ws,
                 size_t ws_bytes, gml_stream_t stream);
 
+/* GIN (the 1-WL baseline of every PyG experiment script, e.g. Zinc12k.py:97-143, sr25.py:74-105): GINConv of torch_geometric 1.6.1
+ * with its nn = Sequential(Linear) (depth 1) or Sequential(Linear, ReLU, Linear) (depth 2) and the script's activation in one launch
+ * (csrc/gml_gin.hip).  (rowptr, col) lists the sources j of every target i (a GraphCSR's target view), (rowptr_t, col_t) the targets
+ * of every source.  EVERY edge occurrence counts, a self loop included; nothing is dropped or added.
+ *
+ * gml_gin_fwd: per target row i
+ *     h[i] = sum over the row's edges (j -> i) in CSR order of x[j], then + (1 + eps) x[i]          (this order is the contract)
+ *     depth 2: t = relu(W1 h + b1) [N, Fh], y = act(W2 t + b2) [N, Fout];   depth 1: y = act(W1 h + b1) [N, Fh]
+ *   act 0 none / 1 relu / 2 tanh; w1 [Fh, Fin], w2 [Fout, Fh] dense row-major; b1, b2 optional (NULL).  eps is a DEVICE pointer to
+ *   one float, read inside the kernel: a captured launch sees the optimiser's update on replay.  h (rows of ldh) and, at depth 2, t
+ *   (rows of ldt) are the backward's inputs.  With depth 1, w2, b2, t, ldt and Fout are not read.  Products: the bias first, then k
+ *   ascending fmaf.  Rows are chunked: any degree.  ONE launch.
+ * gml_gin_bwd: dy (rows of lddy) -> dx (rows of lddx; NULL: not wanted, the source view is not walked) and
+ *   dflat = [dW1 Fh x Fin | db1 Fh | dW2 Fout x Fh | db2 Fout (depth 2 only) | deps 1], gml_gin_dflat_floats floats.
+ *     g2 = dy act'(y) (act' from y alone);  depth 2: dW2 = g2^T t, db2 = sum g2, g1 = (g2 W2) [t > 0];  depth 1: g1 = g2
+ *     dW1 = g1^T h, db1 = sum g1, dh = g1 W1, deps = sum_i <dh[i], x[i]>
+ *     dx[j] = (1 + eps) dh[j], then + dh[i] over the edges (j -> i) in source-view CSR order
+ *   THREE launches (TWO with dx == NULL): the row pass (per-workgroup partials of dflat over contiguous row ranges, rows ascending;
+ *   dh to the workspace), the source-view aggregation, the fold of the partials in ascending workgroup order.  No atomics: every sum
+ *   has a fixed order, two runs give the same bits.
+ * Range: depth in {1, 2}, 1 <= Fin, Fh, Fout <= 64 (gml_gin_supported; Fout is not read at depth 1), any N >= 1, E >= 0 (below
+ * 2^31), any degree, rows of any stride >= their width (no alignment beyond a float's); else GML_E_UNSUPPORTED.  A workspace below
+ * gml_gin_bwd_workspace_bytes: GML_E_WORKSPACE.  Nothing is launched on any error.  Plain fp32 fmaf / tanhf.  No allocation, no host
+ * read: capturable on one stream. */
+int gml_gin_supported(int32_t Fin, int32_t Fh, int32_t Fout, int32_t depth);
+int gml_gin_fwd(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, int64_t N, int64_t E, int32_t Fin, const float* eps,
+                const float* w1, const float* b1, int32_t Fh, const float* w2, const float* b2, int32_t Fout, int32_t depth, int32_t act,
+                float* h, int64_t ldh, float* t, int64_t ldt, float* y, int64_t ldy, gml_stream_t stream);
+int64_t gml_gin_dflat_floats(int32_t Fin, int32_t Fh, int32_t Fout, int32_t depth);
+size_t gml_gin_bwd_workspace_bytes(int64_t N, int32_t Fin, int32_t Fh, int32_t Fout, int32_t depth);
+int gml_gin_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* x, int64_t ldx, const float* h, int64_t ldh, const float* t,
+                int64_t ldt, const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t N, int64_t E, int32_t Fin, const float* eps,
+                const float* w1, int32_t Fh, const float* w2, int32_t Fout, int32_t depth, int32_t act, float* dx, int64_t lddx,
+                float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
