@@ -11,8 +11,9 @@ from .spect_conv import SpectConv, SpectConCatConv, ML3Layer, glorot, zeros
 from .spectral_design import SpectralDesign
 from .gat import GATConv
 from .gin import GINConv
+from .cheb import ChebConv
 from .graph import GraphCSR, Batch, collate, csr_for, shard_graphs, shard_graphs_balanced
 from .dataset import DeviceDataset
 
 __all__ = ['SpectConv', 'SpectConCatConv', 'ML3Layer', 'SpectralDesign', 'GraphCSR', 'Batch', 'collate',
-           'csr_for', 'shard_graphs', 'shard_graphs_balanced', 'DeviceDataset', 'glorot', 'zeros', 'GATConv', 'GINConv']
+           'csr_for', 'shard_graphs', 'shard_graphs_balanced', 'DeviceDataset', 'glorot', 'zeros', 'GATConv', 'GINConv', 'ChebConv']

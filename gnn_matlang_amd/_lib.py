@@ -195,6 +195,13 @@ SIGNATURES = {
     'gml_gin_bwd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32]),
     'gml_gin_bwd': (ctypes.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _i32, _p, _i32, _i32, _i32,
                                    _p, _i64, _p, _p, _sz, _p]),
+    'gml_cheb_supported': (ctypes.c_int, [_i32, _i32, _i32]),
+    'gml_cheb_norm': (ctypes.c_int, [_p, _p, _p, _p, _i64, ctypes.c_float, _i64, _i64, _p, _p]),
+    'gml_cheb_fwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p]),
+    'gml_cheb_dflat_floats': (_i64, [_i32, _i32, _i32]),
+    'gml_cheb_bwd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
+    'gml_cheb_bwd': (ctypes.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _i32, _i32, _i32, _p, _i64, _p,
+                                    _p, _sz, _p]),
 }
 
 

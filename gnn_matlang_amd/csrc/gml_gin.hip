@@ -18,24 +18,12 @@
 //             S  source view: dx[j] = (1 + eps) dh[j], then + dh[i] over the edges (j -> i) in source-view CSR order
 //             F  fold of the partials in ascending workgroup order -> dflat
 // No atomics; every sum has one order.  Plain fp32 fmaf / tanhf.  Column indices outside [0, N) are skipped.
-#include "gml_common.h"
+#include "gml_img64.h"
 
-#define GIN_W 64            // the widest layer; the row length of every LDS image and tile
-#define GIN_TR 32           // rows of a tile (8 per wave)
-#define GIN_RPW 8
+#define GIN_W GML_I64_W
+#define GIN_TR GML_I64_TR
+#define GIN_RPW GML_I64_RPW
 #define GIN_MAXWG 768       // workgroups of the forward and the row pass (3 per CU)
-
-static __device__ __forceinline__ float gin_act(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.f);
-    if (act == 2) return tanhf(v);
-    return v;
-}
-// act'(pre-activation) as a function of y = act(pre-activation)
-static __device__ __forceinline__ float gin_dact(float y, int act) {
-    if (act == 1) return y > 0.f ? 1.f : 0.f;
-    if (act == 2) return 1.f - y * y;
-    return 1.f;
-}
 
 // one (row, column) of the aggregation over a CSR view: SELF_FIRST ? e1 src[row] + sum : sum + e1 src[row], the sum in CSR order
 template <bool SELF_FIRST>
@@ -62,30 +50,6 @@ static __device__ __forceinline__ float gin_gather(const int32_t* __restrict__ r
     return SELF_FIRST ? acc : fmaf(e1, self, acc);
 }
 
-// acc[r] += sum over k < K4 (ascending) of a[(8 wave + r) 64 + k] w[k 64 + lane]: a = a tile (broadcast reads), w = an image
-static __device__ __forceinline__ void gin_prod8(const float* a, const float* w, int K4, int wave, int lane, float (&acc)[GIN_RPW]) {
-    const float* ar = a + wave * GIN_RPW * GIN_W;
-    for (int k = 0; k < K4; k += 4) {
-        const float w0 = w[k * GIN_W + lane], w1 = w[(k + 1) * GIN_W + lane], w2 = w[(k + 2) * GIN_W + lane], w3 = w[(k + 3) * GIN_W + lane];
-#pragma unroll
-        for (int r = 0; r < GIN_RPW; ++r) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(ar + r * GIN_W + k);
-            acc[r] = fmaf(v.w, w3, fmaf(v.z, w2, fmaf(v.y, w1, fmaf(v.x, w0, acc[r]))));
-        }
-    }
-}
-
-// img[a 64 + b] = TRANSPOSE ? w[b ldw + a] : w[a ldw + b] for a < na, b < nb, 0 elsewhere (w: [rows][ldw] row-major, dense)
-template <bool TRANSPOSE>
-static __device__ __forceinline__ void gin_load_image(float* img, const float* __restrict__ w, int na, int nb, int ldw) {
-    for (int e = threadIdx.x; e < GIN_W * GIN_W; e += 256) {
-        const int a = e / GIN_W, b = e % GIN_W;
-        float v = 0.f;
-        if (w && a < na && b < nb) v = TRANSPOSE ? w[b * ldw + a] : w[a * ldw + b];
-        img[e] = v;
-    }
-}
-
 static __global__ __launch_bounds__(256) void gin_k_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                         const float* __restrict__ x, int64_t ldx, int64_t N, int Fin, int gp,
                                                         const float* __restrict__ eps, const float* __restrict__ w1,
@@ -98,8 +62,8 @@ static __global__ __launch_bounds__(256) void gin_k_fwd(const int32_t* __restric
     __shared__ __attribute__((aligned(16))) float hs[GIN_TR * GIN_W];
     __shared__ __attribute__((aligned(16))) float ts[GIN_TR * GIN_W];
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE;
-    gin_load_image<true>(w1s, w1, Fin, Fh, Fin);
-    if (depth == 2) gin_load_image<true>(w2s, w2, Fh, Fout, Fh);
+    gml_i64_load_image<true>(w1s, w1, Fin, Fh, Fin);
+    if (depth == 2) gml_i64_load_image<true>(w2s, w2, Fh, Fout, Fh);
     const float e1 = 1.f + eps[0];
     const int rpp = 64 / gp < GIN_RPW ? 64 / gp : GIN_RPW;                  // rows of one gather pass
     const int sub = lane / gp, c = lane % gp;
@@ -124,7 +88,7 @@ static __global__ __launch_bounds__(256) void gin_k_fwd(const int32_t* __restric
         float acc[GIN_RPW];
 #pragma unroll
         for (int r = 0; r < GIN_RPW; ++r) acc[r] = bias1;
-        gin_prod8(hs, w1s, K1, wave, lane, acc);
+        gml_i64_prod8(hs, w1s, K1, wave, lane, acc);
         if (depth == 2) {
 #pragma unroll
             for (int r = 0; r < GIN_RPW; ++r) {
@@ -134,13 +98,13 @@ static __global__ __launch_bounds__(256) void gin_k_fwd(const int32_t* __restric
                 acc[r] = bias2;
             }
             __syncthreads();
-            gin_prod8(ts, w2s, K2, wave, lane, acc);
+            gml_i64_prod8(ts, w2s, K2, wave, lane, acc);
         }
         const int Fo = depth == 2 ? Fout : Fh;
         if (lane < Fo) {
 #pragma unroll
             for (int r = 0; r < GIN_RPW; ++r)
-                if (r0 + r < N) y[(r0 + r) * ldy + lane] = gin_act(acc[r], act);
+                if (r0 + r < N) y[(r0 + r) * ldy + lane] = gml_i64_act(acc[r], act);
         }
     }
 }
@@ -158,8 +122,8 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_r(const float* __restric
     __shared__ __attribute__((aligned(16))) float g1d[GIN_TR * GIN_W];
     __shared__ __attribute__((aligned(16))) float as[GIN_TR * GIN_W];       // t, then h
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE, tid = threadIdx.x;
-    gin_load_image<false>(w1s, w1, Fh, Fin, Fin);
-    if (depth == 2) gin_load_image<false>(w2s, w2, Fout, Fh, Fh);
+    gml_i64_load_image<false>(w1s, w1, Fh, Fin, Fin);
+    if (depth == 2) gml_i64_load_image<false>(w2s, w2, Fout, Fh, Fh);
     float* g1s = depth == 2 ? g1d : g2s;
     const int Fo = depth == 2 ? Fout : Fh;                                  // the width of y
     const int KO = (Fo + 3) & ~3, KH = (Fh + 3) & ~3;
@@ -175,7 +139,7 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_r(const float* __restric
             const int64_t row = r0 + r;
             const bool on = row < N;
             float g = 0.f;
-            if (on && lane < Fo) g = dy[row * lddy + lane] * gin_dact(y[row * ldy + lane], act);
+            if (on && lane < Fo) g = dy[row * lddy + lane] * gml_i64_dact(y[row * ldy + lane], act);
             g2s[(wave * GIN_RPW + r) * GIN_W + lane] = g;
             float a = 0.f;
             if (depth == 2) {
@@ -203,7 +167,7 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_r(const float* __restric
             float acc[GIN_RPW];
 #pragma unroll
             for (int r = 0; r < GIN_RPW; ++r) acc[r] = 0.f;
-            gin_prod8(g2s, w2s, KO, wave, lane, acc);
+            gml_i64_prod8(g2s, w2s, KO, wave, lane, acc);
 #pragma unroll
             for (int r = 0; r < GIN_RPW; ++r)
                 g1d[(wave * GIN_RPW + r) * GIN_W + lane] = as[(wave * GIN_RPW + r) * GIN_W + lane] > 0.f ? acc[r] : 0.f;
@@ -231,7 +195,7 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_r(const float* __restric
         float acc[GIN_RPW];
 #pragma unroll
         for (int r = 0; r < GIN_RPW; ++r) acc[r] = 0.f;
-        gin_prod8(g1s, w1s, KH, wave, lane, acc);                           // dh[r][k] = sum_o g1[r][o] W1[o][k]
+        gml_i64_prod8(g1s, w1s, KH, wave, lane, acc);                           // dh[r][k] = sum_o g1[r][o] W1[o][k]
         if (lane < Fin) {
 #pragma unroll
             for (int r = 0; r < GIN_RPW; ++r) {

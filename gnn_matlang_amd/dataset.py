@@ -57,6 +57,7 @@ class DeviceDataset(object):
     def __init__(self, x, node_ptr, edge_index, edge_ptr, edge_index2, edge_ptr2, edge_attr2, y):
         self.x, self.node_ptr, self.edge_index, self.edge_ptr = x, node_ptr, edge_index, edge_ptr
         self.edge_index2, self.edge_ptr2, self.edge_attr2, self.y = edge_index2, edge_ptr2, edge_attr2, y
+        self.graph_fields = {}                                 # name -> float32 [G]: one value per graph (from_graphs(graph_fields=))
 
     def __len__(self):
         return int(self.node_ptr.numel() - 1)
@@ -69,13 +70,31 @@ class DeviceDataset(object):
         def ptr(p):
             return torch.cat([(p[:-1].view(1, -1) + k * p[-1]).reshape(-1), (p[-1:] * reps)])
         two = lambda t: t.repeat(1, reps) if t is not None else None
-        return DeviceDataset(self.x.repeat(reps, 1), ptr(self.node_ptr), two(self.edge_index), ptr(self.edge_ptr), two(self.edge_index2),
-                             ptr(self.edge_ptr2) if self.edge_ptr2 is not None else None,
-                             self.edge_attr2.repeat(reps, 1) if self.edge_attr2 is not None else None, self.y.repeat(reps))
+        out = DeviceDataset(self.x.repeat(reps, 1), ptr(self.node_ptr), two(self.edge_index), ptr(self.edge_ptr), two(self.edge_index2),
+                            ptr(self.edge_ptr2) if self.edge_ptr2 is not None else None,
+                            self.edge_attr2.repeat(reps, 1) if self.edge_attr2 is not None else None, self.y.repeat(reps))
+        out.graph_fields = dict((k, v.repeat(reps)) for k, v in self.graph_fields.items())
+        return out
+
+    def _graph_fields(self, ids, padded=False):
+        """the graph fields of the graphs ``ids`` (torch indexing of static shape, no host read).  padded: B + 1 entries like y; absent
+        slots (ids == len(self)) and the padding graph hold the field's neutral value: 2.0 for lmax (torch_geometric's lambda_max of
+        the 'sym' Laplacian when none is given), 0 for any other field."""
+        out = {}
+        for k, v in self.graph_fields.items():
+            if not padded:
+                out[k] = v[ids]
+                continue
+            G = len(self)
+            fill = torch.full((1,), 2.0 if k == 'lmax' else 0.0, dtype=v.dtype, device=v.device)
+            out[k] = torch.cat([torch.where(ids < G, v[ids.clamp(max=G - 1)], fill.expand(ids.numel())), fill])
+        return out
 
     @staticmethod
-    def from_graphs(graphs, device):
-        """graphs: dicts with x, edge_index, y and (optionally) edge_index2 / edge_attr2, as ``SpectralDesign`` returns."""
+    def from_graphs(graphs, device, graph_fields=()):
+        """graphs: dicts with x, edge_index, y and (optionally) edge_index2 / edge_attr2, as ``SpectralDesign`` returns.
+        graph_fields: keys that hold ONE float per graph (('lmax',), which the ChebNets read), kept as float32 [G] in the dict
+        ``graph_fields`` and carried into every batch as Batch.<key>.  Nothing is carried unless it is named here."""
         graphs = list(graphs)
         xs = [np.asarray(g['x'], dtype=np.float32) for g in graphs]
         nptr = np.zeros(len(graphs) + 1, dtype=np.int64)
@@ -93,8 +112,11 @@ class DeviceDataset(object):
         else:
             ei2 = ep2 = ea2 = None
         y = torch.tensor(np.asarray([g.get('y', 0) for g in graphs])).to(device)
-        return DeviceDataset(torch.from_numpy(np.concatenate(xs)).to(device), torch.from_numpy(nptr).to(device),
-                             ei, ep, ei2, ep2, ea2, y)
+        ds = DeviceDataset(torch.from_numpy(np.concatenate(xs)).to(device), torch.from_numpy(nptr).to(device),
+                           ei, ep, ei2, ep2, ea2, y)
+        for k in tuple(graph_fields):
+            ds.graph_fields[k] = torch.tensor([float(np.asarray(g[k]).reshape(-1)[0]) for g in graphs], dtype=torch.float32).to(device)
+        return ds
 
     @staticmethod
     def _ranges(ptr, ids):
@@ -120,6 +142,7 @@ class DeviceDataset(object):
         if self.edge_index2 is not None:
             out['edge_index2'], epos2 = take(self.edge_index2, self.edge_ptr2)
             out['edge_attr2'] = self.edge_attr2[epos2]
+        out.update(self._graph_fields(ids))
         return Batch(**out)
 
     # ------------------------------------------------------------------ equal-size graphs of 97 .. 256 nodes: dense blocks from a bank
@@ -232,7 +255,8 @@ class DeviceDataset(object):
         y = torch.cat([torch.where(has, self.y[idc], torch.zeros_like(self.y[idc])), torch.zeros(1, dtype=self.y.dtype, device=dev)])
         # (no `edge_index` unless asked for: a consumer of data.csr('edge_index'), e.g. a GNNML1 model or a K = 1 raw-adjacency conv,
         #  must fail loudly on a padded batch without it instead of computing on the support edges)
-        b = Batch(x=x, edge_index2=ei2, edge_attr2=ea2, batch=nseg, ptr=ptr, y=y, graph_valid=has.to(self.x.dtype))
+        b = Batch(x=x, edge_index2=ei2, edge_attr2=ea2, batch=nseg, ptr=ptr, y=y, graph_valid=has.to(self.x.dtype),
+                  **self._graph_fields(ids, padded=True))
         if adjacency:
             e_pad, e_deal = bounds['e_pad'], bounds['e_deal']
             apos, aptr, _, aok, asc, ka = layout(self.edge_ptr, e_pad)
@@ -393,7 +417,7 @@ class DeviceDataset(object):
         g.static_shape = True
         if es is not None:                                                # the pre-split supports travel with the batch (functional.presplit_of)
             g._val_cache[('p', ea.data_ptr(), ea._version, tuple(ea.shape))] = (ea, es)
-        b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y, graph_valid=valid)
+        b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y, graph_valid=valid, **self._graph_fields(ids, padded=True))
         b.static_caps = bounds['caps']
         b.pad_graph = True
         b._csr['edge_index2'] = g
@@ -504,9 +528,9 @@ class DeviceDataset(object):
             g._sym_dev = (ea, uid, mir, count)
         x = xbuf[:, :F]
         if exact:
-            b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y)
+            b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y, **self._graph_fields(ids))
         else:
-            b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y, graph_valid=valid)
+            b = Batch(x=x, edge_attr2=ea, batch=batch, ptr=ptr, y=y, graph_valid=valid, **self._graph_fields(ids, padded=True))
             b.static_caps = bounds['caps']
             b.pad_graph = True
         b._csr['edge_index2'] = g

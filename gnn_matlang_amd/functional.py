@@ -2376,3 +2376,141 @@ class GINConvFunction(torch.autograd.Function):
             dw2, db2 = flat[o2:o3].view(Fout, Fh), flat[o3:o3 + Fout]
         hb1, hb2 = ctx.has_b
         return dx, None, flat[-1:].reshape(ctx.eps_shape), dw1, db1 if hb1 else None, dw2, db2 if hb2 else None, None
+
+
+# ---------------------------------------------------------------------------- ChebNet layer (csrc/gml_cheb.hip)
+def cheb_conv_supported(x, Fout, K, Fin=None):
+    """the fused ChebConv layer (ChebConvFunction) serves this input: float32 [N >= 1, Fin] on the device (Fin: another width than
+    x's, for a later layer of the same rows), 1 <= K <= 8 and both widths in 1 .. 64 (gml_cheb_supported) -- every ChebNet of the experiment scripts up to 64 wide.  Any number of edges, any degree.
+    Everything else (the 128- and 200-wide ChebNets of enzymes / ptc / proteins / enzymes_contfeat among it) takes the composition
+    cheb_conv_torch.  GML_NO_CHEB_FUSED=1 sends every shape there.  No shape inside the range is gated onto the composition: one layer
+    forward + backward, fused 90th percentile (norm launch included) against the composition's 10th, ms (tools/bench_cheb.py,
+    profiles/cheb.json, DESIGN s4.22): ZINC-like batch of 64 at K = 2 0.14 against 0.53 (25 -> 64) and 0.15 against 0.53 (64 -> 64),
+    mutag batch 16 at K = 3 0.18 against 0.79 and 0.17 against 0.81, sr25 at K = 4 0.19 against 1.04 and 0.21 against 0.98, the 900-node
+    grid at K = 7 0.16 against 1.61 and 0.30 against 1.63, 500 k rows 2.06 against 4.39 (K = 2) and 6.63 against 14.24 (K = 5)."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1):
+        return False
+    if _os.environ.get('GML_NO_CHEB_FUSED'):
+        return False
+    return bool(_lib.lib().gml_cheb_supported(int(x.size(1)) if Fin is None else int(Fin), int(Fout), int(K)))
+
+
+def _cheb_lambda(lambda_max, batch):
+    """(lmax tensor or None, batch or None, scalar) of ChebConv's lambda_max argument: None = 2.0, a number for every graph, a tensor
+    of one element for every graph, a tensor [B] indexed by batch"""
+    if lambda_max is None:
+        return None, None, 2.0
+    if not isinstance(lambda_max, torch.Tensor):
+        return None, None, float(lambda_max)
+    lam = lambda_max.reshape(-1)
+    if lam.numel() > 1 and batch is None:
+        raise ValueError('lambda_max holds %d values: batch (the graph of every node) is needed to index it' % lam.numel())
+    return lam, (batch if lam.numel() > 1 else None), 2.0
+
+
+def cheb_norm(csr, batch=None, lambda_max=None):
+    """norm [N, 2] = (deg^-1/2 over the non-self edges of the source view, 2 / lambda_max of the node's graph): what every ChebConv of
+    a model reads (gml_cheb_norm, one launch, no host read: inside a captured step it follows batch and lambda_max on replay).
+    lambda_max: None (2.0), a number, or a float32 tensor [B] indexed by batch [N]; values <= 0 or not finite are outside the contract."""
+    dev = csr.device
+    lam, bt, scalar = _cheb_lambda(lambda_max, batch)
+    if lam is not None:
+        _require_cuda(lam, 'lambda_max')
+        lam = lam.to(torch.float32).contiguous()
+    if bt is not None:
+        _require_cuda(bt, 'batch')
+        if bt.numel() != csr.N:
+            raise ValueError('batch holds %d entries, the graph has %d nodes' % (bt.numel(), csr.N))
+        bt = bt.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        norm = torch.empty(csr.N, 2, dtype=torch.float32, device=dev)
+        _lib.call('gml_cheb_norm', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(bt), _ptr(lam), 0 if lam is None else int(lam.numel()),
+                  scalar, csr.N, csr.E, _ptr(norm), _stream(dev))
+    return norm
+
+
+def cheb_conv_torch(x, edge_index, weight, bias=None, batch=None, lambda_max=None, act=None):
+    """ChebConv (torch_geometric 1.6.1, normalization 'sym') composed from torch ops of static shape, on any device and dtype: the road
+    of every shape outside cheb_conv_supported and the opponent of tools/bench_cheb.py.  x [N, Fin], edge_index [2, E] = (source j,
+    target i), weight [K, Fin, Fout], bias [Fout] or None.  Self loops are dropped (masked, not removed: no host read), every other
+    edge occurrence counts;  deg over the sources, L^[i, j] = -s[i] dis[i] dis[j], L^[i, i] = s[i] - 1, s = 2 / lambda_max;
+    Tx_0 = x, Tx_1 = L^ x, Tx_k = 2 L^ Tx_{k-1} - Tx_{k-2};  out = act(bias + sum_k Tx_k W_k)."""
+    src, dst = edge_index[0], edge_index[1]
+    N = int(x.size(0))
+    keep = (src != dst).to(x.dtype)
+    deg = torch.zeros(N, dtype=x.dtype, device=x.device).index_add_(0, src, keep)
+    dis = torch.where(deg > 0, deg.clamp(min=1).pow(-0.5), torch.zeros_like(deg))
+    lam, bt, scalar = _cheb_lambda(lambda_max, batch)
+    if lam is None:
+        s = torch.full((N,), 2.0 / scalar, dtype=x.dtype, device=x.device)
+    else:
+        lam = lam.to(dtype=x.dtype, device=x.device)
+        s = 2.0 / (lam[bt.to(torch.int64)] if bt is not None else lam.expand(N))
+    w = (-(s[dst] * dis[dst]) * dis[src] * keep).unsqueeze(1)
+    diag = (s - 1).unsqueeze(1)
+
+    def lap(t):
+        return torch.zeros_like(t).index_add_(0, dst, w * t[src]) + diag * t
+    t0 = x
+    out = t0 @ weight[0]
+    if weight.size(0) > 1:
+        t1 = lap(t0)
+        out = out + t1 @ weight[1]
+        for k in range(2, int(weight.size(0))):
+            t0, t1 = t1, 2 * lap(t1) - t0
+            out = out + t1 @ weight[k]
+    if bias is not None:
+        out = out + bias
+    a = _gin_act_id(act)
+    return torch.relu(out) if a == 1 else (torch.tanh(out) if a == 2 else out)
+
+
+class ChebConvFunction(torch.autograd.Function):
+    """y = act(bias + sum_k Tx_k W_k) over a GraphCSR of the (source, target) edges and the norm of cheb_norm: K - 1 launches (one at
+    K = 1; gml_cheb_fwd); Tx_1 .. Tx_{K-1} [N, (K - 1) Fin] are kept for the backward.  Backward: gml_cheb_bwd -- the row pass, K - 1
+    adjoint steps over the source view, the fold; two launches when x needs no gradient (dx = NULL: the first layer of most models).
+    No atomics, no host read: bit-reproducible, capturable.  Plain fp32 (exact_products() changes nothing)."""
+
+    @staticmethod
+    def forward(ctx, x, csr, norm, weight, bias, act=None):
+        x, weight = _f32c(x, 'x'), _f32c(weight, 'weight')
+        if x.dim() != 2 or weight.dim() != 3 or weight.size(1) != x.size(1):
+            raise ValueError('ChebConv layer: x [N, Fin], weight [K, Fin, Fout] expected')
+        N, Fin = int(x.size(0)), int(x.size(1))
+        K, Fout = int(weight.size(0)), int(weight.size(2))
+        if csr.N != N:
+            raise ValueError('GraphCSR was built for %d nodes, x has %d rows' % (csr.N, N))
+        norm = _f32c(norm, 'norm')
+        if tuple(norm.shape) != (N, 2):
+            raise ValueError('ChebConv layer: norm [N, 2] (functional.cheb_norm) expected')
+        bias = None if bias is None else _f32c(bias, 'bias')
+        a = _gin_act_id(act)
+        dev = x.device
+        with torch.cuda.device(dev):
+            T = torch.empty(N, (K - 1) * Fin, dtype=torch.float32, device=dev) if K > 1 else None
+            y = torch.empty(N, Fout, dtype=torch.float32, device=dev)
+            with _Timed('cheb_fwd', q=4 * ((K - 1) * (csr.E + 3 * N) * Fin + N * Fin + (2 * K - 1) * N * Fout), f=2 * N * K * Fin * Fout):
+                _lib.call('gml_cheb_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(norm), _ptr(x), Fin, N, csr.E, Fin, _ptr(weight),
+                          _ptr(bias), Fout, K, a, _ptr(T), (K - 1) * Fin, _ptr(y), Fout, _stream(dev))
+        ctx.csr, ctx.act, ctx.dims, ctx.has_bias = csr, a, (N, Fin, Fout, K), bias is not None
+        ctx.save_for_backward(x, norm, weight, T, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, norm, weight, T, y = ctx.saved_tensors
+        csr, (N, Fin, Fout, K) = ctx.csr, ctx.dims
+        dev = x.device
+        dy = _f32c(dy, 'grad of y')
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+            flat = torch.empty(int(L.gml_cheb_dflat_floats(Fin, Fout, K)), dtype=torch.float32, device=dev)
+            nws = int(L.gml_cheb_bwd_workspace_bytes(N, Fin, Fout, K))
+            ws = torch.empty(max(nws // 4, 4), dtype=torch.float32, device=dev)
+            with _Timed('cheb_bwd'):
+                _lib.call('gml_cheb_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(norm), _ptr(x), Fin, _ptr(T), (K - 1) * Fin, _ptr(y), Fout,
+                          _ptr(dy), Fout, N, csr.E, Fin, _ptr(weight), Fout, K, ctx.act, _ptr(dx), Fin, _ptr(flat), _ptr(ws),
+                          ws.numel() * 4, _stream(dev))
+        nw = K * Fin * Fout
+        return dx, None, None, flat[:nw].view(K, Fin, Fout), flat[nw:] if ctx.has_bias else None, None

@@ -332,13 +332,15 @@ class Batch(object):
         return self._csr[which]
 
 
-def collate(graphs, node_fields=()):
+def collate(graphs, node_fields=(), graph_fields=()):
     """graphs: iterable of dicts with x [n,f], edge_index [2,e] and optionally edge_index2/edge_attr2/y
     (numpy or torch).  Node ids are offset per graph; everything stays on the host.
     node_fields: keys that hold PER-NODE float arrays [n, c] (filtering.py: ('y', 'mask')): concatenated along the rows like x
-    -- Batch.y [N, 3], Batch.mask [N, 1] -- instead of one value per graph."""
+    -- Batch.y [N, 3], Batch.mask [N, 1] -- instead of one value per graph.
+    graph_fields: keys that hold ONE float per graph (('lmax',): SpectralDesign's largest Laplacian eigenvalue, which the ChebNets
+    read): Batch.<key>, float32 [B].  Nothing is carried unless it is named here."""
     graphs = list(graphs)
-    node_fields = tuple(node_fields)
+    node_fields, graph_fields = tuple(node_fields), tuple(graph_fields)
     nf = dict((k, []) for k in node_fields)
     xs, e1, e2, ea, bt, ys, ptr, off = [], [], [], [], [], [], [0], 0
     for g, d in enumerate(graphs):
@@ -366,6 +368,8 @@ def collate(graphs, node_fields=()):
         out['edge_attr2'] = torch.from_numpy(np.concatenate(ea))
     for k in node_fields:
         out[k] = torch.from_numpy(np.concatenate(nf[k]))
+    for k in graph_fields:
+        out[k] = torch.tensor([float(np.asarray(d[k]).reshape(-1)[0]) for d in graphs], dtype=torch.float32)
     return Batch(**out)
 
 

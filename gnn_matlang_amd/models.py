@@ -498,7 +498,7 @@ class _Stack(torch.nn.Module):
     some they never call, and their checkpoints load with strict=True), the pools of _pool (or pool=None together with head='node':
     a node-level model) and a head of the class's _HEADS.  A padded static batch hands _node_valid to the bnI in training: padding
     nodes only reach padding nodes (their own self loops), the BatchNorm layers count real nodes only.  A subclass declares its
-    layers and supplies _layers(x, graph, _road): the function (i, x) -> the output of layer i."""
+    layers and supplies _layers(x, graph, _road) (or _batch_layers(data, x, graph, _road)): the function (i, x) -> the output of layer i."""
 
     def _init_stack(self, nlayers, bn_after, nbn, bn_width, pool, head):
         """the checks and attributes of the shared arguments, and bn1 .. bn<nbn>"""
@@ -525,7 +525,7 @@ class _Stack(torch.nn.Module):
                                       'graph and absent slots in the statistics of bn1' % self.head)
         graph = _adjacency(data)
         nvalid = _bn_valid(self, data, self.bn_after)
-        layer = self._layers(x, graph, _road)
+        layer = self._batch_layers(data, x, graph, _road)
         drop = _dropout_pass(self)
         for i in range(1, self.nlayers + 1):
             if drop:
@@ -536,6 +536,10 @@ class _Stack(torch.nn.Module):
         if self.pool is not None:
             x = _pool(self.pool, x, data)
         return x if _features else _apply_head(self, x)
+
+    def _batch_layers(self, data, x, graph, _road):
+        """_layers for this batch; a subclass whose layers read more of the batch than its adjacency (Cheb: lmax) overrides this one"""
+        return self._layers(x, graph, _road)
 
     def features(self, data, pad_grad_zero=False):
         """the features the head is applied to: the pooled graph rows [num_graphs, nin], with head='node' the node rows [N, nin]
@@ -1025,6 +1029,113 @@ def proteins_gin(ninp=4, dropout=0.2):     # proteins.py:31-63 (the ptc shapes a
 
 def enzymes_contfeat_gin(ninp=22, dropout=0.2):    # enzymes_contfeat.py:104-137 (the ptc shapes and roads with (mean, max) pools, fc2: 400 -> 6)
     return GIN(ninp, 200, 2, bn_after=(1, 2), nbn=2, dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=6)
+
+
+class Cheb(_Stack):
+    """The ChebNet of the PyG experiment scripts (Zinc12k.py:193-219, sr25.py:149-167, ...) as one class: conv1 .. convL =
+    cheb.ChebConv(., widths[i], K) over the raw adjacency, x <- act(conv_i x) with act 'relu' or 'tanh' applied inside the layer's
+    last launch; bn_after, nbn, dropout, pool: as _Stack has them (the scripts declare their bnI AFTER the convs: the same key order
+    here); head: a name of _HEADS (the table at _Head).  Same attribute names as the scripts, so their state_dicts load.
+    lmax=True: the layers get lambda_max = data.lmax [num_graphs] indexed by data.batch, as the scripts that pass
+    lambda_max=data.lmax do -- carry it with graph_fields=('lmax',); lmax=False: lambda_max = None (2.0), as mutag.py:178,
+    freqclass.py:198 and enzymes.py:233 call their layers.  The norm (functional.cheb_norm) is computed ONCE per forward call and
+    handed to every layer; it is not cached on the batch, so a captured step that replays over rewritten batch tensors recomputes it
+    inside the graph.  A padded static batch (batch_padded(..., adjacency=True)) works: a padding node carries only self loops, which
+    are dropped, so it is isolated and with x = 0 its output is act(bias); the pools skip the padding graph and the bnI get the row
+    validity.  Each layer takes the fused road where functional.cheb_conv_supported allows (K <= 8, widths up to 64), else
+    functional.cheb_conv_torch; _road='torch' forces the composition."""
+
+    _HEADS = dict(mlp=_MLP, tanh=_TANH, log_softmax=_LOG_SOFTMAX, bn_mlp=_BN_MLP, node=_NODE)
+
+    def __init__(self, ninp, widths, K, act='relu', bn_after=(), nbn=0, dropout=0.0, pool='add', head='mlp', hidden=0, nclass=1, lmax=True):
+        super().__init__()
+        from .cheb import ChebConv
+        widths = [int(w) for w in widths]
+        if act not in ('tanh', 'relu') or head not in self._HEADS or not widths:
+            raise ValueError('act: tanh / relu; at least one width; head: %s' % ' / '.join(self._HEADS))
+        self.act, self.K, self.lmax = act, int(K), bool(lmax)
+        fin = int(ninp)
+        for i, w in enumerate(widths, start=1):
+            setattr(self, 'conv%d' % i, ChebConv(fin, w, self.K))
+            fin = w
+        self._init_stack(len(widths), bn_after, nbn, fin, pool, head)
+        self._init_head(fin, hidden, nclass, dropout)
+
+    def _batch_layers(self, data, x, graph, _road):
+        lam = None
+        if self.lmax:
+            lam = getattr(data, 'lmax', None)
+            if lam is None:
+                raise ValueError("this ChebNet reads data.lmax (one lambda_max per graph): carry it with graph_fields=('lmax',) "
+                                 '(graph.collate / DeviceDataset.from_graphs)')
+        road = 'torch' if _road == 'torch' else None
+        convs = [getattr(self, 'conv%d' % i) for i in range(1, self.nlayers + 1)]
+        fused = road is None and any(Fn.cheb_conv_supported(x, c.out_channels, self.K, Fin=c.in_channels) for c in convs)
+        norm = Fn.cheb_norm(graph, data.batch, lam) if fused else None          # once per forward call, never cached on the batch
+        return lambda i, x: convs[i - 1](x, graph, batch=data.batch, lambda_max=lam, act=self.act, norm=norm, _road=road)
+
+
+def zinc_cheb(ninp=25):                    # Zinc12k.py:193-219 (S = 2: line 197 overrides the S = 5 default; 64 x 4, relu, add-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
+    return Cheb(ninp, (64, 64, 64, 64), 2, act='relu', pool='add', head='mlp', hidden=32)
+
+
+def sr25_cheb(ninp=2):                     # sr25.py:149-167 (S = 4; 32 | 64 | 64, tanh, add-pool, tanh(fc1: 64 -> 10))
+    return Cheb(ninp, (32, 64, 64), 4, act='tanh', pool='add', head='tanh', nclass=10)
+
+
+def graph8c_cheb(ninp=2):                  # graph8c.py:151-169 (the sr25 shapes)
+    return Cheb(ninp, (32, 64, 64), 4, act='tanh', pool='add', head='tanh', nclass=10)
+
+
+def exp_cheb(ninp=2):                      # exp_iso.py:151-169 (the sr25 shapes)
+    return Cheb(ninp, (32, 64, 64), 4, act='tanh', pool='add', head='tanh', nclass=10)
+
+
+def exp_classify_cheb(ninp=2):             # exp_classify.py:163-182 (S = 5; 32 | 64 | 64, relu, mean-pool, relu(fc1: 64 -> 10), fc2: 10 -> 1)
+    return Cheb(ninp, (32, 64, 64), 5, act='relu', pool='mean', head='mlp', hidden=10)
+
+
+def counting_cheb(ninp=2):                 # counting.py:213-237 (S = 5; 48 x 5, relu, add-pool, relu(fc1: 48 -> 32), fc2: 32 -> 1)
+    return Cheb(ninp, (48, 48, 48, 48, 48), 5, act='relu', pool='add', head='mlp', hidden=32)
+
+
+def mutag_cheb(ninp=8):                    # mutag.py:161-184 (S = 3; 32 x 3, relu, NO lambda_max: 2.0; mean-pool, relu(fc1: 32 -> 32), fc2: 32 -> 1)
+    return Cheb(ninp, (32, 32, 32), 3, act='relu', pool='mean', head='mlp', hidden=32, lmax=False)
+
+
+def freqclass_cheb(ninp=1, dropout=0.2):   # freqclass.py:182-206 (S = 5; 32 | 64 | 64, relu, dropout 0.2, NO lambda_max: 2.0; mean-pool, relu(fc1: 64 -> 32), fc2: 32 -> 1)
+    return Cheb(ninp, (32, 64, 64), 5, act='relu', dropout=dropout, pool='mean', head='mlp', hidden=32, lmax=False)
+
+
+def filtering_cheb(ninp=1):                # filtering.py:155-174 (S = 7; 64 x 3, relu, node-level: fc2: 64 -> 1 on every node, no pooling)
+    return Cheb(ninp, (64, 64, 64), 7, act='relu', pool=None, head='node', nclass=1)
+
+
+def mnist75_cheb(ninp=3, dropout=0.1):     # mnist75.py:150-185 (S = 5; 64 x 3, relu, dropout 0.1, mean-pool, bn1 on the pooled rows, relu(fc1: 64 -> 32), log_softmax(fc2: 32 -> 10))
+    return Cheb(ninp, (64, 64, 64), 5, act='relu', dropout=dropout, pool='mean', head='bn_mlp', hidden=32, nclass=10)
+
+
+def enzymes_cheb(ninp=4, dropout=0.1):
+    """enzymes.py:215-243: S = 3, 128 x 4, relu, dropout 0.1, NO lambda_max (2.0), (mean, max) pools, log_softmax(fc2: 256 -> 6), no
+    fc1.  128 wide: conv1 (ninp -> 128) and the rest are beyond the fused layer (widths up to 64) and run on functional.cheb_conv_torch."""
+    return Cheb(ninp, (128, 128, 128, 128), 3, act='relu', dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=6, lmax=False)
+
+
+def ptc_cheb(ninp=20, dropout=0.2):
+    """ptc.py:193-231: S = 3, 200 x 4, relu, dropout 0.2; bn1, bn2 declared, never called; (mean, max) pools, log_softmax(fc2: 400 ->
+    2).  200 wide: every layer runs on functional.cheb_conv_torch."""
+    return Cheb(ninp, (200, 200, 200, 200), 3, act='relu', nbn=2, dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=2)
+
+
+def proteins_cheb(ninp=4, dropout=0.2):
+    """proteins.py:128-166: S = 3, 200 x 2, relu, dropout 0.2, bn1 / bn2 after the layers, (mean, max) pools, log_softmax(fc2: 400 -> 2).
+    200 wide: both layers run on functional.cheb_conv_torch; bn1 / bn2 are beyond the masked BatchNorm kernel, so a padded static batch
+    in TRAINING raises BatchNorm1d's NotImplementedError; plain batches and evaluation run."""
+    return Cheb(ninp, (200, 200), 3, act='relu', bn_after=(1, 2), nbn=2, dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=2)
+
+
+def enzymes_contfeat_cheb(ninp=22, dropout=0.2):   # enzymes_contfeat.py:203-242 (the proteins shapes and roads, fc2: 400 -> 6)
+    return Cheb(ninp, (200, 200), 3, act='relu', bn_after=(1, 2), nbn=2, dropout=dropout, pool=('mean', 'max'), head='log_softmax', nclass=6)
 
 
 def _graph_valid(valid, data):

@@ -1132,6 +1132,52 @@ int gml_gin_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* x, i
                 const float* w1, int32_t Fh, const float* w2, int32_t Fout, int32_t depth, int32_t act, float* dx, int64_t lddx,
                 float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream);
 
+/* ChebNet (the spectral baseline of every PyG experiment script, e.g. Zinc12k.py:193-219, sr25.py:149-167): ChebConv(Fin, Fout, K) of
+ * torch_geometric 1.6.1 with normalization 'sym' and the script's activation (csrc/gml_cheb.hip).  (rowptr, col) lists the sources j of
+ * every target i (a GraphCSR's target view), (rowptr_t, col_t) the targets of every source.  Self loops are dropped; every other edge
+ * occurrence counts, duplicates included.  The graph need not be symmetric.
+ *
+ * gml_cheb_norm: norm [N][2] = (dis[i], s[i]), ONE launch per batch, shared by every layer of a model.
+ *     deg[i] = the non-self edges of the SOURCE row i with a target in [0, N);  dis[i] = 1 / sqrt(deg[i]), 0 at deg 0
+ *     s[i] = 2 / lmax[batch[i]]  (lmax [B] and batch [N], int32, DEVICE pointers; batch NULL: graph 0; a graph id outside [0, B): 2.0),
+ *            or 2 / lambda for every row when lmax == NULL.  lmax <= 0 or not finite is outside the contract (nothing reads it on host).
+ *   The scaled Laplacian it stands for:  L^[i, j] = sum over the edges (j -> i, j != i) of w,  w = (-(s[i] dis[i])) dis[j]  (two fp32
+ *   products in this order),  L^[i, i] = s[i] - 1, for isolated rows too.
+ * gml_cheb_fwd: Tx_0 = x, Tx_1 = L^ x, Tx_k = 2 L^ Tx_{k-1} - Tx_{k-2};  y = act(bias + sum_k Tx_k W_k)
+ *   act 0 none / 1 relu / 2 tanh; w [K][Fin][Fout] dense row-major; bias [Fout] optional (NULL).  T [N, (K - 1) Fin] (rows of ldT)
+ *   receives Tx_1 .. Tx_{K-1} side by side: the backward's inputs (Tx_0 = x is not copied; T is not read at K = 1).  y doubles as the
+ *   accumulator between the launches.  K - 1 launches (each step needs the neighbours' previous Tx), ONE at K = 1.
+ *   The orders are the contract:
+ *     a Tx_k element  a = 0; the row's edges in CSR order: a = fmaf(w, Tx_{k-1}[j][c], a); then a = fmaf(s[i] - 1, Tx_{k-1}[i][c], a);
+ *                     k = 1: Tx_1 = a;  k >= 2: Tx_k = fmaf(2, a, -Tx_{k-2}[i][c])
+ *     a y element     acc = bias (0 without one); then k = 0 .. K - 1 ascending, inside k the input column c ascending:
+ *                     acc = fmaf(Tx_k[i][c], W_k[c][o], acc);  y = act(acc)
+ * gml_cheb_bwd: dy (rows of lddy) -> dx (rows of lddx; NULL: not wanted, the adjoint steps are skipped) and
+ *   dflat = [dW_0 .. dW_{K-1}, each Fin x Fout | db Fout], gml_cheb_dflat_floats floats.  With g = dy act'(y) (act' from y alone):
+ *     dW_k = Tx_k^T g,  db = sum_i g[i],  G_{K-1} = g W_{K-1}^T,  G_k = g W_k^T + c_k L^T G_{k+1} - G_{k+2} (c_0 = 1, else 2; terms with
+ *     an index above K - 1 absent),  dx = G_0.  L^T walks the SOURCE view with the forward's w of every edge.
+ *     a G_k element   a = 0; the source row's edges in CSR order: a = fmaf(w, G_{k+1}[i][c], a); then a = fmaf(s[j] - 1, G_{k+1}[j][c], a);
+ *                     p = 0, o ascending: p = fmaf(g[j][o], W_k[c][o], p);  G_k = fmaf(c_k, a, p), then - G_{k+2}[j][c]
+ *   Launches: the row pass (per-workgroup partials of dflat over contiguous row ranges, rows ascending, k ascending inside a tile of
+ *   32 rows; it also forms g W_{K-1}^T: dx at K = 1), K - 1 adjoint steps (three rotating [N, Fin] buffers in the workspace; the last
+ *   writes dx), the fold of the partials in ascending workgroup order: K + 1 launches, TWO with dx == NULL.  No atomics: two runs give
+ *   the same bits.
+ * Range: 1 <= K <= 8, 1 <= Fin, Fout <= 64 (gml_cheb_supported), any N >= 1, E >= 0 (below 2^31), any degree, rows of any stride >=
+ * their width (no alignment beyond a float's); else GML_E_UNSUPPORTED.  A workspace below gml_cheb_bwd_workspace_bytes:
+ * GML_E_WORKSPACE.  Nothing is launched on any error.  Column ids outside [0, N) are skipped.  Plain fp32 fmaf / tanhf.  No allocation,
+ * no host read: capturable on one stream. */
+int gml_cheb_supported(int32_t Fin, int32_t Fout, int32_t K);
+int gml_cheb_norm(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* batch, const float* lmax, int64_t B, float lambda,
+                  int64_t N, int64_t E, float* norm, gml_stream_t stream);
+int gml_cheb_fwd(const int32_t* rowptr, const int32_t* col, const float* norm, const float* x, int64_t ldx, int64_t N, int64_t E,
+                 int32_t Fin, const float* w, const float* bias, int32_t Fout, int32_t K, int32_t act, float* T, int64_t ldT, float* y,
+                 int64_t ldy, gml_stream_t stream);
+int64_t gml_cheb_dflat_floats(int32_t Fin, int32_t Fout, int32_t K);
+size_t gml_cheb_bwd_workspace_bytes(int64_t N, int32_t Fin, int32_t Fout, int32_t K);
+int gml_cheb_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* norm, const float* x, int64_t ldx, const float* T, int64_t ldT,
+                 const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t N, int64_t E, int32_t Fin, const float* w, int32_t Fout,
+                 int32_t K, int32_t act, float* dx, int64_t lddx, float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
