@@ -15,13 +15,16 @@ baseline of tools/bench_mnist.py.  Same parameters and values as ``SpectConv`` o
 
 One LARGE graph (96 < n <= 1024, F <= 64: the 2-D grid of filtering.py, 900 nodes, a 40 % full mask) takes the same form on
 csrc/gml_dense_big.hip: the work is cut across (support, row block, K slice) instead of across graphs, the projection stays the
-tall GEMM (``_SupportProduct`` dispatches by n; the chained one-launch kernels are n <= 96 only).
+tall GEMM (the chained one-launch kernels are n <= 96 only).
 
 Batches of equal-size graphs of 96 < n <= 256 nodes (freqclass.py: bandclass graphs of 200 nodes, 2-hop masks 6-8 % full, S = 6,
 layers 66 -> 64 + 2) take csrc/gml_dense_mid.hip: one workgroup per (graph, 64-row block, support), F <= 128 in one pass.  The
 supports of the whole data set are packed once into an ``EqualSupports`` bank; a batch names its graphs by bank slot (gid), so a
 batch is x, y and gid only -- a static shape without edge tensors (``DeviceDataset.batch_dense``).
+
+Which of these serves a shape is decided in ONE place: ``dense_road`` (host integers in, a ``DenseRoad`` record out).
 """
+import collections
 import ctypes
 import os
 
@@ -45,9 +48,7 @@ class DenseSupports(object):
         self.B, self.S, self.n = int(B), int(S), int(n)
         self.KP = (self.n + 31) // 32 * 32
         self.blocks = blocks if keep_blocks else None
-        self.fwd = self.bwd = None
-        if not keep_blocks:
-            self.fwd, self.bwd = self._pack(blocks, 0), self._pack(blocks, 1)
+        self.fwd, self.bwd = (None, None) if keep_blocks else (self._pack(blocks, 0), self._pack(blocks, 1))
 
     def _pack(self, blocks, transpose):
         img = torch.empty(self.B, self.S, 2, self.n, self.KP, dtype=torch.int16, device=blocks.device)
@@ -59,22 +60,46 @@ def _library():
     return USE_LIBRARY or Fn.exact_mode()
 
 
-SMALL_N = 96                 # gml_dense.hip: one workgroup per graph
+SMALL_N, SMALL_F = 96, 128   # gml_dense.hip: one workgroup per graph of n <= SMALL_N nodes, F <= SMALL_F features
+CHAIN_FOUT = 128             # and its one-launch layer (gml_dense_conv_fwd / _bwd_x): projections of up to CHAIN_FOUT columns
 BIG_N, BIG_F = 1024, 64      # gml_dense_big.hip: ONE graph of SMALL_N < n <= BIG_N nodes, F <= BIG_F features
+MID_N, MID_F = 256, 128      # gml_dense_mid.hip: B graphs (or a bank) of SMALL_N < n <= MID_N nodes each, F <= MID_F features
+
+# product: what evaluates the support product -- 'library' (torch.bmm fp32), 'small' (gml_dense.hip), 'mid' (gml_dense_mid.hip),
+#          'big' (gml_dense_big.hip), or None: no dense kernel covers the shape
+# chained: _DenseConv serves the whole layer in one launch
+# fmax:    the feature limit of the kernel of this size class (None: the library has none; 0: there is no such kernel)
+# label:   the suffix of the Fn._path labels of _SupportProduct
+DenseRoad = collections.namedtuple('DenseRoad', 'product chained fmax label')
+
+
+def dense_road(num_graphs, n, Fin, Fout=None, bank=False, library=False):
+    """DenseRoad of num_graphs graphs of n nodes with Fin features, from host integers and booleans only (no tensor, no launch).
+    Fout: the width of the projection behind the product, None for a bare product.  bank: the supports are an EqualSupports bank.
+    library: the library mode (_library()) is on -- it serves the size classes the kernels serve, at any Fin."""
+    if 1 <= n <= SMALL_N:                                    # (any number of graphs)
+        product, fmax, label = 'small', SMALL_F, ''
+    elif SMALL_N < n <= BIG_N and num_graphs == 1 and not bank:
+        product, fmax, label = 'big', BIG_F, ', large graph'
+    elif SMALL_N < n <= MID_N and (num_graphs >= 2 or (bool(bank) and num_graphs >= 1)):
+        product, fmax, label = 'mid', MID_F, ', batched blocks'
+    else:
+        return DenseRoad(None, False, 0, '')
+    if library:
+        return DenseRoad('library', False, None, '')
+    covered = 1 <= Fin <= fmax
+    return DenseRoad(product if covered else None, covered and product == 'small' and Fout is not None and Fout <= CHAIN_FOUT, fmax, label)
 
 
 def big_applies(num_graphs, n, F):
     """True when the large-graph dense support product covers this batch (host integers only)."""
-    return num_graphs == 1 and SMALL_N < n <= BIG_N and 1 <= F <= BIG_F
-
-
-MID_N, MID_F = 256, 128     # gml_dense_mid.hip: B graphs (or a bank) of SMALL_N < n <= MID_N nodes each, F <= MID_F features
+    return dense_road(num_graphs, n, F).product == 'big'
 
 
 def mid_applies(num_graphs, n, F, bank=False):
     """True when the batched-blocks support product (csrc/gml_dense_mid.hip) covers this batch (host integers only): two or more
     graphs -- or any number of graphs that name their slots in a bank (EqualSupports) -- of SMALL_N < n <= MID_N nodes each."""
-    return (num_graphs >= 2 or (bool(bank) and num_graphs >= 1)) and SMALL_N < n <= MID_N and 1 <= F <= MID_F
+    return dense_road(num_graphs, n, F, bank=bank).product == 'mid'
 
 
 def _coo_blocks(src, dst, val, g0, g1, S, n):
@@ -135,7 +160,7 @@ def dense_supports(edge_index2, edge_attr2, ptr, n):
     S = int(edge_attr2.size(1))
     if B * n != int(ptr[-1]):
         raise ValueError('dense blocks need equal-size graphs: %d graphs, %d nodes, n=%d' % (B, int(ptr[-1]), n))
-    if n > SMALL_N and not (B == 1 and n <= BIG_N) and not mid_applies(B, n, 1):
+    if dense_road(B, n, 1).product is None:
         raise ValueError('dense blocks are built for n <= %d nodes per graph, graphs of up to %d nodes, or one graph of up to %d nodes: '
                          'got %d graphs of %d' % (SMALL_N, MID_N, BIG_N, B, n))
     src, dst = edge_index2[0], edge_index2[1]
@@ -146,11 +171,23 @@ def dense_supports(edge_index2, edge_attr2, ptr, n):
     return DenseSupports(blocks, keep_blocks=_library())
 
 
-def _kind(sup):
-    """the kernel that serves these supports: '' (gml_dense.hip), 'large graph' (gml_dense_big.hip), 'batched blocks' (gml_dense_mid.hip)"""
-    if sup.n <= SMALL_N:
-        return ''
-    return 'large graph' if sup.B == 1 and not isinstance(sup, EqualSupports) else 'batched blocks'
+def batch_supports(data, n):
+    """The DenseSupports of a batch of graphs of n nodes each, cached on the batch like its CSR (data._spT): built when missing, when
+    they hold another n, or when they hold the side (fp32 blocks against packed images) the current mode does not read."""
+    sp = getattr(data, '_spT', None)
+    if sp is None or sp.n != n or (sp.blocks is None) == bool(_library()):
+        sp = data._spT = dense_supports(data.edge_index2, data.edge_attr2, data.ptr, n)
+    return sp
+
+
+def _road(sup, rows, F, Fout=None, library=False):
+    """dense_road of `rows` activation rows on these supports (a bank: of the graphs the rows name); ValueError where no kernel covers them"""
+    bank = isinstance(sup, EqualSupports)
+    B = rows // max(sup.n, 1) if bank else sup.B
+    road = dense_road(B, sup.n, F, Fout, bank, library)
+    if road.product is None:
+        raise ValueError('no dense-block kernel covers %d graphs of n = %d nodes with Fin = %d (Fin <= %d at this size)' % (B, sup.n, F, road.fmax))
+    return road
 
 
 def support_mm(img, act, sup, F, sa, so, sum_s, gid=None):
@@ -158,8 +195,8 @@ def support_mm(img, act, sup, F, sa, so, sum_s, gid=None):
     One graph of more than SMALL_N nodes: gml_dense_big_support_mm (csrc/gml_dense_big.hip); several, or a bank (EqualSupports) whose
     slots gid (int32 [B]; None = the first B slots in order) names: gml_dense_mid_support_mm (csrc/gml_dense_mid.hip)."""
     act = act.contiguous()
-    kind = _kind(sup)
-    if kind == 'batched blocks':
+    product = _road(sup, int(act.size(0)), int(F)).product
+    if product == 'mid':
         B = int(act.size(0)) // sup.n
         if B * sup.n != int(act.size(0)) or (gid is not None and int(gid.numel()) != B) or (gid is None and B > sup.B):
             raise ValueError('%d rows do not match %s graphs of %d nodes' % (int(act.size(0)), 'the bank slots of %d' % int(gid.numel())
@@ -171,7 +208,7 @@ def support_mm(img, act, sup, F, sa, so, sum_s, gid=None):
     if gid is not None:
         raise ValueError('bank slots (gid) go with an EqualSupports bank')
     out = torch.empty(sup.B * sup.n, F if sum_s else sup.S * so, dtype=torch.float32, device=act.device)
-    if sup.n > SMALL_N:
+    if product == 'big':
         nws = int(_lib.lib().gml_dense_big_workspace_bytes(sup.S, sup.n, int(F), int(bool(sum_s))))
         ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=act.device)
         _lib.call('gml_dense_big_support_mm', _ptr(img), _ptr(act), int(act.stride(0)), int(sa), _ptr(out), int(out.stride(0)), int(so),
@@ -188,16 +225,15 @@ class _SupportProduct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sup, gid=None):
         ctx.sup, ctx.Fin, ctx.gid = sup, int(x.size(1)), gid
-        kind = _kind(sup)
-        Fn._path('dense', 'support product fwd (bf16x3 HIP%s)' % (', ' + kind if kind else ''), sup.S, ctx.Fin, ctx.Fin)
+        ctx.label = _road(sup, int(x.size(0)), ctx.Fin).label
+        Fn._path('dense', 'support product fwd (bf16x3 HIP%s)' % ctx.label, sup.S, ctx.Fin, ctx.Fin)
         return support_mm(sup.fwd, x, sup, ctx.Fin, 0, ctx.Fin, False, gid)
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
             return None, None, None
-        kind = _kind(ctx.sup)
-        Fn._path('dense', 'support product bwd (bf16x3 HIP%s)' % (', ' + kind if kind else ''), ctx.sup.S, ctx.Fin, ctx.Fin)
+        Fn._path('dense', 'support product bwd (bf16x3 HIP%s)' % ctx.label, ctx.sup.S, ctx.Fin, ctx.Fin)
         return support_mm(ctx.sup.bwd, g, ctx.sup, ctx.Fin, ctx.Fin, 0, True, ctx.gid), None, None
 
 
@@ -241,16 +277,13 @@ class _TallGemm(torch.autograd.Function):
 # 1.19): a workgroup per (support, 64-column block, graph slice) recomputes the product per column block and pays the full load
 # latency per graph (208 VGPRs at Fin = 128: one workgroup per CU).  What it needs is in DESIGN s8.
 DW_LIBRARY = os.environ.get('GML_DENSE_DW_HIP', '0') in ('0', '')
-DW_GEMM_LIB = os.environ.get('GML_DENSE_DW_GEMM_LIB', '0') not in ('0', '')   # A/B: the dW GEMM Hcat^T g through the library instead of gml_xty_wide
-CHAIN = os.environ.get('GML_DENSE_CHAIN', '1') not in ('0', '')      # projection chained behind the support product (gml_dense_conv_fwd)
-CHAIN_BWD = os.environ.get('GML_DENSE_CHAIN_BWD', '1') not in ('0', '')   # and the dX path: projection in front of the transposed product
 
 
 class _DenseConv(torch.autograd.Function):
     """out = sum_s (D_s X) W_s + bias in ONE launch: the support product's accumulators are the projection's operand
     (csrc/gml_dense.hip: gml_k_dense_conv_fwd), as libs/layers_tf.py:231-236 forms the layer.  Hcat is written only as the
-    saved tensor of the weight gradient dW = Hcat^T g (row-slab batched GEMM, see _TallGemm); dX = sum_s D_s^T (g W_s^T) is
-    the library GEMM g Wcat^T followed by the support product on the transposed images."""
+    saved tensor of the weight gradient dW = Hcat^T g (gml_xty_wide, or the row-slab batched GEMM of _TallGemm where it does not
+    apply); dX = sum_s D_s^T (g W_s^T) is one launch on the transposed images (gml_k_dense_conv_bwdx)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, sup, relu=False):
@@ -294,20 +327,16 @@ class _DenseConv(torch.autograd.Function):
             else:
                 g = g * (yout > 0)
         if ctx.needs_input_grad[0]:
-            if CHAIN_BWD:
-                # dX = sum_s D_s^T (g W_s^T) in one launch: d Hcat stays on the CU (gml_k_dense_conv_bwdx)
-                dev = g.device
-                wimgT = torch.empty(int(_lib.lib().gml_dense_wimgt_elems(S, Fin, Fout)), dtype=torch.int16, device=dev)
-                _lib.call('gml_dense_pack_wt', _ptr(weight.contiguous()), _ptr(wimgT), S, Fin, Fout, _stream(dev))
-                dx = torch.empty(sup.B * sup.n, Fin, dtype=torch.float32, device=dev)
-                Fn._path('dense', 'projection + support product chained, backward (bf16x3 HIP)', S, Fin, Fout)
-                with Fn._Timed('dense_conv_bwd_x', sup.B * S * 2 * sup.n * sup.KP * 2 + 4 * sup.B * sup.n * (Fin + Fout),
-                               2 * sup.B * S * sup.n * sup.n * Fin + 2 * sup.B * sup.n * S * Fin * Fout):
-                    _lib.call('gml_dense_conv_bwd_x', _ptr(sup.bwd), _ptr(g), int(g.stride(0)), _ptr(wimgT), _ptr(dx), Fin,
-                              sup.B, S, sup.n, sup.KP, Fin, Fout, _stream(dev))
-            else:
-                dh = g.mm(weight.reshape(S * Fin, Fout).t())
-                dx = support_mm(sup.bwd, dh, sup, Fin, Fin, 0, True)
+            # dX = sum_s D_s^T (g W_s^T) in one launch: d Hcat stays on the CU (gml_k_dense_conv_bwdx)
+            dev = g.device
+            wimgT = torch.empty(int(_lib.lib().gml_dense_wimgt_elems(S, Fin, Fout)), dtype=torch.int16, device=dev)
+            _lib.call('gml_dense_pack_wt', _ptr(weight.contiguous()), _ptr(wimgT), S, Fin, Fout, _stream(dev))
+            dx = torch.empty(sup.B * sup.n, Fin, dtype=torch.float32, device=dev)
+            Fn._path('dense', 'projection + support product chained, backward (bf16x3 HIP)', S, Fin, Fout)
+            with Fn._Timed('dense_conv_bwd_x', sup.B * S * 2 * sup.n * sup.KP * 2 + 4 * sup.B * sup.n * (Fin + Fout),
+                           2 * sup.B * S * sup.n * sup.n * Fin + 2 * sup.B * sup.n * S * Fin * Fout):
+                _lib.call('gml_dense_conv_bwd_x', _ptr(sup.bwd), _ptr(g), int(g.stride(0)), _ptr(wimgT), _ptr(dx), Fin,
+                          sup.B, S, sup.n, sup.KP, Fin, Fout, _stream(dev))
         if ctx.needs_input_grad[1] and not ctx.has_h:
             # dW = sum over the graphs of (D_s X)^T g: the support product recomputed on the matrix cores, contracted with g over the graph's
             # rows, no Hcat in HBM and no library GEMM (gml_dense_conv_bwd_w, csrc/gml_dense.hip)
@@ -320,11 +349,10 @@ class _DenseConv(torch.autograd.Function):
         elif ctx.needs_input_grad[1]:
             rows = int(hcat.size(0))
             P = _splits(rows)
-            dw = None
-            if not DW_GEMM_LIB:                                   # round 5: Hcat^T g on the bf16 matrix cores (gml_xty_wide), not a library GEMM
-                with Fn._Timed('dense_dw_xty_wide', 4 * rows * (S * Fin + Fout), 2 * rows * S * Fin * Fout, q2=4 * rows * (Fin + Fout)):
-                    dw = Fn.xty_wide(hcat, g)
-                dw = dw.view(S, Fin, Fout) if dw is not None else None
+            # round 5: Hcat^T g on the bf16 matrix cores (gml_xty_wide); a shape it does not take (None): the library GEMM
+            with Fn._Timed('dense_dw_xty_wide', 4 * rows * (S * Fin + Fout), 2 * rows * S * Fin * Fout, q2=4 * rows * (Fin + Fout)):
+                dw = Fn.xty_wide(hcat, g)
+            dw = dw.view(S, Fin, Fout) if dw is not None else None
             if dw is None:
                 with Fn._Timed('dense_dw_library_gemm', 4 * rows * (S * Fin + Fout), 2 * rows * S * Fin * Fout):
                     dw = (torch.bmm(hcat.view(P, rows // P, S * Fin).transpose(1, 2), g.view(P, rows // P, Fout)).sum(0) if P > 1
@@ -336,25 +364,27 @@ class _DenseConv(torch.autograd.Function):
 
 def spectconv_dense(x, sup, weight, bias, n, relu=False, gid=None):
     """x [B*n, Fin], sup from dense_supports, weight [S, Fin, Fout] -> [B*n, Fout] = act(sum_s (D_s x) W_s + bias), act = relu or none.
-    sup an EqualSupports bank: gid int32 [B] names the bank slot of every graph of x (None: the bank's first B graphs in order)."""
+    sup an EqualSupports bank: gid int32 [B] names the bank slot of every graph of x (None: the bank's first B graphs in order).
+    The road is dense_road's under the library mode of this call; supports built in the other mode raise ValueError."""
     S, Fin, Fout = weight.shape
     bank = isinstance(sup, EqualSupports)
     B = int(x.size(0)) // max(n, 1) if bank else sup.B
     if sup.n != n or sup.S != S or x.size(0) != B * n or (gid is not None and (not bank or int(gid.numel()) != B)) or (gid is None and B > sup.B):
         raise ValueError('supports [%d graphs, S=%d, n=%d] do not match x %s / weight %s%s' %
                          (sup.B, sup.S, sup.n, tuple(x.shape), tuple(weight.shape), '' if gid is None else ' / %d bank slots' % int(gid.numel())))
-    if _library() if bank else sup.blocks is not None:   # library path (GML_DENSE_LIB=1 / GML_F32_MFMA=1)
+    road = _road(sup, int(x.size(0)), Fin, Fout, _library())   # the mode of THIS call decides (GML_DENSE_LIB=1 / GML_F32_MFMA=1), not sup's
+    library = road.product == 'library'
+    if (sup.blocks if library else sup.fwd) is None:
+        raise ValueError('these supports were built %s the library mode (GML_DENSE_LIB=1 / exact products) and this call runs %s it: '
+                         'rebuild them in the mode they are used in (dense_supports / batch_supports)' % (('outside', 'inside') if library else ('inside', 'outside')))
+    if library:
         Fn._path('dense', 'support product (torch.bmm fp32)', S, Fin, Fout)
         D = sup.blocks if not bank else (sup.blocks[:B] if gid is None else sup.blocks[gid.long()])
         h = torch.bmm(D.reshape(B, S * n, n), x.view(B, n, Fin))
         h = h.view(B, S, n, Fin).permute(0, 2, 1, 3).reshape(B * n, S * Fin)
+    elif road.chained:
+        return _DenseConv.apply(x, weight, bias, sup, relu)
     else:
-        kind = _kind(sup)
-        fmax = MID_F if kind == 'batched blocks' else BIG_F if kind else 128
-        if Fin > fmax:
-            raise ValueError('the dense-block kernel covers Fin <= %d at n = %d, got %d' % (fmax, n, Fin))
-        if CHAIN and Fout <= 128 and n <= SMALL_N:
-            return _DenseConv.apply(x, weight, bias, sup, relu)
         h = _SupportProduct.apply(x, sup, gid)
     out = _TallGemm.apply(h, weight.reshape(S * Fin, Fout), bias)
     return torch.relu(out) if relu else out

@@ -226,7 +226,7 @@ def _layer_bn(model, i, x, nvalid):
     return bn(x) if nvalid is None else bn(x, valid=nvalid)
 
 
-# Road choice of a node-level GNNML3 on ONE large graph (GNNML3._dense_big): the dense road (dense_block.py on
+# Road choice of a node-level GNNML3 on ONE large graph (gnnml3_road): the dense road (dense_block.py on
 # csrc/gml_dense_big.hip) is taken from this mask fill E / N^2 upwards.  Measured (tools/bench_filtering.py,
 # profiles/filtering_twodgrid.json: one ML3 layer 48 -> 32 + 16 forward + backward on the 30 x 30 grid, S = 11, ms sparse / dense,
 # both roads alternating in one process):
@@ -235,6 +235,31 @@ def _layer_bn(model, i, x, nvalid):
 # The sparse road is faster at fill 0.0137, the dense road from 0.0412 upwards (1.07 x there, 3.0 x at 0.13, 8.3 x at the filtering
 # graph's own 0.40): the constant sits between the two.
 DENSE_BIG_MIN_FILL = 0.025
+
+# The road of ONE GNNML3 forward.  kind: 'sparse' (CSR kernels), 'dense_n' (the model's own equal-size blocks), 'big' (ONE large
+# graph, csrc/gml_dense_big.hip) or 'mid' (the slots of an EqualSupports bank, csrc/gml_dense_mid.hip); chain: whether the relu
+# hand-over between stacked sparse layers is declared for this call.
+GNNML3Road = namedtuple('GNNML3Road', 'kind chain')
+
+
+def gnnml3_road(head, dense_n, bn, learnedge, fmax, chain, num_graphs, N, E, pad_graph, bank, road=None, drop=False, min_fill=DENSE_BIG_MIN_FILL):
+    """GNNML3Road from plain values only (no tensor, no launch).  The model: head, dense_n, bn, any learnedge, its widest conv input
+    fmax, GNNML3._chain.  The batch: graphs, N nodes, E support edges (None: no edge tensors), pad_graph, whether it carries an
+    EqualSupports bank.  road: forward's _road override; drop: a dropout pass."""
+    from .dense_block import big_applies
+    plain = not (dense_n or bn or pad_graph or learnedge)
+    if bank and plain and road != 'sparse':                    # opt-in through the bank: no fill threshold picks it
+        kind = 'mid'
+    elif bank and E is None:
+        raise ValueError("the sparse road cannot serve this batch: it has no edge tensors (DeviceDataset.batch_dense: x, y and bank slots only); "
+                         "the sparse road needs a batch collated with edge_index2 / edge_attr2")
+    # by itself: a node-level model (every pooled model keeps the sparse road) on ONE graph of 96 < N <= 1024 nodes whose mask fill
+    # E / N^2 reaches min_fill, supports used as they are, layer inputs within the kernel's features; the override is not checked
+    elif road == 'dense' if road else (head == 'node' and plain and E is not None and big_applies(num_graphs, N, fmax) and E >= min_fill * N * N):
+        kind = 'big'
+    else:
+        kind = 'dense_n' if dense_n else 'sparse'
+    return GNNML3Road(kind, bool(chain) and not drop and kind == 'sparse')
 
 
 class GNNML3(torch.nn.Module):
@@ -272,6 +297,7 @@ class GNNML3(torch.nn.Module):
         widths = list(nout1) if isinstance(nout1, (list, tuple)) else [nout1] * nlayers    # per-layer nout1
         self.nlayers, self.bn, self.pool, self.head, self.readout_bn = nlayers, bn, pool, head, readout_bn
         fin = ninp
+        self._learnedge, self._fin_max = bool(learnedge), max([ninp] + [w + nout2 for w in widths[:nlayers - 1]])   # (what gnnml3_road reads of the layers)
         for i in range(nlayers):
             setattr(self, 'conv%d' % (i + 1),
                     ML3Layer(learnedge=learnedge, nedgeinput=ne, nedgeoutput=ne,
@@ -280,10 +306,11 @@ class GNNML3(torch.nn.Module):
             if bn:
                 setattr(self, 'bn%d' % (i + 1), BatchNorm1d(fin))
         self._chain = chain and not bn and not self.dense_n
+        self._chain_on = bool(self._chain)                      # what is declared now: forward() re-declares on a change only
         if self._chain:
             # x = conv2(conv1(x, ...), ...) with nothing else reading the intermediate outputs (Zinc12k.py:338-341,
-            # counting.py:361-366, sr25.py:266-270): the relu hand-over between stacked layers applies.  With dropout in training a
-            # dropout sits between the layers instead: forward() withdraws the declaration for such passes (_declare_chain)
+            # counting.py:361-366, sr25.py:266-270): the relu hand-over between stacked layers applies on the sparse road, outside
+            # dropout passes (a dropout sits between the layers there): gnnml3_road says so per call
             self._declare_chain(True)
         nin = fin * (len(pool) if isinstance(pool, tuple) else 1)
         if readout_bn:                       # TF ReadoutLayer: batch_normalization of the pooled vector
@@ -299,44 +326,42 @@ class GNNML3(torch.nn.Module):
         for i in range(1, self.nlayers):
             getattr(self, 'conv%d' % (i + 1)).chain_after(getattr(self, 'conv%d' % i) if on else None)
 
-    def _dense_big(self, data):
-        """Road of this batch, from host integers only (number of graphs, N, E, learnedge): True = the large-graph dense road.
-        ONE graph of 96 < N <= 1024 nodes whose mask fill E / N^2 reaches DENSE_BIG_MIN_FILL, supports used as they are
-        (learnedge=False), layer inputs within the kernel's 64 features.  Node-level models only: every pooled model keeps the
-        sparse road it has always taken."""
-        from .dense_block import big_applies
-        if self.head != 'node' or self.dense_n or self.bn or getattr(data, 'pad_graph', False):
-            return False
-        N, E = int(data.x.size(0)), int(data.edge_index2.size(1))
-        fmax = max(int(getattr(self, 'conv%d' % (i + 1)).conv1.weight.size(1)) for i in range(self.nlayers))
-        if any(getattr(self, 'conv%d' % (i + 1)).learnedge for i in range(self.nlayers)):
-            return False
-        return big_applies(int(data.ptr.numel()) - 1, N, fmax) and E >= DENSE_BIG_MIN_FILL * N * N
-
-    def _dense_mid(self, data):
-        """True when this batch can take the batched dense road (dense_block.py on csrc/gml_dense_mid.hip): it carries an
-        EqualSupports bank (DeviceDataset.batch_dense / dense_block.attach_bank), no layer learns its supports, and none of bn /
-        dense_n / pad_graph is on.  The road is opt-in through the bank: no fill threshold picks it."""
+    def _road_of(self, data, _road=None, drop=False):
+        """gnnml3_road of this model on this batch: host integers and flags only"""
         from .dense_block import EqualSupports
-        if not isinstance(getattr(data, 'bank', None), EqualSupports):
-            return False
-        if self.dense_n or self.bn or getattr(data, 'pad_graph', False):
-            return False
-        return not any(getattr(self, 'conv%d' % (i + 1)).learnedge for i in range(self.nlayers))
+        ei2 = getattr(data, 'edge_index2', None)
+        return gnnml3_road(self.head, self.dense_n, self.bn, self._learnedge, self._fin_max, self._chain, int(data.ptr.numel()) - 1,
+                           int(data.x.size(0)), None if ei2 is None else int(ei2.size(1)), bool(getattr(data, 'pad_graph', False)),
+                           isinstance(getattr(data, 'bank', None), EqualSupports), _road, drop)
 
-    def _forward_dense_big(self, data, x, drop, bank=None, gid=None):
-        """cat[relu(dense conv), tanh(fc11 x) * tanh(fc12 x)] per layer on the dense blocks of the one graph (cached on the batch
-        like the CSR), or on the slots gid of an EqualSupports bank.  The support product and its adjoint are
-        gml_dense_big_support_mm (bank: gml_dense_mid_support_mm), the projection and its gradients the tall GEMM of dense_block.py;
-        under exact_products() the fp32 library product serves."""
-        from .dense_block import dense_supports, spectconv_dense, _library
-        if bank is not None:
-            sp, n = bank, bank.n
-        else:
-            n = int(x.size(0))
-            sp = getattr(data, '_spT', None)
-            if sp is None or sp.n != n or (sp.blocks is not None) != bool(_library()):
-                sp = data._spT = dense_supports(data.edge_index2, data.edge_attr2, data.ptr, n)
+    def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False, _road=None):
+        """_road (tests and tools/bench_filtering.py): 'dense' / 'sparse' overrides the road choice of gnnml3_road for a batch both
+        roads cover; None: the choice.  A batch with an EqualSupports bank takes the batched dense road unless _road='sparse',
+        which needs the batch's edge tensors (ValueError without them)."""
+        if getattr(data, 'pad_graph', False) and self.training and (self.readout_bn or self.pool_bn is not None):
+            # the padding graph's pooled row would enter the batch statistics of the readout BatchNorm (ADVICE r04)
+            raise NotImplementedError('readout BatchNorm takes plain batches: a padded static batch (pad_graph) would count its padding '
+                                      'row in the statistics')
+        drop = _dropout_pass(self)
+        road = self._road_of(data, _road, drop)
+        if road.chain != self._chain_on:
+            # the relu hand-over is withdrawn for dropout passes and on the dense roads, and back for the next sparse call
+            self._declare_chain(road.chain)
+            self._chain_on = road.chain
+        nvalid = _bn_valid(self, data, self.bn)
+        if road.kind == 'sparse':
+            x, pooled = self._forward_sparse(data, drop, nvalid, _pad_grad_zero)
+            return self._readout(x, data, pooled, _features, _capture)
+        from .dense_block import batch_supports
+        n = data.bank.n if road.kind == 'mid' else self.dense_n if road.kind == 'dense_n' else int(data.x.size(0))
+        sp, gid = (data.bank, getattr(data, 'gid', None)) if road.kind == 'mid' else (batch_supports(data, n), None)
+        return self._readout(self._forward_dense(data.x, drop, nvalid, sp, n, gid), data, False, _features, _capture)
+
+    def _forward_dense(self, x, drop, nvalid, sp, n, gid):
+        """cat[relu(dense conv), tanh(fc11 x) * tanh(fc12 x)] per layer (and its BatchNorm: dense_n models only) on the dense blocks
+        sp of graphs of n nodes: the batch's own (dense_block.batch_supports) or the slots gid of an EqualSupports bank.  Which
+        kernel serves the support product is dense_block.dense_road's answer; under exact_products() the fp32 library product."""
+        from .dense_block import spectconv_dense
         for i in range(self.nlayers):
             layer = getattr(self, 'conv%d' % (i + 1))
             if drop:
@@ -345,54 +370,17 @@ class GNNML3(torch.nn.Module):
             if layer.nout2 > 0:
                 Fn._path('dense', 'Hadamard half (library GEMMs + tanh)', '-', int(x.size(1)), layer.nout2)
                 a = torch.cat([a, torch.tanh(tall_linear(x, layer.fc11)) * torch.tanh(tall_linear(x, layer.fc12))], 1)
-            x = a
+            x = _layer_bn(self, i + 1, a, nvalid) if self.bn else a
         return x
 
-    def forward(self, data, _features=False, _capture=None, _pad_grad_zero=False, _road=None):
-        """_road (tests and tools/bench_filtering.py): 'dense' / 'sparse' overrides the road choice of _dense_big for a batch both
-        roads cover; None: the choice.  A batch with an EqualSupports bank (_dense_mid) takes the batched dense road unless
-        _road='sparse', which needs the batch's edge tensors (ValueError without them)."""
-        x = data.x
-        padded = getattr(data, 'pad_graph', False)
-        if padded and self.training and (self.readout_bn or self.pool_bn is not None):
-            # the padding graph's pooled row would enter the batch statistics of the readout BatchNorm (ADVICE r04)
-            raise NotImplementedError('readout BatchNorm takes plain batches: a padded static batch (pad_graph) would count its padding '
-                                      'row in the statistics')
-        drop = _dropout_pass(self)
-        if self._chain and self.dropout > 0:
-            self._declare_chain(not drop)
-        nvalid = _bn_valid(self, data, self.bn)
-        mid = self._dense_mid(data) and _road != 'sparse'        # a batch with an EqualSupports bank: the batched dense road
-        if not mid and getattr(data, 'bank', None) is not None and getattr(data, 'edge_index2', None) is None:
-            raise ValueError("the sparse road cannot serve this batch: it has no edge tensors (DeviceDataset.batch_dense: x, y and bank slots only); "
-                             "the sparse road needs a batch collated with edge_index2 / edge_attr2")
-        big = False if mid else self._dense_big(data) if _road is None else (_road == 'dense')
-        if self.head == 'node' and self._chain:
-            # the relu hand-over between stacked sparse layers is withdrawn on the dense road (as dense_n does at construction)
-            self._declare_chain(not big and not drop)
-        if self._chain and (mid or getattr(self, '_mid_withdrawn', False)):
-            self._declare_chain(not mid and not big and not drop)   # withdrawn on the batched dense road too, back for the next sparse batch
-            self._mid_withdrawn = mid
-        if big:
-            return self._readout(self._forward_dense_big(data, x, drop), data, False, _features, _capture)
-        if mid:
-            x = self._forward_dense_big(data, x, drop, bank=data.bank, gid=getattr(data, 'gid', None))
-            return self._readout(x, data, False, _features, _capture)
-        if self.dense_n:
-            from .dense_block import dense_supports, spectconv_dense, _library
-            sp = getattr(data, '_spT', None)                    # per-batch data, like the CSR
-            if sp is None or (sp.blocks is not None) != bool(_library()):
-                data._spT = dense_supports(data.edge_index2, data.edge_attr2, data.ptr, self.dense_n)
-        else:
-            csr = data.csr('edge_index2')
-        pooled = False
+    def _forward_sparse(self, data, drop, nvalid, _pad_grad_zero):
+        """the layers on the CSR kernels: (x, whether the last layer pooled already)"""
+        x, csr, pooled = data.x, data.csr('edge_index2'), False
         for i in range(self.nlayers):
             layer = getattr(self, 'conv%d' % (i + 1))
             if drop:
                 x = Fn.dropout(x, self.dropout, True, self.dropout_state, site=i)
-            if self.dense_n:
-                x = spectconv_dense(x, data._spT, layer.conv1.weight, layer.conv1.bias, self.dense_n, relu=True)
-            elif i == self.nlayers - 1 and not self.bn and self.pool in ('add', 'mean') and torch.is_grad_enabled():
+            if i == self.nlayers - 1 and not self.bn and self.pool in ('add', 'mean') and torch.is_grad_enabled():
                 # the pool directly follows the last layer: one autograd node, the pool's gradient is not expanded to [N, C]
                 if getattr(data, '_batch_i32', None) is None:
                     data._batch_i32 = data.batch.to(torch.int32).contiguous()
@@ -403,14 +391,13 @@ class GNNML3(torch.nn.Module):
                 # BatchNorm layers behind the first layer amplify the ~1e-5 relative error of the split bf16 products in ITS weight /
                 # bias gradients past 1e-4 of their scale (mutag.py:272-288: 1.6e-4 measured): that one layer runs on the exact
                 # f32-product kernels, forward and backward (the narrowest layer of the stack: 8 -> 48 features)
-                from . import functional as _Fn
-                with _Fn.exact_products():
+                with Fn.exact_products():
                     x = layer(x, csr, data.edge_attr2)
             else:
                 x = layer(x, csr, data.edge_attr2)
             if self.bn:
                 x = _layer_bn(self, i + 1, x, nvalid)
-        return self._readout(x, data, pooled, _features, _capture)
+        return x, pooled
 
     def _readout(self, x, data, pooled, _features, _capture):
         """pool (unless the last layer pooled already, or the model is node-level), the readout normalisations and the head"""

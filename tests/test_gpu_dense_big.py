@@ -166,7 +166,7 @@ def test_outside_the_range(dev):
                  mask=(torch.rand(n, 1, generator=g) < 0.7).float()).to(dev)
     torch.manual_seed(0)
     m = models.filtering_gnnml3(1, S).to(dev)
-    assert not m._dense_big(data)
+    assert m._road_of(data).kind != 'big'
     old, Fn.VERBOSE = Fn.VERBOSE, True
     Fn.PATHS.clear()
     try:

@@ -243,3 +243,114 @@ def test_dense_supports_takes_batches_of_mid_size_graphs(dev):
     with pytest.raises(ValueError):                             # three graphs of 300 nodes: no dense kernel
         ei2, ea2, ptr = _coo(_blocks(300, dev, graphs=3, S=1))
         DB.dense_supports(ei2, ea2, ptr, 300)
+
+
+# ------------------------------------------------------------------ the mode of the call decides the road, not the supports'
+def _coo_by_source(blocks):
+    """_coo with a symmetric union mask and the edges sorted by source, as SpectralDesign emits them (both roads read these)"""
+    Gb, S, n, _ = blocks.shape
+    mask = (blocks != 0).any(1)
+    bb, ii, jj = torch.nonzero((mask | mask.transpose(1, 2)).transpose(1, 2), as_tuple=True)
+    ptr = torch.arange(Gb + 1, dtype=torch.int32, device=blocks.device) * n
+    return torch.stack([bb * n + ii, bb * n + jj]), blocks[bb, :, jj, ii].contiguous(), ptr
+
+
+def test_supports_built_in_the_other_mode_raise(dev):
+    """spectconv_dense takes the road from the library mode of THE CALL; supports that hold the other side raise before any launch"""
+    from gnn_matlang_amd import dense_block as DB, functional as Fn
+    n, F = 4, 3
+    g = torch.Generator(device='cpu').manual_seed(4)
+    blocks = torch.randn(1, 1, n, n, generator=g).to(dev)
+    ei2, ea2, ptr = _coo(blocks)
+    x, w = torch.randn(n, F, generator=g).to(dev), torch.randn(1, F, 2, generator=g).to(dev)
+    ref = (blocks[0, 0].double() @ x.double()) @ w[0].double()
+    outside = DB.dense_supports(ei2, ea2, ptr, n)
+    assert outside.blocks is None and outside.fwd is not None
+    with Fn.exact_products():
+        inside = DB.dense_supports(ei2, ea2, ptr, n)
+        assert inside.blocks is not None and inside.fwd is None
+        with pytest.raises(ValueError, match='rebuild'):
+            DB.spectconv_dense(x, outside, w, None, n)
+        y_in = DB.spectconv_dense(x, inside, w, None, n)
+    with pytest.raises(ValueError, match='rebuild'):
+        DB.spectconv_dense(x, inside, w, None, n)
+    y_out = DB.spectconv_dense(x, outside, w, None, n)
+    assert rel_err(y_in.cpu().numpy(), ref.cpu().numpy()) <= TOL and rel_err(y_out.cpu().numpy(), ref.cpu().numpy()) <= TOL
+    # the cache on a batch follows the mode
+    data = type('B', (), {})()
+    data.edge_index2, data.edge_attr2, data.ptr = ei2, ea2, ptr
+    a = DB.batch_supports(data, n)
+    assert a.fwd is not None and DB.batch_supports(data, n) is a
+    with Fn.exact_products():
+        b = DB.batch_supports(data, n)
+        assert b is not a and b.blocks is not None and DB.batch_supports(data, n) is b
+    assert DB.batch_supports(data, n).fwd is not None
+
+
+_ROADS = {}
+
+
+def _road_case(kind, dev):
+    """(model, batch, _road, the dense_road arguments (graphs, n, bank)) of one forward of each kind; the 97-node data built once"""
+    from gnn_matlang_amd import dense_block as DB, models
+    from gnn_matlang_amd.graph import Batch
+    if not _ROADS:
+        torch.manual_seed(5)
+        g = torch.Generator(device='cpu').manual_seed(6)
+        n, S = 97, 2
+        blocks = _blocks(n, dev, graphs=2, S=S)
+        ei2, ea2, ptr = _coo_by_source(blocks)
+        one = ei2[0] < n
+        x = torch.randn(2 * n, 1, generator=g).to(dev)
+        node = models.GNNML3(1, S, 8, 4, 2, learnedge=False, pool=None, head='node').to(dev)
+        single = Batch(x=x[:n].contiguous(), edge_index2=ei2[:, one].contiguous(), edge_attr2=ea2[one].contiguous(),
+                       batch=torch.zeros(n, dtype=torch.int64, device=dev), ptr=ptr[:2].contiguous())
+        banked = DB.attach_bank(Batch(x=x, batch=torch.arange(2, device=dev).repeat_interleave(n), ptr=ptr), DB.EqualSupports(ei2, ea2, ptr))
+        n5 = 5
+        b5 = (torch.randn(2, S, n5, n5, generator=g) * 0.3).to(dev)
+        ei5, ea5, ptr5 = _coo_by_source(b5)
+        small = Batch(x=torch.randn(2 * n5, 3, generator=g).to(dev), edge_index2=ei5, edge_attr2=ea5,
+                      batch=torch.arange(2, device=dev).repeat_interleave(n5), ptr=ptr5)
+        pooled = models.GNNML3(3, S, 8, 0, 2, learnedge=False, pool='add', head='mlp32', dense_n=n5).to(dev)
+        _ROADS.update(dense_n=(pooled, small, None, (2, n5, False)), big=(node, single, None, (1, n, False)),
+                      mid=(node, banked, None, (2, n, True)), sparse=(node, single, 'sparse', None))
+    return _ROADS[kind]
+
+
+@pytest.mark.parametrize('kind', ['dense_n', 'big', 'mid', 'sparse'])
+def test_one_forward_and_backward_per_road(dev, kind):
+    """the paths one GNNML3 step records are exactly those its two road records name"""
+    from gnn_matlang_amd import dense_block as DB, functional as Fn
+    m, data, _road, shape = _road_case(kind, dev)
+    assert m._road_of(data, _road) == (kind, kind == 'sparse')
+    old, Fn.VERBOSE = Fn.VERBOSE, True
+    Fn.PATHS.clear()
+    try:
+        m.zero_grad(set_to_none=True)
+        out = m(data, _road=_road)
+        out.sum().backward()
+        paths = set(Fn.PATHS)
+    finally:
+        Fn.VERBOSE = old
+        Fn.PATHS.clear()
+    assert torch.isfinite(out).all() and all(p.grad is not None and torch.isfinite(p.grad).all() for p in m.parameters())
+    dense = {k for k in paths if k.startswith('dense: ')}
+    csr = {k for k in paths if k.startswith('conv_fwd') or k.startswith('conv_bwd')}
+    if kind == 'sparse':
+        assert csr and not dense, paths
+        return
+    want = set()
+    for i in range(m.nlayers):
+        layer = getattr(m, 'conv%d' % (i + 1))
+        S, Fin, Fout = layer.conv1.weight.shape
+        r = DB.dense_road(shape[0], shape[1], Fin, Fout, shape[2], False)
+        assert r.product == {'dense_n': 'small', 'big': 'big', 'mid': 'mid'}[kind] and r.chained == (kind == 'dense_n')
+        if r.chained:
+            names, widths = ('support product + projection chained (bf16x3 HIP)', 'projection + support product chained, backward (bf16x3 HIP)'), (Fin, Fout)
+        else:
+            names, widths = ('support product fwd (bf16x3 HIP%s)' % r.label, 'support product bwd (bf16x3 HIP%s)' % r.label), (Fin, Fin)
+        for name in names[:2 if i else 1]:                           # (the first layer's input needs no gradient)
+            want.add('dense: %s (S=%s Fin=%s Fout=%s)' % ((name, S) + widths))
+        if layer.nout2:
+            want.add('dense: Hadamard half (library GEMMs + tanh) (S=- Fin=%s Fout=%s)' % (Fin, layer.nout2))
+    assert dense == want and not csr, (sorted(dense), sorted(want), sorted(csr))

@@ -156,7 +156,7 @@ def test_model_on_small_grids(dev, a, b, recfield, fill_lo, fill_hi, road):
     torch.manual_seed(11)
     m = models.filtering_gnnml3(1, 11).to(dev)
     state = {k: v.clone() for k, v in m.state_dict().items()}
-    assert m._dense_big(data) == (fill >= models.DENSE_BIG_MIN_FILL)         # the road the model takes by itself
+    assert (m._road_of(data).kind == 'big') == (fill >= models.DENSE_BIG_MIN_FILL)         # the road the model takes by itself
     pre, loss, grads, paths, stats = _run_road(m, data, road)
     _assert_road(paths, road)
     pre_ref, loss_ref, P = _oracle(state, data, 1)
@@ -167,7 +167,7 @@ def test_model_on_small_grids(dev, a, b, recfield, fill_lo, fill_hi, road):
     for k, gk in grads.items():
         _close(gk, P[k].grad, 'grad ' + k)
     # the road the model chooses by itself gives what the forced call gave, bit for bit
-    own = 'dense' if m._dense_big(data) else 'sparse'
+    own = 'dense' if m._road_of(data).kind == 'big' else 'sparse'
     if own == road:
         pre2, loss2, _, paths2, _ = _run_road(m, data, None)
         _assert_road(paths2, road)
