@@ -326,47 +326,59 @@ def conv_epilogue(csr, x, val, w, bias, S, epilogue, ds, self_term, ncols):
 FWD_CHUNKS = _os.environ.get('GML_FWD_CHUNKS', '1') not in ('0', '')
 
 
-def fwd_groups(csr, x, S, Fin, Fout):
-    """(group records, extra flags) the forward kernel wants for this shape: the 8-wave kernel on 128-row records when
-    the shape is compiled for it, else the 64-row kernel."""
-    flags = _lib.GML_F32_MFMA if exact_mode() else 0
+# How one conv forward runs (decided once, by _conv_fwd_road): rows = the group records it walks (128: the 8-wave kernels, 64: the 4-wave
+# family), flags = what the launch adds to the caller's, label = its GML_VERBOSE text; gathers = the SHAPE is one of the 8-wave kernel's
+# (whatever this batch then runs on): a training ML3Layer then keeps its edge branch in source order and the conv gathers the rows
+ConvFwdRoad = _collections.namedtuple('ConvFwdRoad', 'rows flags label gathers')
+
+
+def _conv_fwd_road(S, Fin, Fout, exact, gmax, N, stride, ptr16, chunks):
+    """ConvFwdRoad from plain values only (no tensor, no launch)"""
+    # gmax: (edges, column window) of the largest 128-row group of the target view, None when unknown; N, stride, ptr16: rows of x, their
+    # stride in floats, x's address % 16; chunks: the FWD_CHUNKS switch
+    flags = _lib.GML_F32_MFMA if exact else 0
     L = _lib.lib()
-    rows = int(L.gml_spectconv_fwd_group_rows(int(S), int(Fin), int(Fout), flags))
-    # a window bound without GML_FWD_CHUNKED: only the chunked ring kernel (fwd4) serves the shape on 128-row records
-    win4 = int(L.gml_spectconv_fwd_stage_window(int(S), int(Fin), int(Fout), flags))
-    gm_known = getattr(csr, 'gmax128', None) is not None
-    gm_e, gm_w = csr.gmax128 if gm_known else (0, 0)
-    x4 = x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-    # the chunked ring kernel (fwd4) addresses x with 32-bit byte offsets and needs the real group maxima to check its window: without
-    # either, the 64-row family (any size, global gathers where a group does not fit) -- ADVICE r04
-    small32 = (int(csr.N) + 16) * int(x.stride(0)) * 4 < 2 ** 31
+    shape = (int(S), int(Fin), int(Fout))
+    rows = int(L.gml_spectconv_fwd_group_rows(*shape, flags))
+    road = lambda rows_, fl, label: ConvFwdRoad(rows_, fl, label, rows == 128)
     if rows == 128:
-        cap = int(L.gml_spectconv_fwd_stage_edges(int(S), int(Fin), int(Fout), flags))      # edges of one work item of the ring kernel
-        if win4:                                  # fwd4 alone: known maxima, 32-bit offsets, float4 rows, windows it can stage
-            if not (gm_known and small32 and x4) or gm_w > win4 or (gm_e > cap and not FWD_CHUNKS):
-                rows = 64
-            elif gm_e > cap:
-                # 48 features: one staged X window instead of two -> twice the edges per chunk (sr25: 2 chunks per group instead of 4)
-                onewin = _lib.GML_FWD_ONEWIN if Fin > 32 else 0
-                _path('conv_fwd', 'fused 8-wave bf16x3, edge chunks%s' % (', one X window' if onewin else ''), S, Fin, Fout)
-                return csr.ginfo128, _lib.GML_GROUPS128 | onewin
-        elif cap > 0 and gm_e > cap and FWD_CHUNKS and x4 and small32:
+        # a window bound without GML_FWD_CHUNKED: only the chunked ring kernel (fwd4) serves the shape on 128-row records
+        win4 = int(L.gml_spectconv_fwd_stage_window(*shape, flags))
+        cap = int(L.gml_spectconv_fwd_stage_edges(*shape, flags))      # edges of one work item of the ring kernel
+        gm_e, gm_w = gmax if gmax is not None else (0, 0)
+        # the chunked ring kernel (fwd4) addresses x with 32-bit byte offsets, reads float4 rows and needs the real group maxima to check
+        # its window: without any of them, the 64-row family (any size, global gathers where a group does not fit) -- ADVICE r04
+        ring_ok = stride % 4 == 0 and ptr16 == 0 and (int(N) + 16) * int(stride) * 4 < 2 ** 31
+        if win4 and (not (gmax is not None and ring_ok) or gm_w > win4 or (gm_e > cap and not chunks)):
+            pass                                  # fwd4 alone serves the shape and cannot serve this batch: the 64-row family
+        elif win4 and gm_e > cap:
+            # 48 features: one staged X window instead of two -> twice the edges per chunk (sr25: 2 chunks per group instead of 4)
+            onewin = _lib.GML_FWD_ONEWIN if Fin > 32 else 0
+            return road(128, _lib.GML_GROUPS128 | onewin, 'fused 8-wave bf16x3, edge chunks%s' % (', one X window' if onewin else ''))
+        elif (not win4 and cap > 0 and gm_e > cap and chunks and ring_ok
+              and gm_w <= int(L.gml_spectconv_fwd_stage_window(*shape, flags | _lib.GML_FWD_CHUNKED))):
             # a group beyond what the default ring kernel stages at once: its chunked form instead of global gathers
-            win = int(L.gml_spectconv_fwd_stage_window(int(S), int(Fin), int(Fout), flags | _lib.GML_FWD_CHUNKED))
-            if gm_w <= win:
-                _path('conv_fwd', 'fused 8-wave bf16x3, edge chunks', S, Fin, Fout)
-                return csr.ginfo128, _lib.GML_GROUPS128 | _lib.GML_FWD_CHUNKED
-    if rows == 128:
-        _path('conv_fwd', 'fused 8-wave bf16x3', S, Fin, Fout)
-        return csr.ginfo128, _lib.GML_GROUPS128
-    _path('conv_fwd', 'fused 4-wave (%s)' % ('f32 MFMA' if (exact_mode() or Fin <= 16 or Fout > 32) else 'bf16x3'), S, Fin, Fout)
-    return csr.ginfo, 0
+            return road(128, _lib.GML_GROUPS128 | _lib.GML_FWD_CHUNKED, 'fused 8-wave bf16x3, edge chunks')
+        else:
+            return road(128, _lib.GML_GROUPS128, 'fused 8-wave bf16x3')
+    return road(64, 0, 'fused 4-wave (%s)' % ('f32 MFMA' if (exact or Fin <= 16 or Fout > 32) else 'bf16x3'))
+
+
+# (group records, extra flags) of a ConvFwdRoad; records its GML_VERBOSE label
+def _conv_fwd_records(csr, road, S, Fin, Fout):
+    _path('conv_fwd', road.label, S, Fin, Fout)
+    return (csr.ginfo128 if road.rows == 128 else csr.ginfo), road.flags
+
+
+def fwd_groups(csr, x, S, Fin, Fout):
+    """(group records, extra flags) the forward kernel wants for this shape and this x (the tensor properties _conv_fwd_road decides on)"""
+    return _conv_fwd_records(csr, _conv_fwd_road(S, Fin, Fout, bool(exact_mode()), getattr(csr, 'gmax128', None), csr.N, int(x.stride(0)),
+                                                 x.data_ptr() % 16, FWD_CHUNKS), S, Fin, Fout)
 
 
 def fwd_gathers(S, Fin, Fout):
     """True when the forward of this shape runs on the 8-wave kernel, which can take its value rows through a position map."""
-    flags = _lib.GML_F32_MFMA if exact_mode() else 0
-    return int(_lib.lib().gml_spectconv_fwd_group_rows(int(S), int(Fin), int(Fout), flags)) == 128
+    return _conv_fwd_road(S, Fin, Fout, bool(exact_mode()), None, 0, 4, 0, FWD_CHUNKS).gathers
 
 
 def ml3_edge_in_source_order(csr, S, Fin, Fout):
@@ -515,8 +527,34 @@ def _edge_path(fam, arith, S, L=0):
         _path('edge', ('stack of %d layers in one pass, ' % L if L > 1 else '') + what, S, '-', S)
 
 
-def edge_mlp_fwd(ea, w1, w2, w3, w4, tpos=None, ea_split=None):
-    """returns out (same edge order as ea) and, when tpos is given, the same rows at out_t[tpos[e]]."""
+# family (include/gml.h GML_EDGE_FAM_*), the arithmetic it runs on and the entry point of one edge-branch forward; entry None: no kernel
+EdgeFwd = _collections.namedtuple('EdgeFwd', 'family arith entry')
+
+
+def _edge_fwd_family(S, So, L, arith, has_split, dual, pairs):
+    """EdgeFwd of L layers' edge branches in one pass (L = 1: one layer); every gml_edge_mlp_plan query of the forward is made here."""
+    # has_split / dual: the pre-split rows are there / the scattered second copy is wanted; pairs: the batch has a unique-row list.
+    # Unique rows where the plan has them, else the stacked kernel (L > 1; exact: none) or the single-layer entry of `arith`.
+    NONE = _lib.GML_EDGE_FAM_NONE
+    plan = lambda n, ar, fl: int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(So), n, ar | fl))
+    flags = (_lib.GML_EDGE_HAS_SPLIT if has_split else 0) | (_lib.GML_EDGE_DUAL if dual and L == 1 else 0)
+    # the unique support rows only (gml_edge_chain_sym_impl.h): every output row is written, by its own entry or by its mirror's
+    fam = plan(L, arith, _lib.GML_EDGE_UNIQUE) if pairs else NONE
+    if fam != NONE:
+        return EdgeFwd(fam, arith, 'gml_edge_mlp_fwd_stack6_sym')
+    if L > 1:
+        fam = plan(L, arith, flags)
+        return EdgeFwd(fam, arith, {NONE: None, _lib.GML_EDGE_FAM_CHAIN6: 'gml_edge_mlp_fwd_stack6'}.get(fam, 'gml_edge_mlp_fwd_stack'))
+    fam = plan(0, arith, flags)
+    if fam == NONE and arith == _lib.GML_EDGE_THREE_PIECE:      # S = 1 has no three-piece form: the default entry
+        arith = _lib.GML_EDGE_TWO_PIECE
+        fam = plan(0, arith, flags)
+    # exact arithmetic covers the edge branch too (round 5: it did not); the three-piece entry (fp32-class) reads the fp32 rows itself
+    return EdgeFwd(fam, arith, None if fam == NONE else ('gml_edge_mlp_fwd', 'gml_edge_mlp_fwd6', 'gml_edge_mlp_fwd_exact')[arith])
+
+
+def edge_mlp_fwd(ea, w1, w2, w3, w4, tpos=None, ea_split=None, fam=None):
+    """returns out (same edge order as ea) and, when tpos is given, the same rows at out_t[tpos[e]]; fam: the caller's EdgeFwd, if any"""
     E, S = ea.shape
     So = w4.size(0)
     if So != S:
@@ -525,22 +563,12 @@ def edge_mlp_fwd(ea, w1, w2, w3, w4, tpos=None, ea_split=None):
         return out[:, :So].contiguous(), (out_t[:, :So].contiguous() if out_t is not None else None)
     out = torch.empty(E, So, dtype=torch.float32, device=ea.device)
     out_t = torch.empty(E, So, dtype=torch.float32, device=ea.device) if tpos is not None else None
-    arith = _edge_arith()
-    flags = (_lib.GML_EDGE_HAS_SPLIT if ea_split is not None else 0) | (_lib.GML_EDGE_DUAL if tpos is not None else 0)
-    fam = int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(So), 0, arith | flags))
-    if fam == _lib.GML_EDGE_FAM_NONE and arith == _lib.GML_EDGE_THREE_PIECE:      # S = 1 has no three-piece form: the default entry
-        arith = _lib.GML_EDGE_TWO_PIECE
-        fam = int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(So), 0, arith | flags))
-    if fam == _lib.GML_EDGE_FAM_NONE:
+    fam = fam or _edge_fwd_family(S, So, 1, _edge_arith(), ea_split is not None, tpos is not None, False)
+    if fam.entry is None:
         _lib.check(_lib.GML_E_UNSUPPORTED)
-    _edge_path(fam, arith, S)
-    tail = (_ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4), _ptr(out), _ptr(tpos), _ptr(out_t), int(E), int(S), int(So), _stream(ea.device))
-    if arith == _lib.GML_EDGE_EXACT:                      # exact arithmetic covers the edge branch too (round 5: it did not)
-        _lib.call('gml_edge_mlp_fwd_exact', _ptr(ea), *tail)
-    elif arith == _lib.GML_EDGE_THREE_PIECE:              # three-piece products (fp32-class), reads the fp32 rows itself
-        _lib.call('gml_edge_mlp_fwd6', _ptr(ea), *tail)
-    else:
-        _lib.call('gml_edge_mlp_fwd', _ptr(ea), _ptr(ea_split), *tail)
+    _edge_path(fam.family, fam.arith, S)
+    _lib.call(fam.entry, _ptr(ea), *((_ptr(ea_split),) if fam.arith == _lib.GML_EDGE_TWO_PIECE else ()), _ptr(w1), _ptr(w2), _ptr(w3), _ptr(w4),
+              _ptr(out), _ptr(tpos), _ptr(out_t), int(E), int(S), int(So), _stream(ea.device))
     return out, out_t
 
 
@@ -554,35 +582,25 @@ EDGE_FWD6 = _os.environ.get('GML_EDGE_FWD6', '1') not in ('0', '')
 EDGE_SYM = _os.environ.get('GML_EDGE_SYM', '1') not in ('0', '')
 
 
-def edge_mlp_fwd_stack(ea, ea_split, weights, sym=None):
+def edge_mlp_fwd_stack(ea, ea_split, weights, sym=None, fam=None):
     """The edge branches of several layers on the SAME supports in one pass (gml_edge_mlp_fwd_stack): weights = [(w1, w2, w3, w4)]
     per layer; returns the list of outputs [E, S] (edge order of ea), or None when the library has no stacked kernel for the shape."""
-    import ctypes
+    # sym: the batch's unique-row list; fam: the EdgeFwd the caller resolved for this call (default: asked here)
     E, S = ea.shape
     L = len(weights)
-    if not ((1 if sym is not None else 2) <= L <= 4) or any(w[3].size(0) != S or w[0].size(1) != S for w in weights):
+    if fam is None and not any(w[3].size(0) != S or w[0].size(1) != S for w in weights):
+        fam = _edge_fwd_family(S, S, L, _edge_arith(), ea_split is not None, False, sym is not None and EDGE_SYM)
+    if fam is None or 'stack' not in (fam.entry or ''):
         return None
-    arith = _edge_arith()                                 # (exact: no stacked kernel, the plan answers none)
-    plan = lambda flags: int(_lib.lib().gml_edge_mlp_plan(_lib.GML_EDGE_FWD, int(S), int(S), L, arith | flags))
-    # the unique support rows only (gml_edge_chain_sym_impl.h): every output row is written, by its own entry or by its mirror's
-    fam = plan(_lib.GML_EDGE_UNIQUE) if (sym is not None and EDGE_SYM) else _lib.GML_EDGE_FAM_NONE
-    if fam == _lib.GML_EDGE_FAM_NONE:
-        fam = plan(_lib.GML_EDGE_HAS_SPLIT if ea_split is not None else 0)
-    if fam == _lib.GML_EDGE_FAM_NONE:
-        return None
-    _edge_path(fam, arith, S, L)
+    _edge_path(fam.family, fam.arith, S, L)
     outs = [torch.empty(E, S, dtype=torch.float32, device=ea.device) for _ in range(L)]
     arr = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
     tail = [arr([w[i] for w in weights]) for i in range(4)] + [arr(outs), int(E), int(S), int(S), _stream(ea.device)]
-    if fam in (_lib.GML_EDGE_FAM_SYM6, _lib.GML_EDGE_FAM_SYM16X6):
-        if len(sym) == 3:                                 # (uid, mir, count): the entry count lives on the device (an assembled batch)
-            _lib.call('gml_edge_mlp_fwd_stack6_sym_dev', _ptr(ea), _ptr(sym[0]), _ptr(sym[1]), _ptr(sym[2]), int(sym[0].numel()), L, *tail)
-        else:
-            _lib.call('gml_edge_mlp_fwd_stack6_sym', _ptr(ea), _ptr(sym[0]), _ptr(sym[1]), int(sym[0].numel()), L, *tail)
-    elif fam == _lib.GML_EDGE_FAM_CHAIN6:
-        _lib.call('gml_edge_mlp_fwd_stack6', _ptr(ea), L, *tail)
+    if fam.entry == 'gml_edge_mlp_fwd_stack6_sym':
+        # (uid, mir, count): the entry count lives on the device (an assembled batch)
+        _lib.call(fam.entry + '_dev' if len(sym) == 3 else fam.entry, _ptr(ea), *[_ptr(t) for t in sym], int(sym[0].numel()), L, *tail)
     else:
-        _lib.call('gml_edge_mlp_fwd_stack', _ptr(ea_split), L, *tail)
+        _lib.call(fam.entry, _ptr(ea if fam.entry == 'gml_edge_mlp_fwd_stack6' else ea_split), L, *tail)
     return outs
 
 
@@ -1821,6 +1839,91 @@ def _ml3_stage_separate(road, csr, g, gy, gy_seg, out, x, ea, ea_t, cw, fc):
     return r
 
 
+# How one ML3Layer forward runs (decided once, by _ml3_fwd_road; DESIGN s4.3c has the table):
+#   edge      None (the supports as they are) / 'branch' (the kernels of the edge plan, inside ML3LayerFunction) / 'wide' (EdgeBranchWide,
+#             17 .. 48 supports) / 'library' (GEMMs under autograd)
+#   order     of the branch: 'source_raw' (source order, the supports as given: no value sort) / 'source' (after a gather) / 'dual' (target
+#             order, the second copy scattered into source order by the edge kernel) / 'target'
+#   layers    edge branches in the pass: 0 = none (the head of the stack left this layer's output in the stash), 2 .. 4 = the layers
+#             stacked on this one ride along
+#   pairs     the view ('source' / 'target') in which csr.sym_index is asked for the batch's unique rows, or None: not asked
+#   hadamard  None / 'fused' (inside gml_ml3_fwd) / 'library';  pool  None / 'plain' / 'pattern' (the pool leaves the relu pattern)
+#   chain_in / chain_out  the hand-over tokens the backward keeps;  conv  the ConvFwdRoad
+ML3FwdRoad = _collections.namedtuple('ML3FwdRoad', 'edge order layers pairs hadamard pool chain_in chain_out conv')
+
+
+def _ml3_fwd_road(Se, S, Fin, nout1, nout2, E, learnedge, grad_on, wanted, sup, stash, succ, pooled, exact, arith, bwd, conv,
+                  chain_in_cols=None, edge_stack=True, edge_sym=True, chain=True, bwd_had=True, wide_lib=False):
+    """ML3FwdRoad from plain values only (no tensor, no launch).  Whether the batch HAS pairs is data: the road says where to ask."""
+    # Se / S: supports into the edge branch / into the conv; grad_on, wanted: autograd records, any input wants a gradient; sup: the
+    # supports as the caller holds them -- (2-D float32 contiguous [E, .], Se wide, carry a gradient, csr.src_sorted); stash: a stash hit;
+    # succ: stackable layers on top; arith: _edge_arith(); bwd: the conv backward of (S, Fin, nout1) has a fused plan; conv: ConvFwdRoad
+    plain, width, sup_grad, src_sorted = sup
+    mixk = nout2 > 0 and node_mix_native(Fin, nout2)
+    edge, order, layers, pairs = None, None, 0, None
+    if learnedge and max(Se, S) > 16:
+        # more than 16 supports (no script goes beyond counting.py's 12; the sr25 sweep of SURVEY s8d raises nfreq to 47)
+        edge = 'wide' if (max(Se, S) <= 48 and width and not wide_lib) else 'library'
+    elif learnedge:
+        # When the fused backward will run, the edge branch lives in SOURCE order (the order that kernel walks): the raw supports in that
+        # order are per-batch data (SpectralDesign emits source-sorted edges: the input itself, no value sort at all), the branch writes
+        # its output once, and the forward conv gathers the rows through tpos.  (r02: emitting both orders from the edge kernel cost it
+        # 37 % -- it is HBM-bound and the second copy was a scattered 32-byte-row write: 'dual' is left to the forward kernels without
+        # the gather.)  Inference / unfused training: target order.
+        edge, layers = 'branch', 1
+        if src_sorted and grad_on and plain and width and not sup_grad and S == Se and bwd and conv.gathers:
+            order = 'source_raw'
+            stacks = succ > 0 and edge_stack and _edge_fwd_family(Se, Se, 1 + succ, arith, E > 0, False, False).entry is not None
+            layers = 0 if stash else 1 + succ if stacks else 1
+        else:
+            order = 'target' if not (wanted and bwd) else 'source' if conv.gathers else 'dual' if E * Se * 4 < 0xffffff00 else 'target'
+        # unique support rows only where the batch pairs up: per-batch data (no gradient), one copy, a square branch (a padded one has no such form)
+        if edge_sym and layers and not (sup_grad and grad_on) and order != 'dual' and S == Se:
+            pairs = 'target' if order == 'target' else 'source'
+    keep = chain and edge != 'wide' and edge != 'library'
+    pool = None if not pooled else 'pattern' if _pool_relu_pattern(bwd_had, mixk, nout1, nout2, exact, wanted) else 'plain'
+    return ML3FwdRoad(edge, order, layers, pairs, None if nout2 == 0 else 'fused' if mixk else 'library', pool,
+                      bool(keep and chain_in_cols is not None and chain_in_cols <= Fin), bool(keep and not pooled), conv)
+
+
+# row stride of rows4(_f32rows(x)): x's own where the kernels read its rows as they are, else the zero-padded copy's
+def _rows4_stride(x):
+    asis = x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.size(1) and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+    return int(x.stride(0)) if asis else (int(x.size(-1)) + 3) // 4 * 4
+
+
+def _road_text(road):
+    return ' '.join('%s=%s' % (k, getattr(v, 'kind', None) or v.label if k == 'conv' else int(v) if isinstance(v, bool) else v)
+                    for k, v in zip(road._fields, road))
+
+
+def ml3_fwd_road(csr, x, Se, S, Fin, nout1, nout2, learnedge, grad_on, wanted, sup, stash=False, succ=0, pooled=False, chain_in_cols=None):
+    """ML3FwdRoad of one layer call: the switches, the arithmetic and the plain properties of csr and x are read here, once"""
+    exact = bool(exact_mode())
+    conv = _conv_fwd_road(S, Fin, nout1, exact, getattr(csr, 'gmax128', None), csr.N, _rows4_stride(x), 0, FWD_CHUNKS)
+    bwd = bool(learnedge and grad_on and max(Se, S) <= 16 and fused_bwd_available(csr, S, Fin, nout1))
+    road = _ml3_fwd_road(int(Se), int(S), int(Fin), int(nout1), int(nout2), csr.E, learnedge, grad_on, wanted, sup, stash, succ, pooled,
+                         exact, _edge_arith(), bwd, conv, chain_in_cols, EDGE_STACK, EDGE_SYM, CHAIN, BWD_HAD,
+                         bool(_os.environ.get('GML_EDGE_WIDE_LIB')))
+    if VERBOSE:
+        _path('ml3_fwd', _road_text(road), S, Fin, nout1)
+    return road
+
+
+def _ml3_edge_fwd(road, csr, val, weights, tpos):
+    """the edge branches of road.layers layers on val in ONE launch; returns (outputs, the first one's scattered copy or None)"""
+    # weights = [(w1, w2, w3, w4)] per layer; the family is resolved once, with the batch's answer about pairs
+    (E, Se), L = val.shape, road.layers
+    with _Timed('edge_mlp_fwd', 4 * val.numel() * (L + (2 if tpos is not None else 1)), 20 * E * Se ** 2 * L):
+        split = csr.presplit(val) if L > 1 else None
+        sym = csr.sym_index(val, road.pairs) if road.pairs else None
+        fam = _edge_fwd_family(Se, weights[0][3].size(0), L, _edge_arith(), Se <= 16 and E > 0, tpos is not None, sym is not None)
+        if 'stack' in (fam.entry or ''):                   # (GML_VERBOSE: the edge functions record the family the plan named)
+            return edge_mlp_fwd_stack(val, split, weights, sym, fam), None
+        out, out_t = edge_mlp_fwd(val, *weights[0], tpos, csr.presplit(val), fam)
+        return [out], out_t
+
+
 class ML3LayerFunction(torch.autograd.Function):
     """Whole ML3Layer.forward (libs/spect_conv.py:204-212) with the concat written in place:
          ea' = edge-MLP(val)                      (learnedge)
@@ -1829,8 +1932,9 @@ class ML3LayerFunction(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, val, w1, w2, w3, w4, cw, cb, w11, b11, w12, b12, csr, learnedge, nout2, val_is_source=False,
-                pool_ptr=None, pool_seg=None, pool_mean=False, chain_in=None, chain_out=None, ea_pre=None, stack=None):
+    def forward(ctx, x, val, w1, w2, w3, w4, cw, cb, w11, b11, w12, b12, csr, learnedge, nout2, road,
+                pool_ptr=None, pool_seg=None, pool_mean=False, chain_in=None, chain_out=None, ea_pre=None, stack=((), [])):
+        # road: the ML3FwdRoad the caller decided (ml3_fwd_road) -- this forward runs it
         # ea_pre: this layer's edge-branch output in source order, already computed by the first layer of its stack; stack =
         # (weights of the layers stacked on this one [(w1, w2, w3, w4)], list that receives their edge-branch outputs): the
         # layers all read the same raw supports, one pass serves them (edge_mlp_fwd_stack)
@@ -1838,92 +1942,55 @@ class ML3LayerFunction(torch.autograd.Function):
         # this layer's own token, which the consumer of its output sets (see ChainToken)
         # pool_ptr / pool_seg (int32 [B+1] / [N]): the layer is directly followed by global_add_pool / global_mean_pool
         # (Zinc12k.py:343): the pooled [B, C] tensor is returned and the pool's gradient is never expanded to [N, C]
-        # val_is_source: val holds the raw supports in SOURCE order (the caller checked ml3_edge_in_source_order and that they
-        # carry no gradient); otherwise target-sorted order
+        # val: the raw supports in SOURCE order when road.order is 'source_raw'; otherwise target-sorted order
         x, val, cw = _f32rows(x, 'x'), _f32c(val, 'edge_attr'), _f32c(cw, 'conv1.weight')
         S, Fin, nout1 = cw.shape
-        N = csr.N
+        N, C = csr.N, nout1 + nout2
         if x.size(0) != N or x.size(1) != Fin or val.size(0) != csr.E:
             raise ValueError('shape mismatch: x %s, edge_attr %s, conv1.weight %s, graph N=%d E=%d'
                              % (tuple(x.shape), tuple(val.shape), tuple(cw.shape), N, csr.E))
-        C = nout1 + nout2
         with torch.cuda.device(x.device):
             x = rows4(x)
-            epos = None
+            ea, ea_t, epos = val, None, None
             if learnedge:
-                w1, w2, w3, w4 = (_f32c(w1, 'fc1_1.weight'), _f32c(w2, 'fc1_2.weight'), _f32c(w3, 'fc1_3.weight'),
-                                  _f32c(w4, 'fc1_4.weight'))
-                # When the fused backward will run, the edge branch lives in SOURCE order (the order that kernel walks): the raw
-                # supports in that order are per-batch data (for source-sorted input: the input itself), the branch writes
-                # its output once, and the forward conv gathers the rows through tpos (target position -> source position).
-                # (r02: emitting both orders from the edge kernel cost it 37 % -- it is HBM-bound and the second copy was a
-                # scattered 32-byte-row write.)
-                fused_b = any(ctx.needs_input_grad) and fused_bwd_available(csr, S, Fin, nout1)
-                src_order = bool(val_is_source) or (fused_b and fwd_gathers(S, Fin, nout1))
-                # (forward kernels without the gather: both orders from the edge kernel, second copy scattered through tpos)
-                dual = fused_b and not src_order and val.numel() * 4 < 0xffffff00
-                if src_order:
-                    val_s = val if val_is_source else csr.to_source_order(val, cache=not val.requires_grad)
-                    ea_t = ea_pre if val_is_source else None
-                    if ea_t is None and stack is not None and val_is_source:
-                        ws_ = [(w1, w2, w3, w4)] + [tuple(_f32c(t, 'edge branch weight') for t in w) for w in stack[0]]
-                        with _Timed('edge_mlp_fwd', 4 * val.numel() * (1 + len(ws_)), 20 * val.size(0) * val.size(1) ** 2 * len(ws_)):
-                            outs = edge_mlp_fwd_stack(val_s, csr.presplit(val_s), ws_, csr.sym_index(val_s) if EDGE_SYM else None)
-                        if outs is not None:                # (GML_VERBOSE: the edge functions record the family the plan named)
-                            ea_t = outs[0]
-                            stack[1].extend(outs[1:])
-                    if ea_t is None:
-                        with _Timed('edge_mlp_fwd', 4 * val.numel() * 2, 20 * val.size(0) * val.size(1) ** 2):
-                            sym_ = csr.sym_index(val_s) if (EDGE_SYM and not val.requires_grad) else None
-                            one = edge_mlp_fwd_stack(val_s, None, [(w1, w2, w3, w4)], sym_) if sym_ is not None else None
-                            ea_t = one[0] if one is not None else edge_mlp_fwd(val_s, w1, w2, w3, w4, None, csr.presplit(val_s))[0]
-                    ea, epos = ea_t, csr.tpos
+                assert road.edge == 'branch', 'more than 16 supports: ML3Layer runs that edge branch outside this function'
+                ws_ = [tuple(_f32c(t, 'edge branch weight') for t in w) for w in [(w1, w2, w3, w4)] + list(stack[0])]
+                w1, w2, w3, w4 = ws_[0]
+                if road.layers == 0:
+                    ea = ea_pre
                 else:
-                    with _Timed('edge_mlp_fwd', 4 * val.numel() * (3 if dual else 2), 20 * val.size(0) * val.size(1) ** 2):
-                        # (inference / unfused training: target order; unique support rows only where the batch pairs up)
-                        sym_ = csr.sym_index(val, 'target') if (EDGE_SYM and not dual and not val.requires_grad and w4.size(0) == val.size(1)) else None
-                        one = edge_mlp_fwd_stack(val, None, [(w1, w2, w3, w4)], sym_) if sym_ is not None else None
-                        if one is not None:
-                            ea, ea_t = one[0], None
-                        else:
-                            ea, ea_t = edge_mlp_fwd(val, w1, w2, w3, w4, csr.tpos if dual else None, csr.presplit(val))
-            else:
-                ea, ea_t = val, None
+                    val_s = csr.to_source_order(val, cache=not val.requires_grad) if road.order == 'source' else val
+                    (ea, *rest), ea_t = _ml3_edge_fwd(road, csr, val_s, ws_, csr.tpos if road.order == 'dual' else None)
+                    stack[1].extend(rest)                         # (the stacked layers' outputs: the caller stashes them)
+                if road.order in ('source_raw', 'source'):        # the conv gathers the rows through tpos (target position -> source position)
+                    ea_t, epos = ea, csr.tpos
             if ea.size(1) != S:
                 raise ValueError('conv1 expects %d supports, edge branch produced %d' % (S, ea.size(1)))
             out = torch.empty(N, C, dtype=torch.float32, device=x.device)
             cb_ = _f32c(cb, 'conv1.bias') if cb is not None else None
-            gi, gflag = fwd_groups(csr, x, S, Fin, nout1)
-            if nout2 > 0:
-                w11, b11, w12, b12 = (_f32c(w11, 'fc11.weight'), _f32c(b11, 'fc11.bias'), _f32c(w12, 'fc12.weight'),
-                                      _f32c(b12, 'fc12.bias'))
+            gi, gflag = _conv_fwd_records(csr, road.conv, S, Fin, nout1)
+            mixk = road.hadamard == 'fused'
             q, f = conv_cost(N, int(ea.size(0)), S, Fin, nout1) if PROFILE is not None else (0, 0)
-            mixk = nout2 > 0 and node_mix_native(Fin, nout2)
             if nout2 > 0:
+                w11, b11, w12, b12 = (_f32c(t, n) for t, n in zip((w11, b11, w12, b12), ('fc11.weight', 'fc11.bias', 'fc12.weight', 'fc12.bias')))
                 _path('hadamard', 'fused kernels' if mixk else 'library GEMMs (ninp > 64 or nout2 > 24)', '-', Fin, nout2)
             with _Timed('spectconv_fwd', q, f):                    # conv (+ Hadamard branch of the same rows)
                 _lib.call('gml_ml3_fwd', _ptr(csr.rowptr), _ptr(csr.col), _ptr(gi), _ptr(epos), _ptr(ea), _ptr(x), int(x.stride(0)), _ptr(cw),
-                          Fin * nout1, nout1, 1, _ptr(cb_), _ptr(w11 if mixk else None),
-                          _ptr(b11 if mixk else None), _ptr(w12 if mixk else None),
-                          _ptr(b12 if mixk else None), _ptr(out), C, N, S, Fin, nout1, int(nout2) if mixk else 0,
-                          _lib.GML_RELU | gflag | _fwd_arith_flags(), _stream(x.device))
+                          Fin * nout1, nout1, 1, _ptr(cb_), *[_ptr(t if mixk else None) for t in (w11, b11, w12, b12)], _ptr(out), C, N, S, Fin,
+                          nout1, int(nout2) if mixk else 0, _lib.GML_RELU | gflag | _fwd_arith_flags(), _stream(x.device))
             if nout2 > 0 and not mixk:
                 # ninp > 64 or nout2 > 24 (ptc.py:331-338 has ninp = 80): two plain library GEMMs + elementwise
                 out[:, nout1:] = torch.tanh(_linear(x, w11, b11)) * torch.tanh(_linear(x, w12, b12))
         ctx.csr, ctx.learnedge, ctx.nout2, ctx.has_cb = csr, learnedge, nout2, cb is not None
-        ctx.exact = bool(exact_mode())
-        ctx.src_order = epos is not None
-        ctx.val_is_source = bool(val_is_source)
+        ctx.exact, ctx.src_order, ctx.val_is_source = bool(exact_mode()), epos is not None, road.order == 'source_raw'
         ctx.pool = (pool_ptr, pool_seg, int(pool_mean)) if pool_ptr is not None else None     # bit 0 mean, bit 1 GML_POOL_SKIP_LAST
-        ctx.chain_in = chain_in if (CHAIN and chain_in is not None and chain_in.cols <= Fin) else None
-        ctx.chain_out = chain_out if (CHAIN and ctx.pool is None) else None
+        ctx.chain_in, ctx.chain_out = chain_in if road.chain_in else None, chain_out if road.chain_out else None
         ctx.save_for_backward(x, val, (ea if learnedge and epos is None else None), w1, w2, w3, w4, cw, w11, b11, w12, b12, out, ea_t)
         ctx.pool_mask = None
         if ctx.pool is not None:
-            if _pool_relu_pattern(BWD_HAD, mixk, nout1, nout2, exact_mode(), any(ctx.needs_input_grad)):
-                pooled, ctx.pool_mask = segment_sum_mask(out, pool_ptr, int(pool_mean) & 3)
-            else:
-                pooled = segment_sum(out, pool_ptr, int(pool_mean) & 3)
+            pooled = (segment_sum_mask if road.pool == 'pattern' else segment_sum)(out, pool_ptr, int(pool_mean) & 3)
+            if road.pool == 'pattern':                         # (the pool also leaves the relu pattern of every row)
+                pooled, ctx.pool_mask = pooled
             if int(pool_mean) & 2:
                 skip_last_mask(pooled)                         # (created outside any later graph capture of the backward)
             return pooled
@@ -1955,8 +2022,7 @@ class ML3LayerFunction(torch.autograd.Function):
                              ctx.chain_out is not None and ctx.chain_out.premasked,
                              ctx.chain_in.cols if ctx.chain_in is not None else None, _rows_of(gy), x4)
         if VERBOSE:
-            _path('ml3_bwd', ' '.join('%s=%s' % (k, v.kind if k == 'conv' else int(v) if isinstance(v, bool) else v)
-                                      for k, v in zip(road._fields, road)), S, Fin, nout1)
+            _path('ml3_bwd', _road_text(road), S, Fin, nout1)
         # the hand-over tokens are read once: this layer's is cleared, the lower layer's set when dx leaves with its relu applied
         if ctx.chain_out is not None:
             ctx.chain_out.premasked = False

@@ -12,8 +12,6 @@ row keeps the reference's edge order; the projection is accumulated in a differe
 required (only ``aggr='add'``, ``flow='source_to_target'``, ``node_dim=0`` exist in the reference).
 """
 import math
-import os
-
 import weakref
 
 import torch
@@ -260,6 +258,7 @@ class _EpilogueFn(torch.autograd.Function):
 _CHAIN_STATE = weakref.WeakKeyDictionary()
 # per ML3Layer instance: (key of supports + weight versions, edge-branch output the head of its stack computed for it)
 _EDGE_STASH = weakref.WeakKeyDictionary()
+_EDGE_FCS = ('fc1_1', 'fc1_2', 'fc1_3', 'fc1_4')
 
 
 class ML3Layer(torch.nn.Module):
@@ -297,33 +296,27 @@ class ML3Layer(torch.nn.Module):
         return self
 
     def _edge_key(self, val, csr):
-        w = (self.fc1_1.weight, self.fc1_2.weight, self.fc1_3.weight, self.fc1_4.weight)
+        w = (getattr(self, n).weight for n in _EDGE_FCS)
         # val._version: supports rewritten IN PLACE in the same buffer (a static batch buffer) must not be served the branch
         # output of the old ones
         return (val.data_ptr(), val._version, tuple(val.shape), id(csr)) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in w)
 
     def _edge_stack(self, val, csr):
-        """(ea_pre, stack) for ML3LayerFunction: this layer's edge-branch output if the head of its stack already computed it
-        for exactly these supports and these weight versions; otherwise, for a layer with layers stacked on it that read the
-        same supports (chain_after), the request to compute theirs in the same pass."""
+        """(ea_pre, succ) for the road of this call: what the head of this layer's stack left for it, else the layers stackable on it"""
+        # ea_pre: this layer's edge-branch output, computed for exactly these supports and these weight versions; succ: the layers
+        # stacked on this one that read the same supports (chain_after) through a branch of the same shape: one pass can serve them
         hit = _EDGE_STASH.pop(self, None)
         if hit is not None and hit[0] == self._edge_key(val, csr):
-            return hit[1], None
-        if not Fn.EDGE_STACK:
-            return None, None
+            return hit[1], []
         succ, cur = [], self
         while cur._chain_next and len(succ) < 3:
             nxt = cur._chain_next[0]
             if not (nxt.learnedge and all(getattr(nxt, n).weight.shape == getattr(self, n).weight.shape and
-                                          getattr(nxt, n).weight.device == val.device for n in ('fc1_1', 'fc1_2', 'fc1_3', 'fc1_4'))):
+                                          getattr(nxt, n).weight.device == val.device for n in _EDGE_FCS)):
                 break
             succ.append(nxt)
             cur = nxt
-        if not succ:
-            return None, None
-        for m in succ:                                        # whatever an interrupted / partial forward left behind
-            _EDGE_STASH.pop(m, None)
-        return None, ([tuple(getattr(m, n).weight.detach() for n in ('fc1_1', 'fc1_2', 'fc1_3', 'fc1_4')) for m in succ], [], succ)
+        return None, succ
 
     def _chain_args(self, x):
         cin = None
@@ -341,58 +334,47 @@ class ML3Layer(torch.nn.Module):
 
     def forward(self, x, edge_index, edge_attr, _pool=None):
         _require_cuda(x, 'x')
+        _require_cuda(edge_attr, 'edge_attr')
         csr = csr_for(edge_index, x.size(0))
-        le, n2 = self.learnedge, self.nout2
-        if le and max(self.fc1_1.weight.size(1), self.fc1_4.weight.size(0)) > 16:
-            # more than 16 supports (no script goes beyond counting.py's 12; the sr25 sweep of SURVEY s8d raises nfreq to 47):
-            # the edge branch as four library GEMMs + elementwise under autograd (libs/spect_conv.py:205-207), the node branch on
-            # the fused kernels with the learned supports as its (differentiable) values
-            _require_cuda(edge_attr, 'edge_attr')
-            ea = edge_attr.to(torch.float32)
-            wide = max(self.fc1_1.weight.size(1), self.fc1_4.weight.size(0)) <= 48 and ea.size(1) == self.fc1_1.weight.size(1) \
-                and not os.environ.get('GML_EDGE_WIDE_LIB')
-            Fn._path('edge', 'one-launch kernel for 17..48 supports' if wide else 'library GEMMs (more than 48 supports)',
-                     self.fc1_1.weight.size(1), '-', self.fc1_4.weight.size(0))
-            if wide:
-                # round 5: gml_edge_mlp_wide_fwd (csrc/gml_edge_wide.hip) -- one launch, weights in LDS, nothing but e and out in HBM
-                ev = Fn.EdgeBranchWide.apply(ea.contiguous(), self.fc1_1.weight, self.fc1_2.weight, self.fc1_3.weight, self.fc1_4.weight)
-            else:
-                # fc1_4 applied to the two halves of its input separately: the concatenation of libs/spect_conv.py:205 is never
-                # materialised (at S = 48 it is a 2.5e9-element tensor: torch.cat alone took 83 ms of the layer's 90 on 13 M edges)
-                ev = Fn._edge_branch_torch(ea, self.fc1_1.weight, self.fc1_2.weight, self.fc1_3.weight, self.fc1_4.weight)
-            val = _sorted_values(csr, edge_index, ev, self.conv1.weight.size(0))
-            return ML3LayerFunction.apply(x, val, None, None, None, None, self.conv1.weight, self.conv1.bias,
-                                          self.fc11.weight if n2 > 0 else None, self.fc11.bias if n2 > 0 else None,
-                                          self.fc12.weight if n2 > 0 else None, self.fc12.bias if n2 > 0 else None,
-                                          csr, False, n2, False, *(_pool if _pool is not None else (None, None, False)))   # (no hand-over on this road)
-        # learnedge: fc1_1..3 are Linear(nedgeinput, .) -- the width must match, as in the reference; otherwise conv1
-        # reads the first K columns only
-        # Training with the edge branch: the branch runs in SOURCE order (functional.ML3LayerFunction).  SpectralDesign emits
-        # source-sorted edges, so the raw supports in that order are the input tensor itself: no value sort at all.
-        raw_src = (le and csr.src_sorted and torch.is_grad_enabled() and edge_attr.dim() == 2 and not edge_attr.requires_grad
-                   and edge_attr.dtype == torch.float32 and edge_attr.is_contiguous() and edge_attr.size(0) == csr.E
-                   and edge_attr.size(1) == self.fc1_1.weight.size(1) and self.fc1_4.weight.size(0) == edge_attr.size(1)
-                   and Fn.ml3_edge_in_source_order(csr, edge_attr.size(1), self.conv1.weight.size(1), self.conv1.weight.size(2)))
-        if raw_src:
-            _require_cuda(edge_attr, 'edge_attr')
+        le, n2, cw, cb = self.learnedge, self.nout2, self.conv1.weight, self.conv1.bias
+        ew = tuple(getattr(self, n).weight for n in _EDGE_FCS) if le else (None,) * 4
+        nw = (self.fc11.weight, self.fc11.bias, self.fc12.weight, self.fc12.bias) if n2 > 0 else (None,) * 4
+        pool = _pool if _pool is not None else (None, None, False)
+        # The road of this call, decided once (functional.ML3FwdRoad) from the supports as they arrive: learnedge: fc1_1..3 are
+        # Linear(nedgeinput, .) -- the width must match, as in the reference; otherwise conv1 reads the first K columns only
+        Se = ew[0].size(1) if le else cw.size(0)
+        two_d, grad_on = edge_attr.dim() == 2, torch.is_grad_enabled()
+        sup = (two_d and edge_attr.dtype == torch.float32 and edge_attr.is_contiguous() and edge_attr.size(0) == csr.E,
+               two_d and edge_attr.size(1) == Se, edge_attr.requires_grad, csr.src_sorted)
+        wanted = grad_on and any(t is not None and t.requires_grad for t in (x, edge_attr, cw, cb) + ew + nw)
+        ea_pre, succ = self._edge_stack(edge_attr, csr) if le else (None, [])
+        cin, cout = self._chain_args(x)
+        road = Fn.ml3_fwd_road(csr, x, Se, *cw.shape, n2, le, grad_on, wanted, sup, ea_pre is not None, len(succ), _pool is not None,
+                               cin.cols if cin is not None else None)
+        if road.edge in ('wide', 'library'):
+            # the edge branch under autograd, the node branch on the fused kernels with the learned supports as its (differentiable)
+            # values; no hand-over on this road
+            ea, wide = edge_attr.to(torch.float32), road.edge == 'wide'
+            Fn._path('edge', 'one-launch kernel for 17..48 supports' if wide else 'library GEMMs (more than 48 supports)', Se, '-', cw.size(0))
+            # wide, round 5: gml_edge_mlp_wide_fwd (csrc/gml_edge_wide.hip) -- one launch, weights in LDS, nothing but e and out in HBM
+            # library: four GEMMs + elementwise (libs/spect_conv.py:205-207), fc1_4 applied to the two halves of its input separately:
+            # the concatenation is never materialised (at S = 48 a 2.5e9-element tensor: torch.cat alone took 83 ms of the layer's 90
+            # on 13 M edges)
+            ev = Fn.EdgeBranchWide.apply(ea.contiguous(), *ew) if wide else Fn._edge_branch_torch(ea, *ew)
+            val = _sorted_values(csr, edge_index, ev, cw.size(0))
+            return ML3LayerFunction.apply(x, val, None, None, None, None, cw, cb, *nw, csr, False, n2, road, *pool)
+        if road.order == 'source_raw':
             val = edge_attr.detach()
         else:
-            val = _sorted_values(csr, edge_index, edge_attr, None if le else self.conv1.weight.size(0))
-        cin, cout = self._chain_args(x)
-        ea_pre, stack = self._edge_stack(val, csr) if raw_src else (None, None)
-        out = ML3LayerFunction.apply(
-            x, val,
-            self.fc1_1.weight if le else None, self.fc1_2.weight if le else None,
-            self.fc1_3.weight if le else None, self.fc1_4.weight if le else None,
-            self.conv1.weight, self.conv1.bias,
-            self.fc11.weight if n2 > 0 else None, self.fc11.bias if n2 > 0 else None,
-            self.fc12.weight if n2 > 0 else None, self.fc12.bias if n2 > 0 else None,
-            csr, le, n2, bool(raw_src), *(_pool if _pool is not None else (None, None, False)), cin, cout, ea_pre,
-            stack[:2] if stack is not None else None)
-        if stack is not None and len(stack[1]) == len(stack[2]):
-            # the layers stacked on this one find their edge-branch outputs here (same supports, same weight versions: checked)
-            for m, t in zip(stack[2], stack[1]):
-                _EDGE_STASH[m] = (m._edge_key(val, csr), t)
+            val = _sorted_values(csr, edge_index, edge_attr, None if le else cw.size(0))
+        succ = succ if road.layers > 1 else []
+        for m in succ:                                            # whatever an interrupted / partial forward left behind
+            _EDGE_STASH.pop(m, None)
+        stack = ([tuple(getattr(m, n).weight.detach() for n in _EDGE_FCS) for m in succ], [])
+        out = ML3LayerFunction.apply(x, val, *ew, cw, cb, *nw, csr, le, n2, road, *pool, cin, cout, ea_pre, stack)
+        # the layers stacked on this one find their edge-branch outputs here (same supports, same weight versions: checked)
+        for m, t in zip(succ, stack[1]):
+            _EDGE_STASH[m] = (m._edge_key(val, csr), t)
         if _pool is None and torch.is_grad_enabled():
             _CHAIN_STATE[self] = (weakref.ref(out), cout)       # the output tensor of this forward and its hand-over token
         else:

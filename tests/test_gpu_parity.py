@@ -2587,3 +2587,87 @@ def test_edge_branch_over_unique_rows_twelve_supports(dev):
     assert torch.equal(res[True][0], res[False][0])
     for n in res[True][1]:
         close(res[True][1][n], res[False][1][n], tol=3e-5, what='counting, shared vs plain ' + n)
+
+
+# road kind: (layers in the chain, supports, symmetric supports, supports carry a gradient, grad enabled, rows of the CPU table
+# (tests/test_ml3_fwd_road_cpu.py) the forward calls must record, 'edge' path of the branch)
+_FWD_ROAD_KINDS = {
+    'source + stack + pairs': (4, 8, True, False, True, ['zinc bottom layer, three stackable successors'] + ['the same on a stash hit'] * 3,
+                               'stack of 4 layers in one pass, matrix-core chain, three-piece, unique rows'),
+    'source single': (1, 8, False, False, True, ['EDGE_STACK off'], 'matrix-core chain, three-piece'),
+    'target + pairs under no_grad': (1, 8, True, False, False, ['grad disabled'], 'matrix-core chain, three-piece, unique rows'),
+    'supports with gradient': (1, 8, False, True, True, ['supports that carry a gradient'], 'matrix-core chain, three-piece'),
+    '20 supports (wide)': (1, 20, False, True, True, ['17 supports'], 'one-launch kernel for 17..48 supports'),
+    '50 supports (library)': (1, 50, False, True, True, ['49 supports'], 'library GEMMs (more than 48 supports)'),
+}
+
+
+@pytest.mark.parametrize('kind', sorted(_FWD_ROAD_KINDS))
+def test_ml3_forward_runs_the_road_its_record_names(dev, monkeypatch, kind):
+    """One forward and one backward per road kind of functional._ml3_fwd_road that can run for real, on two graphs of 20 nodes with 6
+    neighbours each, 32 -> 30 + 2: the `ml3_fwd` record of every layer call is the row of the CPU table (written out here from the
+    table's tuples, not by the code's formatter), the edge branch took the family that row names, and the output and every gradient
+    agree with the float64 oracle within TOL = 1e-4, the bar test_ml3layer_golden (the default roads) and test_ml3layer_wide_shapes
+    (trained supports, 17 .. 48 supports, the library GEMMs) hold these roads to.  Under no_grad there is no backward: outputs only."""
+    from gnn_matlang_amd import ML3Layer, functional as Fn
+    from oracle.spect_conv_oracle import OracleML3Layer
+    from oracle.relu_margin import make_safe, make_safe_edges
+    from test_ml3_fwd_road_cpu import TABLE
+    nl, S, symmetric, sup_grad, grad_on, rows, edge_path = _FWD_ROAD_KINDS[kind]
+    torch.manual_seed(71)
+    n, N = 20, 40
+    src = np.repeat(np.arange(N), 6)
+    dst = np.concatenate([(i // n) * n + (i % n + np.array([1, 2, 5, n - 1, n - 2, n - 5])) % n for i in range(N)])
+    o = np.lexsort((dst, src))                                 # source-sorted, columns ascending: as SpectralDesign emits
+    src, dst = src[o], dst[o]
+    ei = torch.from_numpy(np.stack([src, dst]).astype(np.int64))
+    refs = [OracleML3Layer(True, S, S, 32, 30, 2).double() for _ in range(nl)]
+    ms = [ML3Layer(True, S, S, 32, 30, 2).to(dev) for _ in range(nl)]
+    for m, r, lo in zip(ms, refs, [None] + ms):
+        m.load_state_dict({k: p.detach().float() for k, p in r.state_dict().items()})
+        if lo is not None:
+            m.chain_after(lo)
+    x, ea, go = torch.randn(N, 32), torch.randn(ei.size(1), S) * 0.5, torch.randn(N, 32)
+    if symmetric:                                              # an edge and its mirror carry bitwise the same row
+        for _ in range(20):                                    # (rows whose edge-branch relus keep their margin in EVERY layer)
+            before = ea.clone()
+            for r in refs:
+                ea = make_safe_edges(ea, *(getattr(r, 'fc1_%d' % i).weight.detach() for i in (1, 2, 3, 4)), scale=0.5)
+            if torch.equal(before, ea):
+                break
+        low = {(int(a), int(b)): k for k, (a, b) in enumerate(zip(src, dst))}
+        ea = torch.stack([ea[low[(min(a, b), max(a, b))]] for a, b in zip(src.tolist(), dst.tolist())])
+    elif nl == 1:
+        ea, mask = make_safe(x, ei, ea, refs[0].state_dict(), True)       # no relu argument within rounding of zero
+        go[:, :30] *= mask.float()
+    xr, er = x.double().requires_grad_(True), ea.double().requires_grad_(sup_grad)
+    yr = xr
+    for r in refs:
+        yr = r(yr, ei, er)
+    (yr * go.double()).sum().backward()
+    monkeypatch.setattr(Fn, 'VERBOSE', True)
+    Fn.PATHS.clear()
+    xg, eg, eid = x.to(dev).requires_grad_(True), ea.to(dev).requires_grad_(sup_grad), ei.to(dev)
+    with torch.set_grad_enabled(grad_on):
+        y = xg
+        for m in ms:
+            y = m(y, eid, eg)
+    paths = dict(Fn.PATHS)
+    want = {}
+    for name in rows:
+        rec, conv = TABLE[name][1], TABLE[name][2]
+        vals = [int(v) if isinstance(v, bool) else v for v in rec] + [conv[2]]
+        key = 'ml3_fwd: %s (S=%d Fin=32 Fout=30)' % (' '.join('%s=%s' % kv for kv in zip(Fn.ML3FwdRoad._fields, vals)), S)
+        want[key] = want.get(key, 0) + 1
+    assert {k: c for k, c in paths.items() if k.startswith('ml3_fwd:')} == want, paths
+    assert [k for k in paths if k.startswith('edge:')] == ['edge: %s (S=%d Fin=- Fout=%d)' % (edge_path, S, S)], paths
+    close(y, yr, what=kind + ' out')
+    if grad_on:
+        (y * go.to(dev)).sum().backward()
+        close(xg.grad, xr.grad, what=kind + ' g_x')
+        if sup_grad:
+            close(eg.grad, er.grad, what=kind + ' g_edge_attr')
+        for m, r in zip(ms, refs):
+            gp = dict(m.named_parameters())
+            for k, p in r.named_parameters():
+                close(gp[k].grad, p.grad, what='%s %s' % (kind, k))

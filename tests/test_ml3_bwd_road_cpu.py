@@ -139,7 +139,7 @@ def test_forward_and_backward_share_the_pool_mask_predicate(monkeypatch):
     """the forward pools with the relu pattern and the backward takes the masked road by the SAME function: both resolve the module's
     _pool_relu_pattern, the backward's answer implies the forward's on every pooled row of the table, and replacing the function
     moves the backward"""
-    assert '_pool_relu_pattern' in Fn.ML3LayerFunction.forward.__code__.co_names
+    assert '_pool_relu_pattern' in Fn._ml3_fwd_road.__code__.co_names       # (the forward's road: ML3LayerFunction.forward reads its .pool)
     assert '_pool_relu_pattern' in Fn._ml3_bwd_road.__code__.co_names
     for name, (kw, _) in TABLE.items():
         if kw.get('pool'):

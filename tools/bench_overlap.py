@@ -36,8 +36,10 @@ def edge_fwd():
 
 
 def conv_fwd():
+    # (the learned supports as plain target-sorted values: no edge branch, nothing wants a gradient)
+    road = Fn.ml3_fwd_road(csr, x, S, S, Fin, Fout, L.nout2, False, False, False, (False, False, False, csr.src_sorted))
     return Fn.ML3LayerFunction.apply(x, ea, None, None, None, None, cw, L.conv1.bias.detach(), L.fc11.weight.detach(), L.fc11.bias.detach(),
-                                     L.fc12.weight.detach(), L.fc12.bias.detach(), csr, False, L.nout2)
+                                     L.fc12.weight.detach(), L.fc12.bias.detach(), csr, False, L.nout2, road)
 
 
 def edge_bwd():
