@@ -55,7 +55,7 @@ class ChebConv(torch.nn.Module):
                 norm = Fn.cheb_norm(csr, batch, lambda_max)
             return Fn.ChebConvFunction.apply(x, csr, norm, self.weight, self.bias, act)
         if isinstance(edge_index, GraphCSR):
-            edge_index = Fn.gat_edge_index(edge_index)
+            edge_index = Fn.csr_edge_index(edge_index)
         Fn._path('cheb', 'torch ops (outside the fused layer)', K, int(x.size(1)), self.out_channels)
         return Fn.cheb_conv_torch(x, edge_index, self.weight, self.bias, batch, lambda_max, act)
 

@@ -20,57 +20,32 @@
 //                three rotating [N, Fin] buffers in the workspace; the last launch writes dx
 //             F  fold of the partials in ascending workgroup order -> dflat
 // No atomics; every sum has one order.  Plain fp32 fmaf / tanhf.  Column indices outside [0, N) are skipped, self loops dropped.
-#include "gml_img64.h"
+#include "gml_rowtile64.h"
 
-#define CHEB_W GML_I64_W
-#define CHEB_TR GML_I64_TR
-#define CHEB_RPW GML_I64_RPW
-#define CHEB_MAXWG 768      // workgroups of a launch (3 per CU)
 #define CHEB_KMAX 8
 
+// what an edge of `row` to column index j contributes (gml_rt_walk): self loops skipped, fmaf with the weight of the edge (j -> i),
+// (-(s[i] dis[i])) dis[j], where `row` is i in the target view and j in the source view
+template <bool TARGET_VIEW>
+struct cheb_edge {
+    const float* __restrict__ norm;
+    int64_t row;
+    float dr, ndr;                                                          // dis[row], -(s[row] dis[row])
+    __device__ __forceinline__ bool keep(int64_t j) const { return j != row; }
+    __device__ __forceinline__ float weight(int64_t j) const {
+        return TARGET_VIEW ? ndr * norm[2 * j] : (-(norm[2 * j + 1] * norm[2 * j])) * dr;
+    }
+    __device__ __forceinline__ float add(float acc, float w, float v) const { return fmaf(w, v, acc); }
+};
 // one (row, column) of L^ src (TARGET_VIEW: the CSR lists the sources of the target `row`) or of L^T src (the CSR lists the targets
-// of the source `row`): the edges in CSR order, then the diagonal.  The weight of an edge (j -> i) is (-(s[i] dis[i])) dis[j] in both.
+// of the source `row`): the edges in CSR order, then the diagonal
 template <bool TARGET_VIEW>
 static __device__ __forceinline__ float cheb_gather(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                     const float* __restrict__ norm, const float* src, int64_t ld, int64_t row, int c,
                                                     int64_t N) {
     const float dr = norm[2 * row], sr = norm[2 * row + 1];
-    const float ndr = -(sr * dr);
-    float acc = 0.f;
-    const int k0 = rowptr[row], k1 = rowptr[row + 1];
-    int k = k0;
-    for (; k + 4 <= k1; k += 4) {
-        int64_t j[4];
-        float v[4], w[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) j[u] = col[k + u];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool on = j[u] >= 0 && j[u] < N && j[u] != row;
-            v[u] = on ? src[j[u] * ld + c] : 0.f;
-            if (TARGET_VIEW) w[u] = on ? ndr * norm[2 * j[u]] : 0.f;
-            else w[u] = on ? (-(norm[2 * j[u] + 1] * norm[2 * j[u]])) * dr : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = fmaf(w[u], v[u], acc);
-    }
-    for (; k < k1; ++k) {
-        const int64_t j = col[k];
-        if (j >= 0 && j < N && j != row) {
-            const float w = TARGET_VIEW ? ndr * norm[2 * j] : (-(norm[2 * j + 1] * norm[2 * j])) * dr;
-            acc = fmaf(w, src[j * ld + c], acc);
-        }
-    }
+    const float acc = gml_rt_walk(rowptr, col, src, ld, row, c, N, 0.f, cheb_edge<TARGET_VIEW>{norm, row, dr, -(sr * dr)});
     return fmaf(sr - 1.f, src[row * ld + c], acc);
-}
-
-// the rows of a wave, lane = column: tile[(8 wave + r) 64 + lane] = src[row][lane] (0 beyond N and F)
-static __device__ __forceinline__ void cheb_load_rows(float* tile, const float* src, int64_t ld, int64_t r0, int64_t N, int F, int wave, int lane) {
-#pragma unroll
-    for (int r = 0; r < CHEB_RPW; ++r) {
-        const int64_t row = r0 + r;
-        tile[(wave * CHEB_RPW + r) * CHEB_W + lane] = (row < N && lane < F) ? src[row * ld + lane] : 0.f;
-    }
 }
 
 static __global__ __launch_bounds__(256) void cheb_k_norm(const int32_t* __restrict__ rowptr_t, const int32_t* __restrict__ col_t,
@@ -103,46 +78,38 @@ static __global__ __launch_bounds__(256) void cheb_k_step(const int32_t* __restr
                                                           int gp, const float* __restrict__ w0, const float* __restrict__ wk,
                                                           const float* __restrict__ bias, int Fout, int mode, int act, float* tk,
                                                           int64_t ldt, float* y, int64_t ldy, int64_t ntiles) {
-    __shared__ __attribute__((aligned(16))) float w0s[CHEB_W * CHEB_W];     // [in][out]
-    __shared__ __attribute__((aligned(16))) float wks[CHEB_W * CHEB_W];
-    __shared__ __attribute__((aligned(16))) float xs[CHEB_TR * CHEB_W];
-    __shared__ __attribute__((aligned(16))) float ts[CHEB_TR * CHEB_W];
+    __shared__ __attribute__((aligned(16))) float w0s[GML_RT_W * GML_RT_W];     // [in][out]
+    __shared__ __attribute__((aligned(16))) float wks[GML_RT_W * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float xs[GML_RT_TR * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float ts[GML_RT_TR * GML_RT_W];
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE;
-    if (mode & CHEB_X0) gml_i64_load_image<false>(w0s, w0, Fin, Fout, Fout);
-    if (mode & CHEB_GATHER) gml_i64_load_image<false>(wks, wk, Fin, Fout, Fout);
-    const int rpp = 64 / gp < CHEB_RPW ? 64 / gp : CHEB_RPW;               // rows of one gather pass
-    const int sub = lane / gp, c = lane % gp;
+    if (mode & CHEB_X0) gml_rt_load_image<false>(w0s, w0, Fin, Fout, Fout);
+    if (mode & CHEB_GATHER) gml_rt_load_image<false>(wks, wk, Fin, Fout, Fout);
     const int K4 = (Fin + 3) & ~3;
     const float b = (bias && lane < Fout) ? bias[lane] : 0.f;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t r0 = tile * CHEB_TR + wave * CHEB_RPW;
+        const int64_t r0 = tile * GML_RT_TR + wave * GML_RT_RPW;
         __syncthreads();                                                    // the images are in; the last tile's reads are over
-        if ((mode & CHEB_GATHER) && sub < rpp) {
-            for (int pp = 0; pp < CHEB_RPW; pp += rpp) {
-                const int64_t row = r0 + pp + sub;
-                float v = 0.f;
-                if (row < N && c < Fin) {
-                    v = cheb_gather<true>(rowptr, col, norm, p, ldp, row, c, N);
-                    if (q) v = fmaf(2.f, v, -q[row * ldq + c]);
-                    tk[row * ldt + c] = v;
-                }
-                ts[(wave * CHEB_RPW + pp + sub) * CHEB_W + c] = v;
-            }
-        }
-        if (mode & CHEB_X0) cheb_load_rows(xs, x, ldx, r0, N, Fin, wave, lane);
+        gml_rt_gather_rows(ts, r0, N, Fin, gp, wave, lane, (mode & CHEB_GATHER) != 0, [&](int64_t row, int c) {
+            float v = cheb_gather<true>(rowptr, col, norm, p, ldp, row, c, N);
+            if (q) v = fmaf(2.f, v, -q[row * ldq + c]);
+            tk[row * ldt + c] = v;
+            return v;
+        });
+        if (mode & CHEB_X0) gml_rt_load_rows(xs, x, ldx, r0, N, Fin, wave, lane);
         __syncthreads();
-        float acc[CHEB_RPW];
+        float acc[GML_RT_RPW];
 #pragma unroll
-        for (int r = 0; r < CHEB_RPW; ++r) {
+        for (int r = 0; r < GML_RT_RPW; ++r) {
             if (mode & CHEB_X0) acc[r] = b;
             else acc[r] = (lane < Fout && r0 + r < N) ? y[(r0 + r) * ldy + lane] : 0.f;
         }
-        if (mode & CHEB_X0) gml_i64_prod8(xs, w0s, K4, wave, lane, acc);
-        if (mode & CHEB_GATHER) gml_i64_prod8(ts, wks, K4, wave, lane, acc);
+        if (mode & CHEB_X0) gml_rt_prod8(xs, w0s, K4, wave, lane, acc);
+        if (mode & CHEB_GATHER) gml_rt_prod8(ts, wks, K4, wave, lane, acc);
         if (lane < Fout) {
 #pragma unroll
-            for (int r = 0; r < CHEB_RPW; ++r)
-                if (r0 + r < N) y[(r0 + r) * ldy + lane] = (mode & CHEB_LAST) ? gml_i64_act(acc[r], act) : acc[r];
+            for (int r = 0; r < GML_RT_RPW; ++r)
+                if (r0 + r < N) y[(r0 + r) * ldy + lane] = (mode & CHEB_LAST) ? gml_rt_act(acc[r], act) : acc[r];
         }
     }
 }
@@ -155,11 +122,11 @@ static __global__ __launch_bounds__(256) void cheb_k_bwd_r(const float* __restri
                                                            int64_t lddy, int64_t N, int Fin, const float* __restrict__ w, int Fout, int K,
                                                            int act, float* __restrict__ gl, int64_t ldgl, float* __restrict__ part,
                                                            int64_t P, int64_t ntiles, int64_t tpw) {
-    __shared__ __attribute__((aligned(16))) float wts[CHEB_W * CHEB_W];     // W_{K-1}^T: [out][in]
-    __shared__ __attribute__((aligned(16))) float gs[CHEB_TR * CHEB_W];
-    __shared__ __attribute__((aligned(16))) float as[CHEB_TR * CHEB_W];     // Tx_k
+    __shared__ __attribute__((aligned(16))) float wts[GML_RT_W * GML_RT_W];     // W_{K-1}^T: [out][in]
+    __shared__ __attribute__((aligned(16))) float gs[GML_RT_TR * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float as[GML_RT_TR * GML_RT_W];     // Tx_k
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE, tid = threadIdx.x;
-    if (gl) gml_i64_load_image<true>(wts, w + (int64_t)(K - 1) * Fin * Fout, Fout, Fin, Fout);
+    if (gl) gml_rt_load_image<true>(wts, w + (int64_t)(K - 1) * Fin * Fout, Fout, Fin, Fout);
     const int KO = (Fout + 3) & ~3;
     float aw[NK][16], ab = 0.f;
 #pragma unroll
@@ -168,44 +135,27 @@ static __global__ __launch_bounds__(256) void cheb_k_bwd_r(const float* __restri
         for (int u = 0; u < 16; ++u) aw[k][u] = 0.f;
     const int64_t t0 = (int64_t)blockIdx.x * tpw, t1 = t0 + tpw < ntiles ? t0 + tpw : ntiles;
     for (int64_t tile = t0; tile < t1; ++tile) {
-        const int64_t r0 = tile * CHEB_TR + wave * CHEB_RPW;
+        const int64_t r0 = tile * GML_RT_TR + wave * GML_RT_RPW;
         __syncthreads();
-#pragma unroll
-        for (int r = 0; r < CHEB_RPW; ++r) {
-            const int64_t row = r0 + r;
-            float g = 0.f;
-            if (row < N && lane < Fout) g = dy[row * lddy + lane] * gml_i64_dact(y[row * ldy + lane], act);
-            gs[(wave * CHEB_RPW + r) * CHEB_W + lane] = g;
-        }
+        gml_rt_load_g(gs, dy, lddy, y, ldy, r0, N, Fout, act, wave, lane);
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             if (k < K) {
                 if (k) __syncthreads();                                     // the reads of Tx_{k-1}'s tile are over
-                cheb_load_rows(as, k ? T + (int64_t)(k - 1) * Fin : x, k ? ldT : ldx, r0, N, Fin, wave, lane);
+                gml_rt_load_rows(as, k ? T + (int64_t)(k - 1) * Fin : x, k ? ldT : ldx, r0, N, Fin, wave, lane);
                 __syncthreads();
-#pragma unroll 2
-                for (int r = 0; r < CHEB_TR; ++r) {                         // dW_k[i][o] += Tx_k[r][i] g[r][o]
-                    const float g = gs[r * CHEB_W + lane];
-#pragma unroll
-                    for (int u = 0; u < 16; u += 4) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(as + r * CHEB_W + wave * 16 + u);
-                        aw[k][u] = fmaf(a.x, g, aw[k][u]); aw[k][u + 1] = fmaf(a.y, g, aw[k][u + 1]);
-                        aw[k][u + 2] = fmaf(a.z, g, aw[k][u + 2]); aw[k][u + 3] = fmaf(a.w, g, aw[k][u + 3]);
-                    }
-                }
+                gml_rt_outer16(as, gs, wave, lane, aw[k]);                  // dW_k[i][o] += Tx_k[r][i] g[r][o]
             }
         }
-        if (tid < 64)
-#pragma unroll 4
-            for (int r = 0; r < CHEB_TR; ++r) ab += gs[r * CHEB_W + lane];
+        if (tid < 64) gml_rt_colsum(gs, lane, ab);
         if (gl) {
-            float acc[CHEB_RPW];
+            float acc[GML_RT_RPW];
 #pragma unroll
-            for (int r = 0; r < CHEB_RPW; ++r) acc[r] = 0.f;
-            gml_i64_prod8(gs, wts, KO, wave, lane, acc);                       // sum_o g[r][o] W_{K-1}[i][o]
+            for (int r = 0; r < GML_RT_RPW; ++r) acc[r] = 0.f;
+            gml_rt_prod8(gs, wts, KO, wave, lane, acc);                       // sum_o g[r][o] W_{K-1}[i][o]
             if (lane < Fin) {
 #pragma unroll
-                for (int r = 0; r < CHEB_RPW; ++r)
+                for (int r = 0; r < GML_RT_RPW; ++r)
                     if (r0 + r < N) gl[(r0 + r) * ldgl + lane] = acc[r];
             }
         }
@@ -231,43 +181,29 @@ static __global__ __launch_bounds__(256) void cheb_k_bwd_a(const int32_t* __rest
                                                            const float* __restrict__ wk, int Fout, int act, float ck,
                                                            const float* __restrict__ g1, const float* __restrict__ g2,
                                                            float* __restrict__ go, int64_t ldgo, int64_t ntiles) {
-    __shared__ __attribute__((aligned(16))) float wts[CHEB_W * CHEB_W];     // W_k^T: [out][in]
-    __shared__ __attribute__((aligned(16))) float gs[CHEB_TR * CHEB_W];
-    __shared__ __attribute__((aligned(16))) float ts[CHEB_TR * CHEB_W];
+    __shared__ __attribute__((aligned(16))) float wts[GML_RT_W * GML_RT_W];     // W_k^T: [out][in]
+    __shared__ __attribute__((aligned(16))) float gs[GML_RT_TR * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float ts[GML_RT_TR * GML_RT_W];
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE;
-    gml_i64_load_image<true>(wts, wk, Fout, Fin, Fout);
-    const int rpp = 64 / gp < CHEB_RPW ? 64 / gp : CHEB_RPW;
-    const int sub = lane / gp, c = lane % gp;
+    gml_rt_load_image<true>(wts, wk, Fout, Fin, Fout);
     const int KO = (Fout + 3) & ~3;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t r0 = tile * CHEB_TR + wave * CHEB_RPW;
+        const int64_t r0 = tile * GML_RT_TR + wave * GML_RT_RPW;
         __syncthreads();
-#pragma unroll
-        for (int r = 0; r < CHEB_RPW; ++r) {
-            const int64_t row = r0 + r;
-            float g = 0.f;
-            if (row < N && lane < Fout) g = dy[row * lddy + lane] * gml_i64_dact(y[row * ldy + lane], act);
-            gs[(wave * CHEB_RPW + r) * CHEB_W + lane] = g;
-        }
-        if (sub < rpp) {
-            for (int pp = 0; pp < CHEB_RPW; pp += rpp) {
-                const int64_t row = r0 + pp + sub;
-                float v = 0.f;
-                if (row < N && c < Fin) v = cheb_gather<false>(rowptr_t, col_t, norm, g1, Fin, row, c, N);
-                ts[(wave * CHEB_RPW + pp + sub) * CHEB_W + c] = v;
-            }
-        }
+        gml_rt_load_g(gs, dy, lddy, y, ldy, r0, N, Fout, act, wave, lane);
+        gml_rt_gather_rows(ts, r0, N, Fin, gp, wave, lane, true,
+                           [&](int64_t row, int c) { return cheb_gather<false>(rowptr_t, col_t, norm, g1, Fin, row, c, N); });
         __syncthreads();
-        float acc[CHEB_RPW];
+        float acc[GML_RT_RPW];
 #pragma unroll
-        for (int r = 0; r < CHEB_RPW; ++r) acc[r] = 0.f;
-        gml_i64_prod8(gs, wts, KO, wave, lane, acc);
+        for (int r = 0; r < GML_RT_RPW; ++r) acc[r] = 0.f;
+        gml_rt_prod8(gs, wts, KO, wave, lane, acc);
         if (lane < Fin) {
 #pragma unroll
-            for (int r = 0; r < CHEB_RPW; ++r) {
+            for (int r = 0; r < GML_RT_RPW; ++r) {
                 const int64_t row = r0 + r;
                 if (row < N) {
-                    float v = fmaf(ck, ts[(wave * CHEB_RPW + r) * CHEB_W + lane], acc[r]);
+                    float v = fmaf(ck, ts[(wave * GML_RT_RPW + r) * GML_RT_W + lane], acc[r]);
                     if (g2) v -= g2[row * Fin + lane];
                     go[row * ldgo + lane] = v;
                 }
@@ -276,43 +212,16 @@ static __global__ __launch_bounds__(256) void cheb_k_bwd_a(const int32_t* __rest
     }
 }
 
-// workgroups in ascending order
-static __global__ void cheb_k_fold(const float* __restrict__ part, int nwg, int64_t P, float* __restrict__ dflat) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= P) return;
-    float s = 0.f;
-    for (int w = 0; w < nwg; ++w) s += part[(int64_t)w * P + e];
-    dflat[e] = s;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- host
-static inline int cheb_gp(int Fin) {
-    int g = 4;
-    while (g < Fin) g *= 2;
-    return g;
-}
-static inline int64_t cheb_tiles(int64_t N) { return gml_cdiv(N, CHEB_TR); }
-static inline unsigned cheb_grid(int64_t N) {
-    const int64_t nt = cheb_tiles(N);
-    return (unsigned)(nt < CHEB_MAXWG ? nt : CHEB_MAXWG);
-}
-static inline void cheb_row_plan(int64_t N, int64_t* tpw, int* nwg) {
-    const int64_t nt = cheb_tiles(N);
-    *tpw = gml_cdiv(nt, CHEB_MAXWG);
-    *nwg = (int)gml_cdiv(nt, *tpw);
-}
-static inline bool cheb_range(int64_t N, int64_t E) { return N <= 0x7fffffff && E <= 0x7fffffff; }
-
 extern "C" {
 
 int gml_cheb_supported(int32_t Fin, int32_t Fout, int32_t K) {
-    return K >= 1 && K <= CHEB_KMAX && Fin >= 1 && Fin <= CHEB_W && Fout >= 1 && Fout <= CHEB_W;
+    return K >= 1 && K <= CHEB_KMAX && Fin >= 1 && Fin <= GML_RT_W && Fout >= 1 && Fout <= GML_RT_W;
 }
 
 int gml_cheb_norm(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* batch, const float* lmax, int64_t B, float lambda,
                   int64_t N, int64_t E, float* norm, gml_stream_t stream) {
     if (N < 0 || E < 0 || (lmax && B < 1)) return GML_E_BADARG;
-    if (!cheb_range(N, E)) return GML_E_UNSUPPORTED;
+    if (!gml_rt_range(N, E)) return GML_E_UNSUPPORTED;
     if (N == 0) return GML_OK;
     if (!rowptr_t || (E && !col_t) || !norm) return GML_E_BADARG;
     hipLaunchKernelGGL(cheb_k_norm, dim3((unsigned)gml_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, rowptr_t, col_t, batch, lmax, B,
@@ -324,14 +233,14 @@ int gml_cheb_fwd(const int32_t* rowptr, const int32_t* col, const float* norm, c
                  int32_t Fin, const float* w, const float* bias, int32_t Fout, int32_t K, int32_t act, float* T, int64_t ldT, float* y,
                  int64_t ldy, gml_stream_t stream) {
     if (N < 0 || E < 0 || act < 0 || act > 2) return GML_E_BADARG;
-    if (!gml_cheb_supported(Fin, Fout, K) || !cheb_range(N, E)) return GML_E_UNSUPPORTED;
+    if (!gml_cheb_supported(Fin, Fout, K) || !gml_rt_range(N, E)) return GML_E_UNSUPPORTED;
     if (N == 0) return GML_OK;
     if (!x || !w || !y || ldx < Fin || ldy < Fout) return GML_E_BADARG;
     if (K > 1 && (!rowptr || (E && !col) || !norm || !T || ldT < (int64_t)(K - 1) * Fin)) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t nt = cheb_tiles(N);
-    const unsigned grid = cheb_grid(N);
-    const int gp = cheb_gp(Fin);
+    const int64_t nt = gml_rt_tiles(N);
+    const unsigned grid = gml_rt_grid(N);
+    const int gp = gml_rt_gp(Fin);
     const int64_t WS = (int64_t)Fin * Fout;
     if (K == 1) {
         hipLaunchKernelGGL(cheb_k_step, dim3(grid), dim3(256), 0, st, rowptr, col, norm, x, ldx, (const float*)nullptr, (int64_t)0,
@@ -359,7 +268,7 @@ size_t gml_cheb_bwd_workspace_bytes(int64_t N, int32_t Fin, int32_t Fout, int32_
     if (N <= 0 || N > 0x7fffffff || !gml_cheb_supported(Fin, Fout, K)) return 0;
     int64_t tpw;
     int nwg;
-    cheb_row_plan(N, &tpw, &nwg);
+    gml_rt_row_plan(N, &tpw, &nwg);
     // three G buffers [N, Fin] (K >= 2) | partials [workgroups, dflat floats]
     return (size_t)((K > 1 ? 3 * N * Fin : 0) + (int64_t)nwg * gml_cheb_dflat_floats(Fin, Fout, K)) * sizeof(float);
 }
@@ -368,7 +277,7 @@ int gml_cheb_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* nor
                  const float* y, int64_t ldy, const float* dy, int64_t lddy, int64_t N, int64_t E, int32_t Fin, const float* w, int32_t Fout,
                  int32_t K, int32_t act, float* dx, int64_t lddx, float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream) {
     if (N < 0 || E < 0 || act < 0 || act > 2) return GML_E_BADARG;
-    if (!gml_cheb_supported(Fin, Fout, K) || !cheb_range(N, E)) return GML_E_UNSUPPORTED;
+    if (!gml_cheb_supported(Fin, Fout, K) || !gml_rt_range(N, E)) return GML_E_UNSUPPORTED;
     if (!dflat) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = gml_cheb_dflat_floats(Fin, Fout, K);
@@ -383,10 +292,10 @@ int gml_cheb_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* nor
     if (!ws || ((uintptr_t)ws & 3) || ws_bytes < gml_cheb_bwd_workspace_bytes(N, Fin, Fout, K)) return GML_E_WORKSPACE;
     int64_t tpw;
     int nwg;
-    cheb_row_plan(N, &tpw, &nwg);
+    gml_rt_row_plan(N, &tpw, &nwg);
     float* G[3] = {(float*)ws, (float*)ws + N * Fin, (float*)ws + 2 * N * Fin};
     float* part = (float*)ws + (K > 1 ? 3 * N * Fin : 0);
-    const int64_t nt = cheb_tiles(N);
+    const int64_t nt = gml_rt_tiles(N);
     float* gl = dx ? (K == 1 ? dx : G[0]) : (float*)nullptr;                // G_{K-1} lives in G[0]
     const int64_t ldgl = K == 1 ? lddx : Fin;
 #define CHEB_ROW(NK)                                                                                                                   \
@@ -398,8 +307,8 @@ int gml_cheb_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* nor
     else CHEB_ROW(8);
 #undef CHEB_ROW
     if (dx && K > 1) {
-        const int gp = cheb_gp(Fin);
-        const unsigned grid = cheb_grid(N);
+        const int gp = gml_rt_gp(Fin);
+        const unsigned grid = gml_rt_grid(N);
         const int64_t WS = (int64_t)Fin * Fout;
         for (int k = K - 2; k >= 0; --k) {                                  // G_m lives in G[(K - 1 - m) % 3]
             const float* g1 = G[(K - 2 - k) % 3];
@@ -409,7 +318,7 @@ int gml_cheb_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* nor
                                w + k * WS, (int)Fout, (int)act, k == 0 ? 1.f : 2.f, g1, g2, go, k == 0 ? lddx : (int64_t)Fin, nt);
         }
     }
-    hipLaunchKernelGGL(cheb_k_fold, dim3((unsigned)gml_cdiv(P, 256)), dim3(256), 0, st, part, nwg, P, dflat);
+    gml_rt_fold(part, nwg, P, dflat, st);
     return gml_launch_status();
 }
 

@@ -18,37 +18,14 @@
 //             S  source view: dx[j] = (1 + eps) dh[j], then + dh[i] over the edges (j -> i) in source-view CSR order
 //             F  fold of the partials in ascending workgroup order -> dflat
 // No atomics; every sum has one order.  Plain fp32 fmaf / tanhf.  Column indices outside [0, N) are skipped.
-#include "gml_img64.h"
+#include "gml_rowtile64.h"
 
-#define GIN_W GML_I64_W
-#define GIN_TR GML_I64_TR
-#define GIN_RPW GML_I64_RPW
-#define GIN_MAXWG 768       // workgroups of the forward and the row pass (3 per CU)
-
-// one (row, column) of the aggregation over a CSR view: SELF_FIRST ? e1 src[row] + sum : sum + e1 src[row], the sum in CSR order
-template <bool SELF_FIRST>
-static __device__ __forceinline__ float gin_gather(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                   const float* __restrict__ src, int64_t ld, int64_t row, int c, int64_t N, float e1) {
-    const float self = src[row * ld + c];
-    float acc = SELF_FIRST ? e1 * self : 0.f;
-    const int k0 = rowptr[row], k1 = rowptr[row + 1];
-    int k = k0;
-    for (; k + 4 <= k1; k += 4) {
-        int64_t j[4];
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) j[u] = col[k + u];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = (j[u] >= 0 && j[u] < N) ? src[j[u] * ld + c] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc += v[u];
-    }
-    for (; k < k1; ++k) {
-        const int64_t j = col[k];
-        if (j >= 0 && j < N) acc += src[j * ld + c];
-    }
-    return SELF_FIRST ? acc : fmaf(e1, self, acc);
-}
+// the sum of x[j] over the edges: every in-range j, a plain add
+struct gin_edge {
+    __device__ __forceinline__ bool keep(int64_t) const { return true; }
+    __device__ __forceinline__ float weight(int64_t) const { return 1.f; }
+    __device__ __forceinline__ float add(float acc, float, float v) const { return acc + v; }
+};
 
 static __global__ __launch_bounds__(256) void gin_k_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                         const float* __restrict__ x, int64_t ldx, int64_t N, int Fin, int gp,
@@ -57,54 +34,46 @@ static __global__ __launch_bounds__(256) void gin_k_fwd(const int32_t* __restric
                                                         const float* __restrict__ b2, int Fout, int depth, int act,
                                                         float* __restrict__ h, int64_t ldh, float* __restrict__ t, int64_t ldt,
                                                         float* __restrict__ y, int64_t ldy, int64_t ntiles) {
-    __shared__ __attribute__((aligned(16))) float w1s[GIN_W * GIN_W];       // [k][o]
-    __shared__ __attribute__((aligned(16))) float w2s[GIN_W * GIN_W];       // [m][o]
-    __shared__ __attribute__((aligned(16))) float hs[GIN_TR * GIN_W];
-    __shared__ __attribute__((aligned(16))) float ts[GIN_TR * GIN_W];
+    __shared__ __attribute__((aligned(16))) float w1s[GML_RT_W * GML_RT_W];       // [k][o]
+    __shared__ __attribute__((aligned(16))) float w2s[GML_RT_W * GML_RT_W];       // [m][o]
+    __shared__ __attribute__((aligned(16))) float hs[GML_RT_TR * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float ts[GML_RT_TR * GML_RT_W];
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE;
-    gml_i64_load_image<true>(w1s, w1, Fin, Fh, Fin);
-    if (depth == 2) gml_i64_load_image<true>(w2s, w2, Fh, Fout, Fh);
+    gml_rt_load_image<true>(w1s, w1, Fin, Fh, Fin);
+    if (depth == 2) gml_rt_load_image<true>(w2s, w2, Fh, Fout, Fh);
     const float e1 = 1.f + eps[0];
-    const int rpp = 64 / gp < GIN_RPW ? 64 / gp : GIN_RPW;                  // rows of one gather pass
-    const int sub = lane / gp, c = lane % gp;
     const int K1 = (Fin + 3) & ~3, K2 = (Fh + 3) & ~3;
     const float bias1 = (b1 && lane < Fh) ? b1[lane] : 0.f;
     const float bias2 = (depth == 2 && b2 && lane < Fout) ? b2[lane] : 0.f;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t r0 = tile * GIN_TR + wave * GIN_RPW;
+        const int64_t r0 = tile * GML_RT_TR + wave * GML_RT_RPW;
         __syncthreads();                                                    // the images are in; the last tile's reads are over
-        if (sub < rpp) {
-            for (int p = 0; p < GIN_RPW; p += rpp) {
-                const int64_t row = r0 + p + sub;
-                float v = 0.f;
-                if (row < N && c < Fin) {
-                    v = gin_gather<false>(rowptr, col, x, ldx, row, c, N, e1);
-                    h[row * ldh + c] = v;
-                }
-                hs[(wave * GIN_RPW + p + sub) * GIN_W + c] = v;
-            }
-        }
+        gml_rt_gather_rows(hs, r0, N, Fin, gp, wave, lane, true, [&](int64_t row, int c) {
+            const float v = fmaf(e1, x[row * ldx + c], gml_rt_walk(rowptr, col, x, ldx, row, c, N, 0.f, gin_edge()));
+            h[row * ldh + c] = v;
+            return v;
+        });
         __syncthreads();
-        float acc[GIN_RPW];
+        float acc[GML_RT_RPW];
 #pragma unroll
-        for (int r = 0; r < GIN_RPW; ++r) acc[r] = bias1;
-        gml_i64_prod8(hs, w1s, K1, wave, lane, acc);
+        for (int r = 0; r < GML_RT_RPW; ++r) acc[r] = bias1;
+        gml_rt_prod8(hs, w1s, K1, wave, lane, acc);
         if (depth == 2) {
 #pragma unroll
-            for (int r = 0; r < GIN_RPW; ++r) {
+            for (int r = 0; r < GML_RT_RPW; ++r) {
                 const float v = lane < Fh ? fmaxf(acc[r], 0.f) : 0.f;
-                ts[(wave * GIN_RPW + r) * GIN_W + lane] = v;
+                ts[(wave * GML_RT_RPW + r) * GML_RT_W + lane] = v;
                 if (lane < Fh && r0 + r < N) t[(r0 + r) * ldt + lane] = v;
                 acc[r] = bias2;
             }
             __syncthreads();
-            gml_i64_prod8(ts, w2s, K2, wave, lane, acc);
+            gml_rt_prod8(ts, w2s, K2, wave, lane, acc);
         }
         const int Fo = depth == 2 ? Fout : Fh;
         if (lane < Fo) {
 #pragma unroll
-            for (int r = 0; r < GIN_RPW; ++r)
-                if (r0 + r < N) y[(r0 + r) * ldy + lane] = gml_i64_act(acc[r], act);
+            for (int r = 0; r < GML_RT_RPW; ++r)
+                if (r0 + r < N) y[(r0 + r) * ldy + lane] = gml_rt_act(acc[r], act);
         }
     }
 }
@@ -116,14 +85,14 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_r(const float* __restric
                                                           const float* __restrict__ w1, int Fh, const float* __restrict__ w2, int Fout,
                                                           int depth, int act, float* __restrict__ dh, float* __restrict__ part,
                                                           int64_t P, int64_t ntiles, int64_t tpw) {
-    __shared__ __attribute__((aligned(16))) float w1s[GIN_W * GIN_W];       // [o][k]
-    __shared__ __attribute__((aligned(16))) float w2s[GIN_W * GIN_W];       // [o][m]
-    __shared__ __attribute__((aligned(16))) float g2s[GIN_TR * GIN_W];
-    __shared__ __attribute__((aligned(16))) float g1d[GIN_TR * GIN_W];
-    __shared__ __attribute__((aligned(16))) float as[GIN_TR * GIN_W];       // t, then h
+    __shared__ __attribute__((aligned(16))) float w1s[GML_RT_W * GML_RT_W];       // [o][k]
+    __shared__ __attribute__((aligned(16))) float w2s[GML_RT_W * GML_RT_W];       // [o][m]
+    __shared__ __attribute__((aligned(16))) float g2s[GML_RT_TR * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float g1d[GML_RT_TR * GML_RT_W];
+    __shared__ __attribute__((aligned(16))) float as[GML_RT_TR * GML_RT_W];       // t, then h
     const int lane = threadIdx.x % GML_WAVE, wave = threadIdx.x / GML_WAVE, tid = threadIdx.x;
-    gml_i64_load_image<false>(w1s, w1, Fh, Fin, Fin);
-    if (depth == 2) gml_i64_load_image<false>(w2s, w2, Fout, Fh, Fh);
+    gml_rt_load_image<false>(w1s, w1, Fh, Fin, Fin);
+    if (depth == 2) gml_rt_load_image<false>(w2s, w2, Fout, Fh, Fh);
     float* g1s = depth == 2 ? g1d : g2s;
     const int Fo = depth == 2 ? Fout : Fh;                                  // the width of y
     const int KO = (Fo + 3) & ~3, KH = (Fh + 3) & ~3;
@@ -132,73 +101,35 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_r(const float* __restric
     for (int u = 0; u < 16; ++u) aw1[u] = aw2[u] = 0.f;
     const int64_t t0 = (int64_t)blockIdx.x * tpw, t1 = t0 + tpw < ntiles ? t0 + tpw : ntiles;
     for (int64_t tile = t0; tile < t1; ++tile) {
-        const int64_t r0 = tile * GIN_TR + wave * GIN_RPW;
+        const int64_t r0 = tile * GML_RT_TR + wave * GML_RT_RPW;
         __syncthreads();
-#pragma unroll
-        for (int r = 0; r < GIN_RPW; ++r) {
-            const int64_t row = r0 + r;
-            const bool on = row < N;
-            float g = 0.f;
-            if (on && lane < Fo) g = dy[row * lddy + lane] * gml_i64_dact(y[row * ldy + lane], act);
-            g2s[(wave * GIN_RPW + r) * GIN_W + lane] = g;
-            float a = 0.f;
-            if (depth == 2) {
-                if (on && lane < Fh) a = t[row * ldt + lane];
-            } else if (on && lane < Fin) {
-                a = h[row * ldh + lane];
-            }
-            as[(wave * GIN_RPW + r) * GIN_W + lane] = a;
-        }
+        gml_rt_load_g(g2s, dy, lddy, y, ldy, r0, N, Fo, act, wave, lane);
+        if (depth == 2) gml_rt_load_rows(as, t, ldt, r0, N, Fh, wave, lane);
+        else gml_rt_load_rows(as, h, ldh, r0, N, Fin, wave, lane);
         __syncthreads();
         if (depth == 2) {
-#pragma unroll 2
-            for (int r = 0; r < GIN_TR; ++r) {                              // dW2[o][m] += g2[r][o] t[r][m]
-                const float a = as[r * GIN_W + lane];
+            gml_rt_outer16(g2s, as, wave, lane, aw2);                           // dW2[o][m] += g2[r][o] t[r][m]
+            if (tid >= 64 && tid < 128) gml_rt_colsum(g2s, lane, ab);
+            float acc[GML_RT_RPW];
 #pragma unroll
-                for (int u = 0; u < 16; u += 4) {
-                    const f32x4 g = *reinterpret_cast<const f32x4*>(g2s + r * GIN_W + wave * 16 + u);
-                    aw2[u] = fmaf(g.x, a, aw2[u]); aw2[u + 1] = fmaf(g.y, a, aw2[u + 1]);
-                    aw2[u + 2] = fmaf(g.z, a, aw2[u + 2]); aw2[u + 3] = fmaf(g.w, a, aw2[u + 3]);
-                }
-            }
-            if (tid >= 64 && tid < 128)
-#pragma unroll 4
-                for (int r = 0; r < GIN_TR; ++r) ab += g2s[r * GIN_W + lane];
-            float acc[GIN_RPW];
+            for (int r = 0; r < GML_RT_RPW; ++r) acc[r] = 0.f;
+            gml_rt_prod8(g2s, w2s, KO, wave, lane, acc);
 #pragma unroll
-            for (int r = 0; r < GIN_RPW; ++r) acc[r] = 0.f;
-            gml_i64_prod8(g2s, w2s, KO, wave, lane, acc);
-#pragma unroll
-            for (int r = 0; r < GIN_RPW; ++r)
-                g1d[(wave * GIN_RPW + r) * GIN_W + lane] = as[(wave * GIN_RPW + r) * GIN_W + lane] > 0.f ? acc[r] : 0.f;
+            for (int r = 0; r < GML_RT_RPW; ++r)
+                g1d[(wave * GML_RT_RPW + r) * GML_RT_W + lane] = as[(wave * GML_RT_RPW + r) * GML_RT_W + lane] > 0.f ? acc[r] : 0.f;
             __syncthreads();
-#pragma unroll
-            for (int r = 0; r < GIN_RPW; ++r) {
-                const int64_t row = r0 + r;
-                as[(wave * GIN_RPW + r) * GIN_W + lane] = (row < N && lane < Fin) ? h[row * ldh + lane] : 0.f;
-            }
+            gml_rt_load_rows(as, h, ldh, r0, N, Fin, wave, lane);
             __syncthreads();
         }
-#pragma unroll 2
-        for (int r = 0; r < GIN_TR; ++r) {                                  // dW1[o][k] += g1[r][o] h[r][k]
-            const float a = as[r * GIN_W + lane];
+        gml_rt_outer16(g1s, as, wave, lane, aw1);                               // dW1[o][k] += g1[r][o] h[r][k]
+        if (tid < 64) gml_rt_colsum(g1s, lane, ab);
+        float acc[GML_RT_RPW];
 #pragma unroll
-            for (int u = 0; u < 16; u += 4) {
-                const f32x4 g = *reinterpret_cast<const f32x4*>(g1s + r * GIN_W + wave * 16 + u);
-                aw1[u] = fmaf(g.x, a, aw1[u]); aw1[u + 1] = fmaf(g.y, a, aw1[u + 1]);
-                aw1[u + 2] = fmaf(g.z, a, aw1[u + 2]); aw1[u + 3] = fmaf(g.w, a, aw1[u + 3]);
-            }
-        }
-        if (tid < 64)
-#pragma unroll 4
-            for (int r = 0; r < GIN_TR; ++r) ab += g1s[r * GIN_W + lane];
-        float acc[GIN_RPW];
-#pragma unroll
-        for (int r = 0; r < GIN_RPW; ++r) acc[r] = 0.f;
-        gml_i64_prod8(g1s, w1s, KH, wave, lane, acc);                           // dh[r][k] = sum_o g1[r][o] W1[o][k]
+        for (int r = 0; r < GML_RT_RPW; ++r) acc[r] = 0.f;
+        gml_rt_prod8(g1s, w1s, KH, wave, lane, acc);                           // dh[r][k] = sum_o g1[r][o] W1[o][k]
         if (lane < Fin) {
 #pragma unroll
-            for (int r = 0; r < GIN_RPW; ++r) {
+            for (int r = 0; r < GML_RT_RPW; ++r) {
                 const int64_t row = r0 + r;
                 if (row < N) {
                     if (dh) dh[row * Fin + lane] = acc[r];
@@ -234,53 +165,28 @@ static __global__ __launch_bounds__(256) void gin_k_bwd_s(const int32_t* __restr
     const int sub = threadIdx.x / gp, c = threadIdx.x % gp;
     const int64_t row = (int64_t)blockIdx.x * rpb + sub;
     if (row >= N || c >= Fin) return;
-    dx[row * lddx + c] = gin_gather<true>(rowptr_t, col_t, dh, Fin, row, c, N, 1.f + eps[0]);
+    dx[row * lddx + c] = gml_rt_walk(rowptr_t, col_t, dh, Fin, row, c, N, (1.f + eps[0]) * dh[row * Fin + c], gin_edge());
 }
-
-// workgroups in ascending order
-static __global__ void gin_k_fold(const float* __restrict__ part, int nwg, int64_t P, float* __restrict__ dflat) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= P) return;
-    float s = 0.f;
-    for (int w = 0; w < nwg; ++w) s += part[(int64_t)w * P + e];
-    dflat[e] = s;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- host
-static inline int gin_gp(int Fin) {
-    int g = 4;
-    while (g < Fin) g *= 2;
-    return g;
-}
-static inline int64_t gin_tiles(int64_t N) { return gml_cdiv(N, GIN_TR); }
-static inline void gin_row_plan(int64_t N, int64_t* tpw, int* nwg) {
-    const int64_t nt = gin_tiles(N);
-    *tpw = gml_cdiv(nt, GIN_MAXWG);
-    *nwg = (int)gml_cdiv(nt, *tpw);
-}
-static inline bool gin_range(int64_t N, int64_t E) { return N <= 0x7fffffff && E <= 0x7fffffff; }
 
 extern "C" {
 
 int gml_gin_supported(int32_t Fin, int32_t Fh, int32_t Fout, int32_t depth) {
     if (depth != 1 && depth != 2) return 0;
-    if (Fin < 1 || Fin > GIN_W || Fh < 1 || Fh > GIN_W) return 0;
-    return depth == 1 || (Fout >= 1 && Fout <= GIN_W);
+    if (Fin < 1 || Fin > GML_RT_W || Fh < 1 || Fh > GML_RT_W) return 0;
+    return depth == 1 || (Fout >= 1 && Fout <= GML_RT_W);
 }
 
 int gml_gin_fwd(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, int64_t N, int64_t E, int32_t Fin, const float* eps,
                 const float* w1, const float* b1, int32_t Fh, const float* w2, const float* b2, int32_t Fout, int32_t depth, int32_t act,
                 float* h, int64_t ldh, float* t, int64_t ldt, float* y, int64_t ldy, gml_stream_t stream) {
     if (N < 0 || E < 0 || act < 0 || act > 2) return GML_E_BADARG;
-    if (!gml_gin_supported(Fin, Fh, Fout, depth) || !gin_range(N, E)) return GML_E_UNSUPPORTED;
+    if (!gml_gin_supported(Fin, Fh, Fout, depth) || !gml_rt_range(N, E)) return GML_E_UNSUPPORTED;
     if (N == 0) return GML_OK;
     const int Fo = depth == 2 ? Fout : Fh;
     if (!rowptr || (E && !col) || !x || !eps || !w1 || !h || !y || ldx < Fin || ldh < Fin || ldy < Fo) return GML_E_BADARG;
     if (depth == 2 && (!w2 || !t || ldt < Fh)) return GML_E_BADARG;
-    const int64_t nt = gin_tiles(N);
-    const unsigned grid = (unsigned)(nt < GIN_MAXWG ? nt : GIN_MAXWG);
-    hipLaunchKernelGGL(gin_k_fwd, dim3(grid), dim3(256), 0, (hipStream_t)stream, rowptr, col, x, ldx, N, (int)Fin, gin_gp(Fin), eps, w1, b1,
-                       (int)Fh, w2, b2, (int)Fout, (int)depth, (int)act, h, ldh, t, ldt, y, ldy, nt);
+    hipLaunchKernelGGL(gin_k_fwd, dim3(gml_rt_grid(N)), dim3(256), 0, (hipStream_t)stream, rowptr, col, x, ldx, N, (int)Fin, gml_rt_gp(Fin),
+                       eps, w1, b1, (int)Fh, w2, b2, (int)Fout, (int)depth, (int)act, h, ldh, t, ldt, y, ldy, gml_rt_tiles(N));
     return gml_launch_status();
 }
 
@@ -293,7 +199,7 @@ size_t gml_gin_bwd_workspace_bytes(int64_t N, int32_t Fin, int32_t Fh, int32_t F
     if (N <= 0 || N > 0x7fffffff || !gml_gin_supported(Fin, Fh, Fout, depth)) return 0;
     int64_t tpw;
     int nwg;
-    gin_row_plan(N, &tpw, &nwg);
+    gml_rt_row_plan(N, &tpw, &nwg);
     // dh [N, Fin] | partials [workgroups, dflat floats]
     return (size_t)(N * Fin + (int64_t)nwg * gml_gin_dflat_floats(Fin, Fh, Fout, depth)) * sizeof(float);
 }
@@ -303,7 +209,7 @@ int gml_gin_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* x, i
                 const float* w1, int32_t Fh, const float* w2, int32_t Fout, int32_t depth, int32_t act, float* dx, int64_t lddx,
                 float* dflat, void* ws, size_t ws_bytes, gml_stream_t stream) {
     if (N < 0 || E < 0 || act < 0 || act > 2) return GML_E_BADARG;
-    if (!gml_gin_supported(Fin, Fh, Fout, depth) || !gin_range(N, E)) return GML_E_UNSUPPORTED;
+    if (!gml_gin_supported(Fin, Fh, Fout, depth) || !gml_rt_range(N, E)) return GML_E_UNSUPPORTED;
     if (!dflat) return GML_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = gml_gin_dflat_floats(Fin, Fh, Fout, depth);
@@ -318,17 +224,17 @@ int gml_gin_bwd(const int32_t* rowptr_t, const int32_t* col_t, const float* x, i
     if (!ws || ((uintptr_t)ws & 3) || ws_bytes < gml_gin_bwd_workspace_bytes(N, Fin, Fh, Fout, depth)) return GML_E_WORKSPACE;
     int64_t tpw;
     int nwg;
-    gin_row_plan(N, &tpw, &nwg);
+    gml_rt_row_plan(N, &tpw, &nwg);
     float* dh = (float*)ws;
     float* part = dh + N * Fin;
     hipLaunchKernelGGL(gin_k_bwd_r, dim3(nwg), dim3(256), 0, st, x, ldx, h, ldh, t, ldt, y, ldy, dy, lddy, N, (int)Fin, w1, (int)Fh, w2,
-                       (int)Fout, (int)depth, (int)act, dx ? dh : (float*)nullptr, part, P, gin_tiles(N), tpw);
+                       (int)Fout, (int)depth, (int)act, dx ? dh : (float*)nullptr, part, P, gml_rt_tiles(N), tpw);
     if (dx) {
-        const int gp = gin_gp(Fin);
+        const int gp = gml_rt_gp(Fin);
         hipLaunchKernelGGL(gin_k_bwd_s, dim3((unsigned)gml_cdiv(N, 256 / gp)), dim3(256), 0, st, rowptr_t, col_t, dh, N, (int)Fin, gp, eps,
                            dx, lddx);
     }
-    hipLaunchKernelGGL(gin_k_fold, dim3((unsigned)gml_cdiv(P, 256)), dim3(256), 0, st, part, nwg, P, dflat);
+    gml_rt_fold(part, nwg, P, dflat, st);
     return gml_launch_status();
 }
 

@@ -2185,6 +2185,37 @@ class PPGNBlockFunction(torch.autograd.Function):
                 None)
 
 
+# ---------------------------------------------------------------------------- what the message-passing layers (GAT, GIN, ChebNet) share
+RELU_TANH = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2}
+
+
+def _relu_tanh_id(act):
+    if act not in RELU_TANH:
+        raise ValueError("act: None, 'relu' or 'tanh', got %r" % (act,))
+    return RELU_TANH[act]
+
+
+def _fused_input_ok(x):
+    """what every fused layer asks of its input: float32 [N >= 1, F] on the device"""
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1
+
+
+def csr_edge_index(csr):
+    """int64 [2, E] = (source, target) of a GraphCSR in its target-sorted order (for the *_conv_torch compositions)"""
+    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).to(torch.int64)
+    dst = torch.repeat_interleave(torch.arange(csr.N, device=csr.device), deg, output_size=csr.E)
+    return torch.stack([csr.col.to(torch.int64), dst])
+
+
+def _flat_and_ws(layer, N, dims, dev):
+    """(dflat, workspace) of a layer's backward, float32, sized by the library's gml_<layer>_dflat_floats(*dims) and
+    gml_<layer>_bwd_workspace_bytes(N, *dims)"""
+    L = _lib.lib()
+    flat = torch.empty(int(getattr(L, 'gml_%s_dflat_floats' % layer)(*dims)), dtype=torch.float32, device=dev)
+    nws = int(getattr(L, 'gml_%s_bwd_workspace_bytes' % layer)(N, *dims))
+    return flat, torch.empty(max(nws // 4, 4), dtype=torch.float32, device=dev)
+
+
 # ---------------------------------------------------------------------------- GAT attention layer (csrc/gml_gat.hip)
 GAT_ACTS = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'elu': 3}
 GAT_SLOPE = 0.2
@@ -2203,7 +2234,7 @@ def gat_conv_supported(x, heads, channels):
     one layer forward + backward, fused 90th percentile against the composition's 10th, ms (tools/bench_gat.py, profiles/gat.json,
     DESIGN s4.20): ZINC-like batch of 64 0.37 against 1.01 (25 -> 8 x 8) and 0.36 against 0.98 (96 -> 8 x 12), mutag batch 16 0.36 against
     0.79, sr25 0.21 against 0.82, the 900-node grid 0.21 against 0.81, 500 k rows 2.11 against 7.05 and 2.66 against 8.38."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1):
+    if not _fused_input_ok(x):
         return False
     if _os.environ.get('GML_NO_GAT_FUSED'):
         return False
@@ -2246,11 +2277,7 @@ def gat_conv_torch(x, edge_index, weight, att_l, att_r, bias=None, act=None, neg
     return out
 
 
-def gat_edge_index(csr):
-    """int64 [2, E] = (source, target) of a GraphCSR in its target-sorted order (for gat_conv_torch)"""
-    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).to(torch.int64)
-    dst = torch.repeat_interleave(torch.arange(csr.N, device=csr.device), deg, output_size=csr.E)
-    return torch.stack([csr.col.to(torch.int64), dst])
+gat_edge_index = csr_edge_index
 
 
 class GATConvFunction(torch.autograd.Function):
@@ -2314,13 +2341,7 @@ class GATConvFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------- GIN layer (csrc/gml_gin.hip)
-GIN_ACTS = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2}
-
-
-def _gin_act_id(act):
-    if act not in GIN_ACTS:
-        raise ValueError("act: None, 'relu' or 'tanh', got %r" % (act,))
-    return GIN_ACTS[act]
+GIN_ACTS, _gin_act_id = RELU_TANH, _relu_tanh_id
 
 
 def gin_nn_linears(nn):
@@ -2347,7 +2368,7 @@ def gin_conv_supported(x, Fh, Fout=None):
     profiles/gin.json, DESIGN s4.21): ZINC-like batch of 64 0.30 against 0.50 (25 -> 64 -> 64) and 0.30 against 0.50 (64 -> 64 -> 64),
     mutag batch 16 0.30 against 0.49 and 0.29 against 0.49, sr25 at depth 1 0.28 against 0.39 and 0.27 against 0.38, the 900-node grid
     0.28 against 0.38 (1 -> 64 -> 64) and 0.15 against 0.38, 500 k rows 1.65 against 3.44 and 2.01 against 4.27."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1):
+    if not _fused_input_ok(x):
         return False
     if _os.environ.get('GML_NO_GIN_FUSED'):
         return False
@@ -2368,7 +2389,7 @@ def gin_conv_torch(x, edge_index, eps, linears, act=None):
     out = _linear(h, linears[0][0], linears[0][1])
     if len(linears) == 2:
         out = _linear(torch.relu(out), linears[1][0], linears[1][1])
-    a = _gin_act_id(act)
+    a = _relu_tanh_id(act)
     return torch.relu(out) if a == 1 else (torch.tanh(out) if a == 2 else out)
 
 
@@ -2399,7 +2420,7 @@ class GINConvFunction(torch.autograd.Function):
             raise ValueError('GraphCSR was built for %d nodes, x has %d rows' % (csr.N, N))
         b1 = None if b1 is None else _f32c(b1, 'b1')
         b2 = None if b2 is None else _f32c(b2, 'b2')
-        a = _gin_act_id(act)
+        a = _relu_tanh_id(act)
         dev = x.device
         Fo = Fout if depth == 2 else Fh
         with torch.cuda.device(dev):
@@ -2423,12 +2444,9 @@ class GINConvFunction(torch.autograd.Function):
         dev = x.device
         dy = _f32c(dy, 'grad of y')
         Fo = Fout if depth == 2 else Fh
-        L = _lib.lib()
         with torch.cuda.device(dev):
             dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-            flat = torch.empty(int(L.gml_gin_dflat_floats(Fin, Fh, Fout, depth)), dtype=torch.float32, device=dev)
-            nws = int(L.gml_gin_bwd_workspace_bytes(N, Fin, Fh, Fout, depth))
-            ws = torch.empty(max(nws // 4, 4), dtype=torch.float32, device=dev)
+            flat, ws = _flat_and_ws('gin', N, (Fin, Fh, Fout, depth), dev)
             with _Timed('gin_bwd'):
                 _lib.call('gml_gin_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(x), Fin, _ptr(h), Fin, _ptr(t), Fh, _ptr(y), Fo, _ptr(dy),
                           Fo, N, csr.E, Fin, _ptr(eps), _ptr(w1), Fh, _ptr(w2), Fout, depth, ctx.act, _ptr(dx), Fin, _ptr(flat), _ptr(ws),
@@ -2454,7 +2472,7 @@ def cheb_conv_supported(x, Fout, K, Fin=None):
     profiles/cheb.json, DESIGN s4.22): ZINC-like batch of 64 at K = 2 0.14 against 0.53 (25 -> 64) and 0.15 against 0.53 (64 -> 64),
     mutag batch 16 at K = 3 0.18 against 0.79 and 0.17 against 0.81, sr25 at K = 4 0.19 against 1.04 and 0.21 against 0.98, the 900-node
     grid at K = 7 0.16 against 1.61 and 0.30 against 1.63, 500 k rows 2.06 against 4.39 (K = 2) and 6.63 against 14.24 (K = 5)."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) >= 1):
+    if not _fused_input_ok(x):
         return False
     if _os.environ.get('GML_NO_CHEB_FUSED'):
         return False
@@ -2527,7 +2545,7 @@ def cheb_conv_torch(x, edge_index, weight, bias=None, batch=None, lambda_max=Non
             out = out + t1 @ weight[k]
     if bias is not None:
         out = out + bias
-    a = _gin_act_id(act)
+    a = _relu_tanh_id(act)
     return torch.relu(out) if a == 1 else (torch.tanh(out) if a == 2 else out)
 
 
@@ -2550,7 +2568,7 @@ class ChebConvFunction(torch.autograd.Function):
         if tuple(norm.shape) != (N, 2):
             raise ValueError('ChebConv layer: norm [N, 2] (functional.cheb_norm) expected')
         bias = None if bias is None else _f32c(bias, 'bias')
-        a = _gin_act_id(act)
+        a = _relu_tanh_id(act)
         dev = x.device
         with torch.cuda.device(dev):
             T = torch.empty(N, (K - 1) * Fin, dtype=torch.float32, device=dev) if K > 1 else None
@@ -2568,12 +2586,9 @@ class ChebConvFunction(torch.autograd.Function):
         csr, (N, Fin, Fout, K) = ctx.csr, ctx.dims
         dev = x.device
         dy = _f32c(dy, 'grad of y')
-        L = _lib.lib()
         with torch.cuda.device(dev):
             dx = torch.empty(N, Fin, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-            flat = torch.empty(int(L.gml_cheb_dflat_floats(Fin, Fout, K)), dtype=torch.float32, device=dev)
-            nws = int(L.gml_cheb_bwd_workspace_bytes(N, Fin, Fout, K))
-            ws = torch.empty(max(nws // 4, 4), dtype=torch.float32, device=dev)
+            flat, ws = _flat_and_ws('cheb', N, (Fin, Fout, K), dev)
             with _Timed('cheb_bwd'):
                 _lib.call('gml_cheb_bwd', _ptr(csr.rowptr_t), _ptr(csr.col_t), _ptr(norm), _ptr(x), Fin, _ptr(T), (K - 1) * Fin, _ptr(y), Fout,
                           _ptr(dy), Fout, N, csr.E, Fin, _ptr(weight), Fout, K, ctx.act, _ptr(dx), Fin, _ptr(flat), _ptr(ws),

@@ -60,7 +60,7 @@ class GATConv(torch.nn.Module):
             return Fn.GATConvFunction.apply(x, csr, self.lin_l.weight, self.att_l, self.att_r, self.bias, act)
         Fn._path('gat', 'torch ops (outside the fused attention kernel)', '-', self.in_channels, self.heads * self.out_channels)
         if isinstance(edge_index, GraphCSR):
-            edge_index = Fn.gat_edge_index(edge_index)
+            edge_index = Fn.csr_edge_index(edge_index)
         return Fn.gat_conv_torch(x, edge_index, self.lin_l.weight, self.att_l, self.att_r, self.bias, act)
 
     def __repr__(self):

@@ -47,7 +47,7 @@ class GINConv(torch.nn.Module):
             return Fn.GINConvFunction.apply(x, csr, self.eps, lins[0].weight, lins[0].bias, None if l2 is None else l2.weight,
                                             None if l2 is None else l2.bias, act)
         if isinstance(edge_index, GraphCSR):
-            edge_index = Fn.gat_edge_index(edge_index)
+            edge_index = Fn.csr_edge_index(edge_index)
         if lins is not None:
             Fn._path('gin', 'torch ops (outside the fused layer)', '-', int(x.size(1)), lins[-1].out_features)
             return Fn.gin_conv_torch(x, edge_index, self.eps, [(l.weight, l.bias) for l in lins], act)
@@ -60,5 +60,5 @@ class GINConv(torch.nn.Module):
 
 
 def _act(v, act):
-    a = Fn._gin_act_id(act)
+    a = Fn._relu_tanh_id(act)
     return torch.relu(v) if a == 1 else (torch.tanh(v) if a == 2 else v)

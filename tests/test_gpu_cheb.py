@@ -609,3 +609,73 @@ def test_graph8c_decisions_equal_float64(dev):
     gs = _as_dicts(readers.load_graph8c(os.path.join(RAW, 'graph8c.g6'))[1000:1300])
     must_sep, must_sim = _decisions(dev, models.graph8c_cheb, gs[0]['x'].shape[1], [0, 1, 2], gs, 1e-3, 'graph8c[1000:1300]')
     assert must_sep.size == 44850 and must_sep.sum() > 40000
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. many tiles
+MAXWG = 768              # the workgroups of a tile-walking launch and of a row pass (csrc/gml_rowtile64.h)
+COPIES = 367             # of rand67: 24,589 rows = 769 tiles of 32 rows, the fewest copies with more than MAXWG tiles
+
+
+def sparse_laplacian(ei, N, batch, lam, dtype):
+    """R.laplacian as a sparse [N, N] matrix, every step in `dtype`: the same entries, repeats summed"""
+    ei = torch.as_tensor(ei, dtype=torch.int64)
+    ei = ei[:, ei[0] != ei[1]]
+    A = torch.sparse_coo_tensor(torch.stack([ei[1], ei[0]]), torch.ones(ei.size(1), dtype=dtype), (N, N)).coalesce()
+    deg = torch.sparse.sum(A, 0).to_dense()
+    dis = torch.where(deg > 0, deg.clamp(min=1).pow(-0.5), torch.zeros_like(deg))
+    s = 2.0 / lam.to(dtype)[batch]
+    i, j = A.indices()
+    d = torch.arange(N)
+    return torch.sparse_coo_tensor(torch.cat([A.indices(), torch.stack([d, d])], 1), torch.cat([-(s * dis)[i] * A.values() * dis[j], s - 1]),
+                                   (N, N)).coalesce()
+
+
+_MANY = {}
+
+
+def many_tiles_case(si, act):
+    """(case, graph tuple, (float64, float32) references) of rand67 as COPIES block-diagonal copies, each a graph of the batch with the
+    small graph's lambda_max: x repeated per copy, the weights of the small case, dy fresh for every row; the kink margin is asserted
+    on the small case, whose pre-activations are the only values the big one takes.  Computed once."""
+    if not _MANY:
+        case, (ei, n, batch, lam), L, seed = R.layer_case(si, act, 'rand67')
+        assert_margin(case, L, act, 'many tiles: the small case, seed %d' % seed)
+        N = COPIES * n
+        big = dict(case, x=case['x'].repeat(COPIES, 1))
+        big['dy'] = torch.randn(N, case['dy'].size(1), generator=torch.Generator().manual_seed(seed + 1))
+        eib = (ei[:, None, :] + n * np.arange(COPIES, dtype=np.int64)[None, :, None]).reshape(2, -1)
+        gr = (eib, N, torch.arange(COPIES).repeat_interleave(n), lam.repeat(COPIES))
+        refs = []
+        for dt in (torch.float64, torch.float32):
+            d = {k: v.to(dt) for k, v in big.items()}
+            Ls = sparse_laplacian(eib, N, gr[2], gr[3], dt)
+            r = R.backward(d['x'], Ls, d['W'], d['b'], act, d['dy'])
+            r['y'] = R.forward(d['x'], Ls, d['W'], d['b'], act)
+            refs.append(r)
+        _MANY.update(case=big, gr=gr, refs=tuple(refs))
+    return _MANY['case'], _MANY['gr'], _MANY['refs']
+
+
+@pytest.mark.parametrize('need_dx', [True, False])
+def test_many_tiles(dev, need_dx):
+    """769 tiles at K = 3 (the smallest K whose adjoint runs one step without G_{k+2} and one with it): the forward's and the adjoint's
+    workgroups make a second trip of their tile loop, the row pass gets two tiles per workgroup and a last workgroup that owns one.
+    Reference: backward() / forward() of tests/_cheb_ref.py, the float64 restatement and its float32 twin, fed a SPARSE L^
+    (sparse_laplacian above, built from the big edge list in the reference's own dtype) in place of the dense [N, N] one."""
+    from gnn_matlang_amd import _lib
+    from gnn_matlang_amd.graph import GraphCSR
+    si, act = 2, 'relu'
+    Fin, Fout, K = R.SHAPES[si]
+    assert K == 3 and Fin != Fout and max(Fin, Fout) < 64
+    big, gr, (ref64, ref32) = many_tiles_case(si, act)
+    N = gr[1]
+    tiles = -(-N // 32)
+    L = _lib.lib()
+    P = int(L.gml_cheb_dflat_floats(Fin, Fout, K))
+    nwg, rest = divmod(int(L.gml_cheb_bwd_workspace_bytes(N, Fin, Fout, K)) // 4 - 3 * N * Fin, P)
+    tpw = -(-tiles // nwg)
+    print('many tiles: N %d, tiles %d, row-pass workgroups %d of %d tiles (the last: %d)' % (N, tiles, nwg, tpw, tiles - (nwg - 1) * tpw))
+    assert N == 24589 and tiles == MAXWG + 1                   # the forward and the adjoint: a second trip for workgroup 0 alone
+    assert rest == 0 and 1 < nwg < tiles and tpw == 2 and tiles - (nwg - 1) * tpw == 1
+    csr = GraphCSR.from_edge_index(torch.from_numpy(gr[0]).to(dev), N)
+    check_layer(layer_gpu(dev, big, gr, csr, act, need_dx), ref64, ref32, 'many tiles dx=%s' % need_dx, need_dx)

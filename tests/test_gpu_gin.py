@@ -640,3 +640,45 @@ def test_graph8c_decisions_equal_float64(dev):
     assert not got_sim[must_sep].any(), '%d pairs the float64 model separates stayed similar' % int(got_sim[must_sep].sum())
     assert got_sim[must_sim].all(), '%d pairs the float64 model cannot separate were separated' % int((~got_sim[must_sim]).sum())
     assert counts[-1] == int(got_sim.sum())
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. many tiles
+MAXWG = 768              # the workgroups of a tile-walking launch and of a row pass (csrc/gml_rowtile64.h)
+COPIES = 367             # of rand67: 24,589 rows = 769 tiles of 32 rows, the fewest copies with more than MAXWG tiles
+
+
+def many_tiles_case(si, act):
+    """(case, edge_index, N) of rand67 as COPIES block-diagonal copies: x repeated per copy, the weights of the small case, dy fresh
+    for every row; the kink margin is asserted on the small case, whose pre-activations are the only values the big one takes"""
+    case, ei, N, A, seed = R.layer_case(si, act, 'rand67')
+    assert_margin(case, A, act, 'many tiles: the small case, seed %d' % seed)
+    big = dict(case, x=case['x'].repeat(COPIES, 1))
+    big['dy'] = torch.randn(COPIES * N, case['dy'].size(1), generator=torch.Generator().manual_seed(seed + 1))
+    eib = (ei[:, None, :] + N * np.arange(COPIES, dtype=np.int64)[None, :, None]).reshape(2, -1)
+    return big, eib, COPIES * N
+
+
+@pytest.mark.parametrize('need_dx', [True, False])
+def test_many_tiles(dev, need_dx):
+    """769 tiles: the forward's workgroups make a second trip of their tile loop, the row pass gets two tiles per workgroup and a last
+    workgroup that owns one.  Reference: backward() / forward() of tests/_gin_ref.py, the float64 restatement and its float32 twin, fed
+    a SPARSE adjacency (torch.sparse_coo_tensor, coalesced: repeats summed, self loops kept) in place of the dense [N, N] one."""
+    from gnn_matlang_amd import _lib
+    from gnn_matlang_amd.graph import GraphCSR
+    si, act = 2, 'relu'
+    assert R.SHAPES[si] == (3, 20, 36, 2)
+    big, eib, N = many_tiles_case(si, act)
+    Fin, Fh, Fout, depth = R.SHAPES[si]
+    tiles = -(-N // 32)
+    L = _lib.lib()
+    P = int(L.gml_gin_dflat_floats(Fin, Fh, Fout, depth))
+    nwg, rest = divmod(int(L.gml_gin_bwd_workspace_bytes(N, Fin, Fh, Fout, depth)) // 4 - N * Fin, P)
+    tpw = -(-tiles // nwg)
+    print('many tiles: N %d, tiles %d, row-pass workgroups %d of %d tiles (the last: %d)' % (N, tiles, nwg, tpw, tiles - (nwg - 1) * tpw))
+    assert N == 24589 and tiles == MAXWG + 1                   # the forward: a second trip for workgroup 0 alone
+    assert rest == 0 and 1 < nwg < tiles and tpw == 2 and tiles - (nwg - 1) * tpw == 1
+    t = torch.from_numpy(eib)
+    A = torch.sparse_coo_tensor(torch.stack([t[1], t[0]]), torch.ones(t.size(1), dtype=torch.float64), (N, N)).coalesce()
+    ref64, ref32 = R.layer_ref('many tiles', big, A, act)
+    csr = GraphCSR.from_edge_index(t.to(dev), N)
+    check_layer(layer_gpu(dev, big, csr, act, need_dx), ref64, ref32, 'many tiles dx=%s' % need_dx, need_dx)
