@@ -1018,90 +1018,54 @@ class TallLinearFunction(torch.autograd.Function):
         return gx, gw, gb
 
 
-class HeadL1Function(torch.autograd.Function):
-    """loss = sum_{r < len(y)} valid[r] |fc2(relu(fc1 p[r])) - y[r]| (Zinc12k.py:343-345, :365) as ONE launch forward and ONE launch
-    backward (csrc/gml_head.hip) for small batches -- the reference's batch 64.  p [R, nin] pooled rows (R >= len(y): further rows,
-    e.g. the padding graph of a static batch, are ignored and get zero gradient)."""
-
-    @staticmethod
-    def forward(ctx, p, y, valid, w1, b1, w2, b2, loss_sum=None):
-        p = _f32c(p, 'pooled')
-        R, nin = p.shape
-        loss = torch.empty((), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            # loss_sum (optional, a float32 scalar on the device): += loss inside the same launch -- an epoch's running loss
-            with _Timed('head'):
-                _lib.call('gml_head_l1_fwd_acc', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                          int(R), int(y.numel()), int(nin), int(w1.size(0)), _ptr(loss), _ptr(loss_sum), _ptr(None), _stream(p.device))
-        ctx.save_for_backward(p, y, valid, w1, b1, w2, b2)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        p, y, valid, w1, b1, w2, b2 = ctx.saved_tensors
-        R, nin = p.shape
-        nh = int(w1.size(0))
-        gp = torch.empty(R, nin, dtype=torch.float32, device=p.device)
-        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
-        db1 = torch.empty_like(b1) if b1 is not None else None
-        db2 = torch.empty_like(b2) if b2 is not None else None
-        g = g.contiguous()
-        with torch.cuda.device(p.device):
-            with _Timed('head'):
-                _lib.call('gml_head_l1_bwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                          int(R), int(y.numel()), int(nin), nh, _ptr(g), _ptr(gp), nin, _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2),
-                          _stream(p.device))
-        return gp, None, None, dw1, db1, dw2, db2, None
+# The road of the readout head and its loss (models._step_loss; DESIGN s4.4c), decided ONCE, from plain values, BEFORE the model's
+# features run.  kind: 'l1_small' (csrc/gml_head.hip, one workgroup), 'l1_big' (gml_head_big.hip), 'bce' (gml_head_bce.hip), 'node'
+# (gml_node_head.hip) or 'torch'; pad_grad_zero: what model.features is told about a static batch's padding row; label: the PATHS text.
+HeadRoad = _collections.namedtuple('HeadRoad', 'kind pad_grad_zero label')
+HEAD_MLP32 = (False, 32, 'relu', True, None)       # models._MLP32, relu(fc1: nin -> 32) then fc2: the head row the L1 kernels serve
+_BCE_LABEL = 'fused BCE head (%d -> %d -> 1, %s)'
 
 
-class HeadL1BigFunction(torch.autograd.Function):
-    """HeadL1Function for any number of rows (nin = nh = 32; csrc/gml_head_big.hip): one pass + a fold each way instead of the ~16
-    launches of the general road (two library GEMMs, relu, the loss's elementwise chain and their backward) at the bench's batch size."""
+def head_road(loss, head, listed, nin, nh, nout, R, nl, num_graphs, f32=True, aligned=True, override=None, env=_os.environ):
+    """HeadRoad from plain values only (no tensor, no launch).  loss: 'l1' / 'bce' / 'node_sq'.  head: the model's _Head row (its
+    `between` is the BCE kernel's activation); listed: the model's class names that head for this loss (L1: the 'mlp32' row, BCE: its
+    _BCE_HEADS, node_sq: any).  fc1: nin -> nh, fc2: nh -> nout (node_sq: fc2: nin -> nout).  R: the rows model.features returns, nl:
+    the labels, num_graphs: the batch's own count.  f32, aligned: head_flags.  override: a kind -- only that road where it serves the
+    input, else 'torch' (tests, tools, the *_supported predicates).  GML_NO_HEAD_BIG / GML_NO_HEAD_BCE are read here and nowhere else."""
+    if not listed or nout != 1:
+        return HeadRoad('torch', False, "torch ops (%s on the model's own head)" % {'l1': 'L1', 'bce': 'BCE', 'node_sq': 'node loss'}[loss])
+    may = lambda kind: override in (None, kind)
+    ok = bool(f32 and aligned)
+    if loss == 'l1':
+        ok = ok and nl <= R
+        if (ok and may('l1_small') and R <= 256 and nin <= 64 and nh <= 64 and nin % 4 == 0 and nh % 4 == 0
+                and 4 * (R * nin + 2 * R * nh + 2 * R + nh * nin + 256) <= 160 * 1024):
+            # (the one workgroup gives the rows beyond nl a zero gradient: the pool need not mask the padding graph's)
+            return HeadRoad('l1_small', num_graphs <= 256 and nl <= num_graphs, 'fused L1 head, one workgroup (%d -> %d -> 1)' % (nin, nh))
+        if ok and may('l1_big') and nin == 32 and nh == 32 and R >= 1 and not env.get('GML_NO_HEAD_BIG'):
+            return HeadRoad('l1_big', False, 'fused L1 head, one pass + fold (32 -> 32 -> 1)')
+        return HeadRoad('torch', False, 'torch ops (L1 head outside the fused kernels)')
+    if loss == 'bce':                                      # (both roads give the padding graph's row a zero gradient)
+        if ok and may('bce') and 1 <= nin <= 64 and 1 <= nh <= 64 and R >= 1 and nl <= R and not env.get('GML_NO_HEAD_BCE'):
+            return HeadRoad('bce', True, _BCE_LABEL % (nin, nh, 'relu' if head[2] == 'relu' else 'identity'))
+        return HeadRoad('torch', True, 'torch ops (BCE head outside the fused kernel)')
+    if f32 and may('node') and 1 <= nin <= 64:
+        return HeadRoad('node', False, 'fused node head (%d -> 1)' % nin)
+    return HeadRoad('torch', False, 'torch ops (node head outside the fused kernel)')
 
-    @staticmethod
-    def forward(ctx, p, y, valid, w1, b1, w2, b2, loss_sum=None):
-        p = _f32c(p, 'pooled')
-        R, nin = p.shape
-        nws = int(_lib.lib().gml_head_l1_big_workspace_floats(int(R), int(nin), int(w1.size(0))))
-        ws = torch.empty(nws, dtype=torch.float32, device=p.device)
-        loss = torch.empty((), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            with _Timed('head'):
-                _lib.call('gml_head_l1_big_fwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                          int(R), int(y.numel()), int(nin), int(w1.size(0)), _ptr(loss), _ptr(loss_sum), _ptr(ws), nws, _stream(p.device))
-        ctx.save_for_backward(p, y, valid, w1, b1, w2, b2)
-        ctx.nws = nws
-        return loss
 
-    @staticmethod
-    def backward(ctx, g):
-        p, y, valid, w1, b1, w2, b2 = ctx.saved_tensors
-        R, nin = p.shape
-        nh = int(w1.size(0))
-        dev = p.device
-        gp = torch.empty(R, nin, dtype=torch.float32, device=dev)
-        ws = torch.empty(ctx.nws, dtype=torch.float32, device=dev)
-        g = g.contiguous()
-        npart = nh * nin + 2 * nh + 1
-        fq = _fold_queue()
-        if fq is not None:                                   # the partials stay in ws; the gradients are views of the flat buffer the fold fills
-            flat = torch.empty(npart, dtype=torch.float32, device=dev)
-            fq.append((ws, ctx.nws // npart, npart, [(flat, npart)]))
-            dw1, db1 = flat[:nh * nin].view_as(w1), (flat[nh * nin:nh * nin + nh] if b1 is not None else None)
-            dw2 = flat[nh * nin + nh:nh * nin + 2 * nh].view_as(w2)
-            db2 = flat[nh * nin + 2 * nh:] if b2 is not None else None
-            kd = (None,) * 4
-        else:
-            dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
-            db1 = torch.empty_like(b1) if b1 is not None else None
-            db2 = torch.empty_like(b2) if b2 is not None else None
-            kd = (dw1, db1, dw2, db2)
-        with torch.cuda.device(dev):
-            with _Timed('head'):
-                _lib.call('gml_head_l1_big_bwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                          int(R), int(y.numel()), int(nin), nh, _ptr(g), _ptr(gp), nin, _ptr(kd[0]), _ptr(kd[1]), _ptr(kd[2]), _ptr(kd[3]),
-                          _ptr(ws), ctx.nws, _stream(dev))
-        return gp, None, None, dw1, db1, dw2, db2, None
+def head_flags(loss, x, valid, w1, b1, w2, b2):
+    """(f32, aligned) of head_road.  f32: x, the head's parameters and (L1) the validity are float32 on x's CUDA device.  aligned: what
+    the launchers ask beyond shapes -- BCE: contiguous weights; L1: contiguous parameters, fc1.weight and fc2.weight on 16-byte
+    boundaries (gml_head.hip:141, gml_head_big.hip:236); node_sq: nothing."""
+    dev, f32 = x.device, x.is_cuda
+    for t in (x, w1, b1, w2, b2, valid if loss == 'l1' else None):
+        if t is not None and not (t.dtype == torch.float32 and t.device == dev):
+            f32 = False
+    if loss == 'node_sq' or not f32:
+        return f32, True
+    return f32, w1.is_contiguous() and w2.is_contiguous() and (loss == 'bce' or (
+        (b1 is None or b1.is_contiguous()) and (b2 is None or b2.is_contiguous()) and w1.data_ptr() % 16 == 0 and w2.data_ptr() % 16 == 0))
 
 
 def _head_bce_args(p, y, valid, w1, b1, w2, b2, stats):
@@ -1125,62 +1089,124 @@ def _head_bce_args(p, y, valid, w1, b1, w2, b2, stats):
     return p, y, valid, w1.contiguous(), c(b1), w2.contiguous(), c(b2)
 
 
-def _head_bce_ws(rows, nin, nh, dev):
-    nws = int(_lib.lib().gml_head_bce_workspace_floats(int(rows), int(nin), int(nh)))
-    return (torch.empty(nws, dtype=torch.float32, device=dev) if nws else None), nws
+# kind -> (forward entry, backward entry, workspace query or None): what the three pooled heads below differ in besides their
+# trailing arguments; 'l1_big' alone lets its weight-gradient partials join an open deferred_folds scope
+_HEAD_ENTRIES = dict(l1_small=('gml_head_l1_fwd_acc', 'gml_head_l1_bwd', None),
+                     l1_big=('gml_head_l1_big_fwd', 'gml_head_l1_big_bwd', 'gml_head_l1_big_workspace_floats'),
+                     bce=('gml_head_bce_fwd', 'gml_head_bce_bwd', 'gml_head_bce_workspace_floats'))
+
+
+def _head_call(entry, t, *tail):
+    """one launch of a pooled-head entry on t = (p, y, valid, w1, b1, w2, b2): the twelve common arguments, the entry's own, the stream"""
+    p, y, valid, w1, b1, w2, b2 = t
+    with torch.cuda.device(p.device):
+        with _Timed('head'):
+            _lib.call(entry, _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(p.size(0)),
+                      int(y.numel()), int(p.size(1)), int(w1.size(0)), *tail, _stream(p.device))
+
+
+def _head_ws(kind, p, w1, nws=None):
+    """(workspace or None, its floats) of one launch; nws: what the forward's query answered"""
+    q = _HEAD_ENTRIES[kind][2]
+    if nws is None:
+        nws = int(getattr(_lib.lib(), q)(int(p.size(0)), int(p.size(1)), int(w1.size(0)))) if q else 0
+    return (torch.empty(nws, dtype=torch.float32, device=p.device) if nws else None), nws
+
+
+def _pooled_head_fwd(ctx, kind, t, act, acc):
+    """loss = sum_{r < len(y)} valid[r] rowloss(fc2(act(fc1 p[r])), y[r]) in ONE pass.  Saves nothing but its inputs -- the backward
+    recomputes the forward --, no host read: capturable."""
+    p, w1 = t[0], t[3]
+    ws, nws = _head_ws(kind, p, w1)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    if kind == 'bce':                                       # (as ever: direct callers of HeadBCEFunction show in PATHS too)
+        _path('head', _BCE_LABEL % (int(p.size(1)), int(w1.size(0)), 'relu' if act else 'identity'))
+    L, A, Z = _ptr(loss), _ptr(acc), _ptr(None)                # (Z: the logits, which no training step asks for)
+    tail = (L, A, Z) if kind == 'l1_small' else (L, A, _ptr(ws), nws) if kind == 'l1_big' else (act, L, Z, A, _ptr(ws), nws)
+    _head_call(_HEAD_ENTRIES[kind][0], t, *tail)
+    ctx.save_for_backward(*t)
+    ctx.kind, ctx.act, ctx.nws = kind, act, nws
+    return loss
+
+
+def _pooled_head_bwd(ctx, g):
+    """(gp, None, None, dw1, db1, dw2, db2): the gradients of the seven tensor arguments, in ONE pass"""
+    t, kind = ctx.saved_tensors, ctx.kind
+    p, w1, b1, w2, b2 = t[0], t[3], t[4], t[5], t[6]
+    R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
+    gp = torch.empty(R, nin, dtype=torch.float32, device=dev)
+    ws, nws = _head_ws(kind, p, w1, ctx.nws)
+    g = g.contiguous().float()
+    fq = _fold_queue() if kind == 'l1_big' else None
+    if fq is not None:                                   # the partials stay in ws; the gradients are views of the flat buffer the fold fills
+        npart = nh * nin + 2 * nh + 1
+        flat = torch.empty(npart, dtype=torch.float32, device=dev)
+        fq.append((ws, nws // npart, npart, [(flat, npart)]))
+        dw1, db1 = flat[:nh * nin].view_as(w1), (flat[nh * nin:nh * nin + nh] if b1 is not None else None)
+        dw2 = flat[nh * nin + nh:nh * nin + 2 * nh].view_as(w2)
+        db2 = flat[nh * nin + 2 * nh:] if b2 is not None else None
+        kd = (None,) * 4
+    else:
+        dw1, db1, dw2, db2 = kd = tuple(torch.empty_like(v) if v is not None else None for v in (w1, b1, w2, b2))
+    tail = (_ptr(g), _ptr(gp), nin, _ptr(kd[0]), _ptr(kd[1]), _ptr(kd[2]), _ptr(kd[3])) + ((_ptr(ws), nws) if kind != 'l1_small' else ())
+    _head_call(_HEAD_ENTRIES[kind][1], t, *(((ctx.act,) if kind == 'bce' else ()) + tail))
+    return gp, None, None, dw1, db1, dw2, db2
+
+
+class HeadL1Function(torch.autograd.Function):
+    """loss = sum_{r < len(y)} valid[r] |fc2(relu(fc1 p[r])) - y[r]| (Zinc12k.py:343-345, :365) as ONE launch forward and ONE launch
+    backward (csrc/gml_head.hip) for small batches -- the reference's batch 64.  p [R, nin] pooled rows (R >= len(y): further rows,
+    e.g. the padding graph of a static batch, are ignored and get zero gradient).  loss_sum (optional, a float32 scalar on the
+    device): += loss inside the same launch -- an epoch's running loss."""
+
+    @staticmethod
+    def forward(ctx, p, y, valid, w1, b1, w2, b2, loss_sum=None):
+        return _pooled_head_fwd(ctx, 'l1_small', (_f32c(p, 'pooled'), y, valid, w1, b1, w2, b2), 1, loss_sum)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _pooled_head_bwd(ctx, g) + (None,)
+
+
+class HeadL1BigFunction(torch.autograd.Function):
+    """HeadL1Function for any number of rows (nin = nh = 32; csrc/gml_head_big.hip): one pass + a fold each way instead of the ~16
+    launches of the general road (two library GEMMs, relu, the loss's elementwise chain and their backward) at the bench's batch size."""
+
+    @staticmethod
+    def forward(ctx, p, y, valid, w1, b1, w2, b2, loss_sum=None):
+        return _pooled_head_fwd(ctx, 'l1_big', (_f32c(p, 'pooled'), y, valid, w1, b1, w2, b2), 1, loss_sum)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _pooled_head_bwd(ctx, g) + (None,)
 
 
 class HeadBCEFunction(torch.autograd.Function):
     """loss = sum_{r < len(y)} valid[r] BCE(fc2(act(fc1 p[r])), y[r]) on logits (exp_classify.py:293-295 / :260-262, :328-329) as
-    ONE pass forward and ONE backward for any number of rows (csrc/gml_head_bce.hip; act: 1 = relu, 0 = identity).  p [R, nin]
-    pooled rows (R >= len(y): further rows, the padding graph of a static batch, are ignored and get a zero gradient).  stats
+    ONE pass forward and ONE backward for any number of rows (csrc/gml_head_bce.hip; act: 1 = relu, 0 = identity).  p as above.  stats
     (optional, float32 [3] on the device) accumulates {loss, correct predictions, rows with valid != 0} in the same launch
-    (models.accuracy_from_stats).  Saves nothing but its inputs -- the backward recomputes the forward --, no host read: capturable."""
+    (models.accuracy_from_stats)."""
 
     @staticmethod
     def forward(ctx, p, y, valid, w1, b1, w2, b2, act, stats=None):
-        p, y, valid, w1, b1, w2, b2 = _head_bce_args(p, y, valid, w1, b1, w2, b2, stats)
-        R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
-        ws, nws = _head_bce_ws(R, nin, nh, dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        _path('head', 'fused BCE head (%d -> %d -> 1, %s)' % (nin, nh, 'relu' if act else 'identity'))
-        with torch.cuda.device(dev):
-            with _Timed('head'):
-                _lib.call('gml_head_bce_fwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                          R, int(y.numel()), nin, nh, int(bool(act)), _ptr(loss), _ptr(None), _ptr(stats), _ptr(ws), nws, _stream(dev))
-        ctx.save_for_backward(p, y, valid, w1, b1, w2, b2)
-        ctx.act = int(bool(act))
-        return loss
+        return _pooled_head_fwd(ctx, 'bce', _head_bce_args(p, y, valid, w1, b1, w2, b2, stats), int(bool(act)), stats)
 
     @staticmethod
     def backward(ctx, g):
-        p, y, valid, w1, b1, w2, b2 = ctx.saved_tensors
-        R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
-        gp = torch.empty(R, nin, dtype=torch.float32, device=dev)
-        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
-        db1 = torch.empty_like(b1) if b1 is not None else None
-        db2 = torch.empty_like(b2) if b2 is not None else None
-        ws, nws = _head_bce_ws(R, nin, nh, dev)
-        g = g.contiguous().float()
-        with torch.cuda.device(dev):
-            with _Timed('head'):
-                _lib.call('gml_head_bce_bwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                          R, int(y.numel()), nin, nh, ctx.act, _ptr(g), _ptr(gp), nin, _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2),
-                          _ptr(ws), nws, _stream(dev))
-        return gp, None, None, dw1, db1, dw2, db2, None, None
+        return _pooled_head_bwd(ctx, g) + (None, None)
+
+
+POOLED_HEADS = dict(l1_small=HeadL1Function, l1_big=HeadL1BigFunction, bce=HeadBCEFunction)     # HeadRoad.kind -> its function
 
 
 def head_bce_logits(p, y, valid, w1, b1, w2, b2, act):
     """(loss, logits [R]) of the fused BCE head, forward only (inspection and tests; no gradient)"""
     with torch.no_grad():
-        p, y, valid, w1, b1, w2, b2 = _head_bce_args(p, y, valid, w1, b1, w2, b2, None)
-        R, nin, nh, dev = int(p.size(0)), int(p.size(1)), int(w1.size(0)), p.device
-        ws, nws = _head_bce_ws(R, nin, nh, dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        pre = torch.empty(R, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call('gml_head_bce_fwd', _ptr(p), int(p.stride(0)), _ptr(y), _ptr(valid), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
-                      R, int(y.numel()), nin, nh, int(bool(act)), _ptr(loss), _ptr(pre), _ptr(None), _ptr(ws), nws, _stream(dev))
+        t = _head_bce_args(p, y, valid, w1, b1, w2, b2, None)
+        ws, nws = _head_ws('bce', t[0], t[3])
+        loss = torch.empty((), dtype=torch.float32, device=t[0].device)
+        pre = torch.empty(int(t[0].size(0)), dtype=torch.float32, device=t[0].device)
+        _head_call('gml_head_bce_fwd', t, int(bool(act)), _ptr(loss), _ptr(pre), _ptr(None), _ptr(ws), nws)
     return loss, pre
 
 
@@ -1188,15 +1214,11 @@ def head_bce_supported(p, w1, w2):
     """True when HeadBCEFunction serves these tensors: float32 CUDA tensors on one device, p [R >= 1, nin] with unit column stride
     (any row stride >= nin), fc1 weight [nh, nin] and fc2 weight [1, nh] with 1 <= nin, nh <= 64.  The kernel asks no more than float
     alignment, which every float32 tensor has.  False sends the caller to the torch-op road."""
-    ts = (p, w1, w2)
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == p.device for t in ts):
+    if not (all(isinstance(t, torch.Tensor) for t in (p, w1, w2)) and p.dim() == w1.dim() == w2.dim() == 2):
         return False
-    if p.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or p.size(0) < 1:
-        return False
-    nin, nh = int(p.size(1)), int(w1.size(0))
-    return (1 <= nin <= 64 and 1 <= nh <= 64 and int(w1.size(1)) == nin and tuple(w2.shape) == (1, nh)
-            and p.stride(1) == 1 and p.stride(0) >= nin and w1.is_contiguous() and w2.is_contiguous()
-            and not _os.environ.get('GML_NO_HEAD_BCE'))
+    return (w1.size(1) == p.size(1) and w2.size(1) == w1.size(0) and p.stride(1) == 1 and p.stride(0) >= p.size(1) and
+            head_road('bce', HEAD_MLP32, True, int(p.size(1)), int(w1.size(0)), int(w2.size(0)), int(p.size(0)), 0, 0,
+                      *head_flags('bce', p, None, w1, None, w2, None), 'bce').kind == 'bce')
 
 
 class NodeHeadLossFunction(torch.autograd.Function):
@@ -1246,19 +1268,18 @@ class NodeHeadLossFunction(torch.autograd.Function):
 
 
 def node_head_supported(x, fc2):
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and 1 <= int(x.size(1)) <= 64 and int(fc2.weight.size(0)) == 1
-            and fc2.weight.dtype == torch.float32)
+    return head_road('node_sq', None, True, int(x.size(-1)), 0, int(fc2.weight.size(0)), 0, 0, 0,
+                     x.dim() == 2 and head_flags('node_sq', x, None, fc2.weight, None, None, None)[0], True, 'node').kind == 'node'
 
 
 def head_l1_big_supported(p, w1, w2):
-    return (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and int(p.size(1)) == 32 and tuple(w1.shape) == (32, 32)
-            and tuple(w2.shape) == (1, 32) and p.size(0) > 0 and not _os.environ.get('GML_NO_HEAD_BIG'))
+    return (p.dim() == 2 and tuple(w1.shape) == (32, 32) and tuple(w2.shape) == (1, 32) and
+            head_road('l1', HEAD_MLP32, True, int(p.size(1)), 32, 1, int(p.size(0)), 0, 0, p.is_cuda and p.dtype == torch.float32, True, 'l1_big').kind == 'l1_big')
 
 
 def head_l1_supported(p, w1, w2):
-    R, nin, nh = int(p.size(0)), int(p.size(1)), int(w1.size(0))
-    return (p.is_cuda and p.dtype == torch.float32 and R <= 256 and nin <= 64 and nh <= 64 and int(w2.size(0)) == 1
-            and nin % 4 == 0 and nh % 4 == 0 and 4 * (R * nin + 2 * R * nh + 2 * R + nh * nin + 256) <= 160 * 1024)
+    return head_road('l1', HEAD_MLP32, True, int(p.size(1)), int(w1.size(0)), int(w2.size(0)), int(p.size(0)), 0, 0,
+                     p.is_cuda and p.dtype == torch.float32).kind == 'l1_small'
 
 
 def tall_linear(x, lin):

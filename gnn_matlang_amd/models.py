@@ -1145,50 +1145,36 @@ def zinc_loss(pre, y):                     # Zinc12k.py:365
     return F.l1_loss(pre, y.unsqueeze(-1), reduction='sum')
 
 
-def zinc_step_loss(model, data, valid=None, loss_sum=None):
-    """zinc_loss(model(data), data.y) -- with the head and the loss as ONE launch each way where the batch is small enough for it
-    (functional.HeadL1Function: the reference's batch 64; a static batch's padding graph and absent slots are masked through
-    `valid` / data.graph_valid).  Same value and gradients up to summation order; large batches take the general path."""
-    valid = _graph_valid(valid, data)
-    # the fused roads serve fc2(relu(fc1 x)) with fc1: nin -> 32 (head 'mlp32' of GNNML3 and GNNML1Blocks), one output
-    if model._HEADS[model.head] == _MLP32 and model.fc2.weight.size(0) == 1 and data.x.is_cuda:
-        nl = int(data.y.numel()) if valid is None else int(valid.numel())
-        ng = int(data.num_graphs) if hasattr(data, 'num_graphs') else nl
-        small = ng <= 256                                   # (the one-workgroup head: its rows beyond nl get a zero gradient)
-        x = model.features(data, pad_grad_zero=small and nl <= ng)
-        if Fn.head_l1_supported(x, model.fc1.weight, model.fc2.weight) and nl <= x.size(0):
-            y = data.y[:nl].float().contiguous()
-            return Fn.HeadL1Function.apply(x, y, valid, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias, loss_sum)
-        if small and nl <= ng:                              # (not the fused head after all: the promise above does not hold -- redo)
-            x = model.features(data)
-        if Fn.head_l1_big_supported(x, model.fc1.weight, model.fc2.weight) and nl <= x.size(0):
-            # any batch size: one pass + a fold each way (rows beyond nl -- a static batch's padding graph -- get a zero gradient)
-            y = data.y[:nl].float().contiguous()
-            return Fn.HeadL1BigFunction.apply(x, y, valid, model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias, loss_sum)
-        pre = _apply_head(model, x)
-    else:
-        pre = model(data)
-    if valid is not None:
-        l = _valid_sum(lambda p, y: (p[:, 0] - y).abs(), pre, data.y, valid)
-    else:
-        l = zinc_loss(pre, data.y)
+def _exp_head(model, loss='bce'):
+    """(fc1, fc2, act) of a model whose head the fused kernels of `loss` may serve, act = 1 (relu) / 0 (identity), else None.  'l1':
+    the row 'mlp32'; 'bce': a head that is fc2(act(fc1 x)) and nothing else AND that its class lists in _BCE_HEADS -- the description
+    alone would also admit GNNML3 'mlp32' and GAT 'mlp', which have never taken the fused BCE road: widening it is a change of
+    behaviour, not of this function."""
+    h = getattr(model, '_HEADS', {}).get(getattr(model, 'head', None))            # (PPGN, DSSGCN: no head name at all)
+    if h is None or not (h == _MLP32 if loss == 'l1' else model.head in getattr(model, '_BCE_HEADS', ())):
+        return None
+    assert h.fc1 and h.fc2 and not h.bn1 and h.out is None, h
+    return model.fc1, model.fc2, int(h.between == 'relu')
+
+
+def _l1_torch(pre, data, nl, valid, loss_sum, ntask):
+    l = _valid_sum(lambda p, y: (p[:, 0] - y).abs(), pre, data.y, valid) if valid is not None else zinc_loss(pre, data.y)
     if loss_sum is not None:
         loss_sum.add_(l.detach())
     return l
 
 
-def filtering_loss(pre, y, mask, ntask=0):   # filtering.py:320
-    return torch.square(mask * (pre - y[:, ntask:ntask + 1])).sum()
+def _bce_torch(pre, data, nl, valid, stats, ntask):
+    loss = exp_classify_loss(pre, data.y, valid)
+    if stats is not None:
+        with torch.no_grad():
+            v = valid if valid is not None else torch.ones(nl, dtype=pre.dtype, device=pre.device)
+            ok = ((pre[:nl, 0] > 0) == (data.y[:nl] == 1)).to(pre.dtype)
+            stats[:3].add_(torch.stack([loss.detach(), (ok * v).sum(), (v != 0).to(pre.dtype).sum()]))
+    return loss
 
 
-def filtering_step_loss(model, data, ntask=0, stats=None, _road=None):
-    """filtering_loss(model(data), data.y, data.mask, ntask) -- the ``loss_fn(model, data)`` of dist.TrainStep -- with the readout
-    fc2, the masked loss and the sums of R^2 as ONE launch each way (functional.NodeHeadLossFunction).  stats: optional float32 [4]
-    on the device, receives {loss, ss_res, ss_tot, count} over the rows with mask == 1 (r2_from_stats); no host read."""
-    x = model.forward(data, _features=True, _road=_road)
-    if Fn.node_head_supported(x, model.fc2):
-        return Fn.NodeHeadLossFunction.apply(x, model.fc2.weight, model.fc2.bias, data.y, data.mask, int(ntask), stats)[0]
-    pre = tall_linear(x, model.fc2)
+def _node_sq_torch(pre, data, nl, valid, stats, ntask):
     loss = filtering_loss(pre, data.y, data.mask, ntask)
     if stats is not None:
         with torch.no_grad():
@@ -1198,6 +1184,59 @@ def filtering_step_loss(model, data, ntask=0, stats=None, _road=None):
             ybar = (m * yt).sum() / cnt.clamp(min=1)
             stats[:4].copy_(torch.stack([loss.detach(), (m * (yt - pre) ** 2).sum(), (m * (yt - ybar) ** 2).sum(), cnt]))
     return loss
+
+
+_TORCH_ROADS = dict(l1=_l1_torch, bce=_bce_torch, node_sq=_node_sq_torch)
+
+
+def _step_loss(loss, model, data, valid=None, acc=None, ntask=0, _road=None, _head_road=None):
+    """What zinc_step_loss, exp_classify_step_loss and filtering_step_loss share.  The road of the head is ONE record
+    (functional.head_road) built from host values before any layer runs; the model's features run ONCE, with the record's
+    pad_grad_zero; then the fused head of the record's kind, or the torch-op road of the same loss with its acc arithmetic.  A model
+    whose head no fused kernel of this loss may serve runs its own forward.  _head_road: the record's override ('torch': tests, tools)."""
+    node = loss == 'node_sq'
+    head = (None, model.fc2, 0) if node else _exp_head(model, loss)
+    nl = 0 if node else int(data.y.numel()) if valid is None else int(valid.numel())
+    if head is None or not (node or int(head[1].weight.size(0)) == 1):
+        Fn._path('head', Fn.head_road(loss, None, False, 0, 0, 0, 0, nl, 0).label)
+        return _TORCH_ROADS[loss](model(data), data, nl, valid, acc, ntask)
+    fc1, fc2, act = head
+    w2, b2 = fc2.weight, fc2.bias
+    w1, b1 = (None, None) if node else (fc1.weight, fc1.bias)
+    R, nin = int(data.x.size(0)) if node else int(data.ptr.numel()) - 1, int((w2 if node else w1).size(1))
+    road = Fn.head_road(loss, None if node else model._HEADS[model.head], True, nin, int(w2.size(1)), int(w2.size(0)), R, nl,
+                        int(data.num_graphs) if hasattr(data, 'num_graphs') else nl,
+                        *Fn.head_flags(loss, data.x, valid, w2 if node else w1, b1, w2, b2), _head_road)
+    if road.kind != 'bce':                                  # (HeadBCEFunction writes its own entry, for direct callers too)
+        Fn._path('head', road.label)
+    x = model.forward(data, _features=True, _road=_road) if node else model.features(data, pad_grad_zero=road.pad_grad_zero)
+    if road.kind == 'torch':
+        return _TORCH_ROADS[loss](tall_linear(x, fc2) if node else _apply_head(model, x), data, nl, valid, acc, ntask)
+    # the postcondition of features that the record was built on
+    assert x.dim() == 2 and (node or x.size(0) == R) and x.size(1) == nin and x.dtype == torch.float32 and x.stride(1) == 1, (road, x.shape, x.dtype)
+    if node:
+        return Fn.NodeHeadLossFunction.apply(x, w2, b2, data.y, data.mask, int(ntask), acc)[0]
+    y = data.y[:nl] if road.kind == 'bce' else data.y[:nl].float().contiguous()
+    return Fn.POOLED_HEADS[road.kind].apply(x, y, valid, w1, b1, w2, b2, *((act, acc) if road.kind == 'bce' else (acc,)))
+
+
+def zinc_step_loss(model, data, valid=None, loss_sum=None, _head_road=None):
+    """zinc_loss(model(data), data.y) -- with the head and the loss as ONE launch each way where a kernel serves the batch
+    (functional.head_road: 'l1_small', the reference's batch 64, or 'l1_big', any size; a static batch's padding graph and absent slots
+    are masked through `valid` / data.graph_valid).  Same value and gradients up to summation order; other heads take the torch ops."""
+    return _step_loss('l1', model, data, _graph_valid(valid, data), loss_sum, _head_road=_head_road)
+
+
+def filtering_loss(pre, y, mask, ntask=0):   # filtering.py:320
+    return torch.square(mask * (pre - y[:, ntask:ntask + 1])).sum()
+
+
+def filtering_step_loss(model, data, ntask=0, stats=None, _road=None, _head_road=None):
+    """filtering_loss(model(data), data.y, data.mask, ntask) -- the ``loss_fn(model, data)`` of dist.TrainStep -- with the readout
+    fc2, the masked loss and the sums of R^2 as ONE launch each way (functional.NodeHeadLossFunction).  stats: optional float32 [4]
+    on the device, receives {loss, ss_res, ss_tot, count} over the rows with mask == 1 (r2_from_stats); no host read.  _road: the
+    model's (GNNML3.forward)."""
+    return _step_loss('node_sq', model, data, None, stats, ntask, _road, _head_road)
 
 
 def r2_from_stats(stats):
@@ -1214,43 +1253,13 @@ def exp_classify_loss(pre, y, valid=None):   # exp_classify.py:328-329
     return _valid_sum(_bce_rows, pre, y, valid)
 
 
-def _exp_head(model):
-    """(fc1, fc2, act) of a model whose head is fc2(act(fc1 x)) and nothing else, act = 1 (relu) / 0 (identity).  Only for the heads a
-    class lists in _BCE_HEADS: the description alone would also admit GNNML3 'mlp32' and GAT 'mlp', which have never taken the
-    fused BCE road -- widening it is a change of behaviour, not of this function."""
-    if getattr(model, 'head', None) not in getattr(model, '_BCE_HEADS', ()):           # (PPGN, DSSGCN: no head name at all)
-        return None
-    h = model._HEADS[model.head]
-    assert h.fc1 and h.fc2 and not h.bn1 and h.out is None, h
-    return model.fc1, model.fc2, int(h.between == 'relu')
-
-
-def exp_classify_step_loss(model, data, valid=None, stats=None):
+def exp_classify_step_loss(model, data, valid=None, stats=None, _head_road=None):
     """exp_classify_loss(model(data), data.y) -- the ``loss_fn(model, data)`` of dist.TrainStep -- with the head, the loss, the
-    number of correct predictions and their backward as ONE launch each way (functional.HeadBCEFunction) where the head is
+    number of correct predictions and their backward as ONE launch each way (functional.head_road: 'bce') where the head is
     fc2(act(fc1 x)) with one output and at most 64 units a side; otherwise the torch-op road.  Plain and padded static batches
     (valid = data.graph_valid), training and evaluation under torch.no_grad() alike.  stats: optional float32 [3] on the device,
     ACCUMULATES {loss, correct predictions, graphs counted} (accuracy_from_stats); no host read."""
-    valid = _graph_valid(valid, data)
-    nl = int(data.y.numel()) if valid is None else int(valid.numel())
-    head = _exp_head(model)
-    if head is not None and int(head[1].weight.size(0)) == 1:
-        fc1, fc2, act = head
-        x = model.features(data, pad_grad_zero=True)          # (both roads below give the padding graph's row a zero gradient)
-        if Fn.head_bce_supported(x, fc1.weight, fc2.weight) and nl <= x.size(0):
-            return Fn.HeadBCEFunction.apply(x, data.y[:nl], valid, fc1.weight, fc1.bias, fc2.weight, fc2.bias, act, stats)
-        Fn._path('head', 'torch ops (BCE head outside the fused kernel)')
-        pre = _apply_head(model, x)
-    else:
-        Fn._path('head', 'torch ops (BCE on the model\'s own head)')
-        pre = model(data)
-    loss = exp_classify_loss(pre, data.y, valid)
-    if stats is not None:
-        with torch.no_grad():
-            v = valid if valid is not None else torch.ones(nl, dtype=pre.dtype, device=pre.device)
-            ok = ((pre[:nl, 0] > 0) == (data.y[:nl] == 1)).to(pre.dtype)
-            stats[:3].add_(torch.stack([loss.detach(), (ok * v).sum(), (v != 0).to(pre.dtype).sum()]))
-    return loss
+    return _step_loss('bce', model, data, _graph_valid(valid, data), stats, _head_road=_head_road)
 
 
 # freqclass.py:368-375 / :385-390: the same sum BCE on sigmoid(pre[:, 0]) and the same count of round(sigmoid) == y.  The head of
